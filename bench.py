@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Paillier array encryption on MI355X (BASELINE.json metric and configs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {0,1,2,3,4}] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {0,1,2,3,4}] [--dump-outputs DIR] [--full] ...
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU, RCCL over xGMI)
 
 `--gpus N > 1` without a torch.distributed launcher (no WORLD_SIZE in the environment) starts the N rank
@@ -11,7 +11,7 @@ code; under torchrun the ranks come from the environment.
 Workloads (BASELINE.json configs; synthetic float32 N(0,1) vectors, seeded keys):
   --config 1 (default at every N): nb = 2048, 1 048 576 elements per GPU, device-resident encryption
              (the headline metric "Paillier-2048 encrypts/sec (device-resident), 1M-elem float32 array");
-             weak scaling, no data-path collective (elements are independent). The same run times the
+             weak scaling, no data-path collective (elements are independent). With --full the same run times the
              configs[3] leg below as `extra.config3_strong` unless --no-strong;
   --config 3: nb = 2048, 16 777 216 elements in total, sharded over the N ranks
              (strong scaling: 2M per GPU at N = 8), ciphertext shards reassembled on every rank by an
@@ -24,6 +24,13 @@ keyed by the GLOBAL element index (ciphertexts do not depend on N). A key holder
 fixed-base sampler (kernels_fb.hpp; its tables are built, and timed under `setup`, before the timed
 region). `value` = elements of the whole job per second over the K timed steps (barrier + synchronize
 on both sides, max over ranks).
+
+A plain run does only that: it sets up (key, context, tables), warms up, times the K steps and prints the result
+line (`ms_per_step` = the timed region / K). `--dump-outputs DIR` also writes the last timed step's outputs as
+DIR/<name>.npy (dump_outputs; it implies --deterministic, so two runs with the same arguments are comparable output
+for output). Every other leg described here (the decrypt check of the timed output, `cpu_baseline` and the oracle
+checks, the public-key, generic, nb = 1024, configs[2] and configs[3] legs, the host boundary, fresh keys, the
+all-gather contention rehearsal) runs only with `--full`, where the --no-* options choose among them.
 
 Rank 0 prints ONE JSON line. `roofline` is for the dominant kernel of the timed path, its duration
 timed live with HIP events recorded on the launch stream between the kernels of every timed call; its
@@ -615,6 +622,40 @@ def nb1024_leg(args, dev, stream, lib, rng_key, x, local_rank, base, steps=5):
     return leg, check
 
 
+DUMP_ROWS = 16384           # rows of a ciphertext array that --dump-outputs keeps (nb = 2048: 16 MiB as float64)
+DUMP_SEED = 20240229
+
+
+def dump_rows(n: int) -> np.ndarray:
+    """The rows --dump-outputs keeps of an n-row output: all of them up to DUMP_ROWS, else a fixed seeded sample
+    (sorted, so that it is the same from run to run and from build to build)."""
+    if n <= DUMP_ROWS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_ROWS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname: str, rows: np.ndarray, words=None, exps=None, values=None) -> dict:
+    """--dump-outputs: what the timed path's last step handed its caller, as <dirname>/<name>.npy in float64 (exact for
+    32-bit words): `sample_index` (the rows kept, dump_rows), `ciphertext_words` [rows, W] (unsigned 32-bit words,
+    least significant first) and `exponents` [rows] of the device tensors words/exps at those rows, and `values`
+    (every element of up to 4M, else the same rows) where the step ends in a decryption. Returns {name: shape}."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"sample_index": rows.astype(np.float64)}
+    idx = torch.from_numpy(rows)
+    if words is not None:
+        arrays["ciphertext_words"] = words[idx.to(words.device)].cpu().numpy().view(np.uint32).astype(np.float64)
+        arrays["exponents"] = exps[idx.to(exps.device)].cpu().numpy().astype(np.float64)
+    if values is not None:
+        whole = values.numel() <= (4 << 20)      # 32 MiB; a longer vector is kept at the sample rows
+        arrays["values"] = (values if whole else values[idx.to(values.device)]).cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
+FULL_ONLY_LEGS = ("cpu_baseline", "decrypt", "public", "add8", "host", "strong", "contention", "nb1024")
+
+
 def selftest_cpu(args) -> None:
     """The launcher's CPU self-test (tests/test_bench_launcher.py): gloo ranks, each contributes a shard
     of rank-stamped rows, one all-gather through sharding.gather_shards; rank 0 prints the world as the
@@ -682,8 +723,26 @@ def main():
     ap.add_argument("--no-nb1024", action="store_true",
                     help="skip the nb = 1024 leg (configs[1]'s vector under a 1024-bit key: fixed-base encrypt, decrypt, "
                          "public-key path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the timed steps (decrypt check, CPU baseline and oracle checks, "
+                         "public-key and generic paths, configs[2]/[3] legs, nb = 1024, host boundary, fresh key, "
+                         "all-gather contention); the --no-* options choose among them. Without it a run sets up, "
+                         "warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (float64; ciphertexts "
+                         "at a fixed seeded sample of rows); implies --deterministic, so that two runs with the same "
+                         "arguments encrypt the same inputs under the same obfuscators: the timed run then uses the "
+                         "fixed obfuscator key instead of a fresh one (`obfuscator_key` in the result line; the work "
+                         "per step is the same). With --gpus N > 1 only rank 0 writes, and only its own shard")
     ap.add_argument("--selftest-cpu", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        for leg in FULL_ONLY_LEGS:
+            setattr(args, "no_" + leg, True)
+    if args.dump_outputs:
+        args.deterministic = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -904,6 +963,15 @@ def main():
                                                "by the job's elements per step, bench.py step_base)"}
     stage_avg = [float(np.mean([s[i] for s in stage_ms])) for i in range(len(stage_ms[0]))] if stage_ms else []
 
+    # ---- --dump-outputs: the last timed step's outputs as this rank's caller receives them (rank 0 writes its own)
+    if args.dump_outputs and rank == 0:
+        if cfg_id == 2:
+            shapes = dump_outputs(args.dump_outputs, dump_rows(N), sum_ct, sum_ex, val8)
+        else:
+            shapes = dump_outputs(args.dump_outputs, dump_rows(n_real), ct, ex)
+        extra["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": shapes, "dtype": "float64",
+                                   "obfuscator_index_base": index_base_chk}
+
     # ---- correctness of the timed output: decrypt on the device, compare with the input exactly
     if not args.no_decrypt and cfg_id != 2:
         val = torch.empty(N, dtype=torch.float64, device=dev)
@@ -1082,7 +1150,7 @@ def main():
 
     # ---- a freshly generated key (VERDICT r2 Missing #4): context + private key + the first device-RNG call,
     # setup included, at the library defaults (W = 16 tables, built only past the break-even count)
-    if solo and cfg_id == 1 and use_fb:
+    if args.full and solo and cfg_id == 1 and use_fb:
         fresh = {}
         for label, nf, seed, nbf in (("first_1M_call", N, 2, nb), ("first_1k_call", 1000, 3, nb),
                                      ("first_1k_call_nb1024", 1000, 4, 1024)):
@@ -1127,7 +1195,7 @@ def main():
     S_chk = min(N, cpu_sample)
     # ---- the generic CRT path on the same input (untimed): bit-reproducible against GMP
     ct_ref = ct
-    if use_fb and solo:
+    if args.full and use_fb and solo:
         ct_ref = torch.empty_like(ct)
         ex_ref = torch.empty_like(ex)
         ctx.set_fixed_base(False)
@@ -1152,9 +1220,10 @@ def main():
                 "value": n_gen / (sum(gen_ms) * 1e-3), "unit": "encrypts/s per GPU", "elements": n_gen,
                 "note": "no lane CRT at nb = 4096: r from the ChaCha20 stream, r^n mod n^2 by the public-key "
                         "kernel k_encrypt<8>; bit-identical to the GMP baseline"}
-    ct_host_check = ct_ref[:S_chk].cpu().numpy().view(np.uint32).copy()
-    ex_host_check = ex[:S_chk].cpu().numpy().copy()
-    ct_timed_check = ct[:S_chk].cpu().numpy().view(np.uint32).copy()
+    if args.full:    # host copies for the host-boundary and cpu_baseline legs
+        ct_host_check = ct_ref[:S_chk].cpu().numpy().view(np.uint32).copy()
+        ex_host_check = ex[:S_chk].cpu().numpy().copy()
+        ct_timed_check = ct[:S_chk].cpu().numpy().view(np.uint32).copy()
 
     # ---- the public-key path on the same input (untimed region), for the record and as a parity check
     if holder and (use_crt or use_fb) and not args.no_public and solo:
@@ -1565,6 +1634,8 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3,
+        "full": args.full,
+        "obfuscator_key": "fixed (--deterministic)" if args.deterministic else "os.urandom",
         "higher_is_better": True,
         "scaling": cfg["shard"],
         "vs_baseline": None,

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/abdec4
 mkdir -p $O
 cd $R
-BA="--config 4 --n 1048576 --steps 1 --warmup 0 --no-cpu-baseline --no-host --no-add8 --no-strong --no-contention --no-public"
+BA="--full --config 4 --n 1048576 --steps 1 --warmup 0 --no-cpu-baseline --no-host --no-add8 --no-strong --no-contention --no-public"
 for rep in 1 2; do
   for v in base occ1; do
     L=""; [ $v = occ1 ] && L=$R/ab/libflexpai_dec4occ1.so

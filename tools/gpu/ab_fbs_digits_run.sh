@@ -13,7 +13,7 @@ BA="--steps 10 --warmup 2 --no-cpu-baseline --no-host --no-public --no-add8 --no
 for rep in 1 2 3; do
   for v in base D; do
     L=""; [ $v = D ] && L=$R/ab/libflexpai_abD.so
-    A="$BA"; [ $v = D ] && [ $rep = 1 ] && A="--steps 10 --warmup 2 --no-cpu-baseline --no-host --no-public --no-add8 --no-strong --no-contention"
+    A="$BA"; [ $v = D ] && [ $rep = 1 ] && A="--full --steps 10 --warmup 2 --no-cpu-baseline --no-host --no-public --no-add8 --no-strong --no-contention"
     FLEXPAI_LIB=$L timeout -k 10 240 python -u bench.py $A > $O/bench_${v}_$rep.log 2>&1 || { echo "bench $v failed"; tail -5 $O/bench_${v}_$rep.log; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); e=d['extra']; print(sys.argv[2], sys.argv[3], round(d['value']/1e6,3), round(d['ms_per_step'],3), json.dumps({k: round(v['kernel_ms'],3) for k, v in e['stages'].items()}), e.get('roundtrip_exact'))" $O/bench_${v}_$rep.log $v $rep
   done

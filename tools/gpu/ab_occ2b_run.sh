@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/abocc2b
 mkdir -p $O
 cd $R
-BA="--steps 2 --warmup 1 --no-cpu-baseline --no-host --no-add8 --no-strong --no-contention --no-public --no-decrypt"
+BA="--full --steps 2 --warmup 1 --no-cpu-baseline --no-host --no-add8 --no-strong --no-contention --no-public --no-decrypt"
 for rep in 1 2; do
   for v in base occ2b; do
     L=""; [ $v = occ2b ] && L=$R/ab/libflexpai_occ2b.so

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/abocc
 mkdir -p $O
 cd $R
-BA="--steps 2 --warmup 1 --no-cpu-baseline --no-host --no-add8 --no-strong --no-contention --no-public"
+BA="--full --steps 2 --warmup 1 --no-cpu-baseline --no-host --no-add8 --no-strong --no-contention --no-public"
 for rep in 1 2; do
   for v in base occ2; do
     L=""; [ $v = occ2 ] && L=$R/ab/libflexpai_occ2.so

@@ -3,7 +3,7 @@
 # chained so that the first failure ends the call; logs under gpurun_out/, names prefixed with TAG:
 #   0. the address-guarded sampler suite (tests/test_gpu_guard.py on libflexpai_xcheck.so; NO_GUARD=1 skips);
 #   1. the -m gpu parity tests (TESTS="tests/test_x.py ..." for a subset; NO_TESTS=1 skips), one process;
-#   2. one bench line (BENCH_ARGS; NO_BENCH=1 skips);
+#   2. one bench line with every leg (bench.py --full $BENCH_ARGS; NO_BENCH=1 skips);
 #   3. PROF=1: a rocprofv3 --kernel-trace --stats profile of bench.py $PROF_ARGS (summary: ${TAG}_prof/run_kernel_stats.csv);
 #   4. PMC="FETCH_SIZE WRITE_SIZE ...": one rocprofv3 --pmc pass per counter set (sets separated by ';'), each with
 #      --kernel-trace only (MI355X_MICROARCH.md's HBM section: separate passes), over bench.py $PMC_ARGS.
@@ -27,10 +27,10 @@ if [ -z "$NO_TESTS" ]; then
   [ $rc -ne 0 ] && { echo "pytest failed rc=$rc"; grep -E "FAILED|Error|error" $O/${T}_pytest_gpu.log | head -20; exit 1; }
 fi
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py ${BENCH_ARGS:-} > $O/${T}_bench.log 2>&1 || { echo "bench failed rc=$?"; tail -30 $O/${T}_bench.log; exit 1; }
+  timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py --full ${BENCH_ARGS:-} > $O/${T}_bench.log 2>&1 || { echo "bench failed rc=$?"; tail -30 $O/${T}_bench.log; exit 1; }
   tail -1 $O/${T}_bench.log | cut -c1-800
 fi
-PA=${PROF_ARGS:---steps 5 --warmup 2 --no-cpu-baseline --no-host --no-public --no-add8 --no-strong --no-contention}
+PA=${PROF_ARGS:---full --steps 5 --warmup 2 --no-cpu-baseline --no-host --no-public --no-add8 --no-strong --no-contention}
 if [ -n "$PROF" ]; then
   timeout -k 10 ${PROF_TIMEOUT:-400} rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -o run -- python3 bench.py $PA > $O/${T}_prof.log 2>&1 || { echo "prof failed rc=$?"; tail -20 $O/${T}_prof.log; exit 1; }
   tail -1 $O/${T}_prof.log | cut -c1-400
