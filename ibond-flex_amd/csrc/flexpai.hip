@@ -54,6 +54,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_mul.hpp"
 #include "engine_crtw.hpp"
 #include "engine_pe1.hpp"
+#include "engine_pe4.hpp"
 
 using namespace fpai;
 
@@ -135,6 +136,10 @@ struct pai_ctx {
   uint32_t *d_pe1_n = nullptr, *d_pe1_one = nullptr, *d_pe1_prog = nullptr, *d_pe1_r2n = nullptr;
   int pe1_nprog = 0;
   uint32_t pe1_mprime = 0;
+  // public-key encryption of n of 2049..4096 bits on pair groups over the 152 limbs of n (kernels_pe4.hpp); taken by
+  // contexts without the private key ($FLEXPAI_PAIR=0, test build: k_encrypt)
+  bool pe4_ok = false;
+  Pe4Const* d_pe4 = nullptr;
   bool pef_ok = false;          // the factored public-key chain (k_pe_pow_f) is set up ($FLEXPAI_PEF=0, test build: off)
   PeConst* d_pe = nullptr;
   uint32_t *d_pe_n = nullptr, *d_pe_r2 = nullptr, *d_pe_oneR = nullptr;   // n, R^2, R mod n (R = 2^(28 74)): the batch
@@ -729,6 +734,7 @@ int pai_device_count(int* count) {
 
 static int setup_pe(pai_ctx* c, const HBig& n);
 static int setup_pe1(pai_ctx* c, const HBig& n);
+static int setup_pe4(pai_ctx* c, const HBig& n);
 
 int pai_ctx_create(const uint8_t* n_le, size_t n_bytes, int device, pai_ctx** out) {
   if (!n_le || !out || n_bytes == 0) return fail(PAI_ERR_ARG, "pai_ctx_create: null argument");
@@ -787,7 +793,7 @@ int pai_ctx_create(const uint8_t* n_le, size_t n_bytes, int device, pai_ctx** ou
       (rc = upload(c, R2.limbs(c->S_e, LB), &c->d_R2)) ||
       (rc = upload(c, n.limbs(c->S_e, LB), &c->d_nl)) || (rc = upload(c, prog, &c->d_prog)) ||
       (rc = upload(c, oneR.limbs(c->S_e, LB), &c->d_oneR)) || (rc = (SetupTrace("  setup_pe"), setup_pe(c, n))) ||
-      (rc = setup_pe1(c, n))) {
+      (rc = setup_pe1(c, n)) || (rc = setup_pe4(c, n))) {
     delete c;
     return rc;
   }
@@ -988,6 +994,36 @@ static int setup_pe1(pai_ctx* c, const HBig& n) {
   c->d_pe1_r2n = dr2;
   c->pe1_mprime = mp;
   c->pe1_ok = true;
+  return 0;
+}
+
+// Public-key encryption on pair groups (kernels_pe4.hpp) for n of 2049..4096 bits: S = 152 limbs of n, R = 2^(28 S)
+// >= 2^24 n. Constants: n, (1 - R) and (1 - R^2) mod n, the pair of R^3 mod n^2, the op list for n; for k_pe4_fin
+// n^2 and n R' mod n^2 on the 296 limbs of the L = 37 group engine (R' = 2^(28 296)).
+static int setup_pe4(pai_ctx* c, const HBig& n) {
+  bool pair = true;
+  if (const char* e = xcheck_env("FLEXPAI_PAIR")) pair = atoi(e) != 0;
+  const size_t RS = (size_t)LB * PE4_S;
+  if (!pair || n.bits() <= 2048 || n.bits() > 4096 || n.bits() + 24 > RS || c->ct_words > 2 * PE4_S) return 0;
+  std::vector<uint32_t> prog;
+  if (!build_lane_program(n, prog)) return 0;
+  const HBig n2 = mul(n, n);
+  auto one_minus = [&](const HBig& r) { return mod(sub(add(n, HBig(1)), r), n); };   // (1 - r) mod n, 0 < r < n
+  const HBig r3 = mul_pow2_mod(HBig(1), 3 * RS, n2);
+  const HBig qt = div_big(r3, n), rm = sub(r3, mul(qt, n));
+  std::vector<uint32_t> ck = rm.limbs(PE4_S, LB), b = qt.limbs(PE4_S, LB);
+  ck.insert(ck.end(), b.begin(), b.end());
+  uint32_t *dn, *dx1, *dxk, *dck, *dprog, *dn2, *dnr;
+  int rc;
+  if ((rc = upload(c, n.limbs(PE4_S, LB), &dn)) ||
+      (rc = upload(c, one_minus(mul_pow2_mod(HBig(1), RS, n)).limbs(PE4_S, LB), &dx1)) ||
+      (rc = upload(c, one_minus(mul_pow2_mod(HBig(1), 2 * RS, n)).limbs(PE4_S, LB), &dxk)) ||
+      (rc = upload(c, ck, &dck)) || (rc = upload(c, prog, &dprog)) || (rc = upload(c, n2.limbs(PE4_FS, LB), &dn2)) ||
+      (rc = upload(c, mul_pow2_mod(n, (size_t)LB * PE4_FS, n2).limbs(PE4_FS, LB), &dnr)))
+    return rc;
+  std::vector<Pe4Const> pc{Pe4Const{dn, dx1, dxk, dck, dprog, (int)prog.size(), mont_prime(n, LB), dn2, dnr, mont_prime(n2, LB)}};
+  if ((rc = upload(c, pc, &c->d_pe4))) return rc;
+  c->pe4_ok = true;
   return 0;
 }
 
@@ -2141,7 +2177,7 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
       return 0;
     case PAI_OPT_PAIR:
       *value = ((c->dec_pair_ok || c->dec4_ok) && c->dec_lane_enabled ? 1 : 0) | (c->crt_pair_ok ? 2 : 0) |
-               (c->pe_ok || c->pe1_ok ? 4 : 0);
+               (c->pe_ok || c->pe1_ok || (c->pe4_ok && !c->has_priv) ? 4 : 0);
       return 0;
   }
   return fail(PAI_ERR_ARG, "pai_ctx_get_option: unknown option");
@@ -2929,6 +2965,51 @@ static int launch_pe(pai_ctx* c, const EncParams& e, hipStream_t st) {
   return 0;
 }
 
+// public-key encryption for n of 2049..4096 bits on pair groups (kernels_pe4.hpp, engine_pe4.hip), in chunks of CRT_CHUNK
+// elements; stage times: k_pe4_pre, k_pe4_pow, k_pe4_fin
+static int launch_pe4(pai_ctx* c, const EncParams& e, hipStream_t st) {
+  const long long N = e.n;
+  const long long chunk = std::min(N, CRT_CHUNK);
+  const int RW = e.obf == PAI_OBF_GIVEN ? e.r_words : e.rng_words;
+  if (RW <= 0 || 32 * RW > 2 * LB * PE4_S)   // r's 2 S digits (its words are staged in the same 2 S slot words)
+    return fail(PAI_ERR_ARG, "4096-bit pair encrypt: obfuscator too wide");
+  Pe4Geom g;
+  pe4_geometry(c->cus, chunk, &g);
+  int rc = ensure_scratch(c, g.scratch_bytes);
+  if (rc) return rc;
+  const size_t xbytes = (size_t)2 * PE4_S * 4;   // per element, + 8 for M
+  if ((rc = ensure_work(c, (xbytes + 8) * chunk))) return rc;
+  const size_t esz = e.dtype == PAI_F32 ? 4 : 8;
+  for (long long off = 0; off < N; off += chunk) {
+    const long long n = std::min(chunk, N - off);
+    hipEvent_t* ev = stage_chunk(c);
+    if (ev) c->nev = 4;
+    Pe4Params p{};
+    p.k = c->d_pe4;
+    p.x = (const char*)e.x + (size_t)off * esz;
+    p.dtype = e.dtype;
+    p.exp_mode = e.exp_mode;
+    p.fexp = e.fexp;
+    p.obf = e.obf;
+    p.r = e.r ? e.r + (size_t)off * e.r_stride : nullptr;
+    p.r_stride = e.r_stride;
+    p.r_words = e.r_words;
+    p.rng_words = e.rng_words;
+    std::memcpy(p.rng_key, e.rng_key, sizeof(p.rng_key));
+    p.index_base = e.index_base + (unsigned long long)off;
+    p.n = n;
+    p.xw = (uint32_t*)c->d_work;
+    p.M = (int64_t*)((char*)c->d_work + xbytes * chunk);
+    p.scratch = (uint32_t*)c->d_scratch;
+    p.ct = e.ct + (size_t)off * c->ct_words;
+    p.ct_words = c->ct_words;
+    p.exp = e.exp + off;
+    p.status = e.status ? e.status + off : nullptr;
+    HIPCHK(pe4_launch(p, g, st, ev));
+  }
+  return 0;
+}
+
 // k_crt_fin over elements [off, off + n) of the call: c = (u_p q^2 + u_q p^2) c0 mod n^2 from u [2][sb][n]
 static int crt_finish(pai_ctx* c, const EncParams& e, const uint32_t* u, int sb, long long off, long long n,
                       hipStream_t st) {
@@ -3116,6 +3197,7 @@ int pai_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mo
   }
   if (obf_mode != PAI_OBF_NONE && c->pe_ok && c->ct_words == 2 * 64) return launch_pe(c, p, st);
   if (obf_mode != PAI_OBF_NONE && c->pe1_ok) return launch_pe1(c, p, st);
+  if (obf_mode != PAI_OBF_NONE && c->pe4_ok && !c->has_priv) return launch_pe4(c, p, st);
   switch (c->tpi_e) {
     case 2: return launch_encrypt<2>(c, p, st);
     case 4: return launch_encrypt<4>(c, p, st);

@@ -399,7 +399,9 @@ class Context:
 
     @property
     def pair_paths(self) -> int:
-        """Bit 0: decryption, bit 1: CRT encryption stage B on p-adic pairs (kernels_pair.hpp)."""
+        """Bit 0: decryption, bit 1: CRT encryption stage B on p-adic pairs (kernels_pair.hpp); bit 2: public-key
+        encryption on pairs (n of at most 1024 bits and of 1537..2048 bits; n of 2049..4096 bits on pair groups,
+        kernels_pe4.hpp, while the context holds no private key)."""
         return int(self._get_option(PAI_OPT_PAIR))
 
     def prepare_fixed_base(self):

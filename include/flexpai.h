@@ -120,9 +120,10 @@ typedef struct pai_comm pai_comm;
                                     kernels_grp_pair.hpp: the default; round 1's k_fb / k_fbg were retired in round 6),
                                     else 0                                                                     */
 #define PAI_OPT_PAIR 9           /* read-only: bit 0 = decryption, bit 1 = CRT encryption (stage B), bit 2 =
-                                    public-key encryption (2048-bit n, and n of at most 1024 bits) run on
-                                    p-adic pairs (kernels_pair.hpp, kernels_dec4.hpp, kernels_pe.hpp,
-                                    kernels_pe1.hpp: the default; $FLEXPAI_PAIR=0 at context creation selects
+                                    public-key encryption (n of at most 1024 bits, of 1537..2048 bits, and, in a
+                                    context without the private key, of 2049..4096 bits) run on p-adic pairs
+                                    (kernels_pair.hpp, kernels_dec4.hpp, kernels_pe.hpp, kernels_pe1.hpp,
+                                    kernels_pe4.hpp: the default; $FLEXPAI_PAIR=0 at context creation selects
                                     the kernels they replace)                                                  */
 #define PAI_OPT_PUBLIC_FB 10     /* 1 (default): PAI_OBF_RNG encryption WITHOUT the private key (2048-bit n) samples
                                   * r^n through the public fixed bases (kernels_pfb.hpp) once the break-even count
@@ -165,7 +166,8 @@ int pai_ctx_set_option(pai_ctx* ctx, int option, int value);
 int pai_ctx_get_option(const pai_ctx* ctx, int option, int* value);
 /* With PAI_OPT_STAGE_TIMING on: kernel durations (ms) of the last encrypt call, summed over all its chunks
  * (a host-buffer call's chunks included; past 64 chunks the recorded ones are folded into running sums,
- * which waits for them), in launch order (CRT: stage A, stage B, finish; public key on pairs: k_pe_pre, k_pe_pow, k_pe_fin; other public-key
+ * which waits for them), in launch order (CRT: stage A, stage B, finish; public key on pairs: k_pe_pre, k_pe_pow, k_pe_fin,
+ * or k_pe4_pre, k_pe4_pow, k_pe4_fin for n of 2049..4096 bits without the private key; other public-key
  * paths: the one encrypt kernel). Waits for them. */
 int pai_ctx_stage_times(pai_ctx* ctx, float* ms_out, int max_out, int* count);
 /* key bits, 32-bit words per ciphertext (2*key_bits/32), words per plaintext (key_bits/32) */

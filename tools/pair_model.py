@@ -106,6 +106,87 @@ def check(pbits, trials=200, seed=1):
     print(f"pbits={pbits} S={S}: {trials} x (mul, sqr, c0-first) ok")
 
 
+# ---- pair groups (bn_pgroup.hpp): TPI lanes x LL limbs, the second row kept non-negative by LMASK - q1
+def pgroup_pass(A, B, a2, b2, p, TPI, LL, sqr=False, start2=0):
+    """The CIOS of bn_pgroup.hpp (step<TPI, LL, SQR, B2Z>) over the digits (a2[j], b2[j]), len(a2) a multiple of LL:
+    lane t owns limbs [LL t, LL t + LL) of A, B and p and LL rotating 64-bit accumulators per row; per digit
+      P1 += A a2j, P2 += B a2j + A b2j (sqr: P2 += A (2 b2j)); q1 from lane 0; P2_low += LMASK - q1 (lane 0); q2;
+      P1 += q1 p, P2 += q2 p; both rows shift one limb across the group.
+    The second row starts at start2 (an integer < 2^(28 S)). Returns (U, Bn, mx): the two rows as integers and an
+    upper bound (exact above bit 32) of the largest value any accumulator held before a shift. The accumulators are
+    kept exactly as (high, low) halves in numpy uint64, so the model runs S = 152 in milliseconds."""
+    import numpy as np
+    S = TPI * LL
+    assert len(a2) == len(b2) and len(a2) % LL == 0
+    M32 = np.uint64(0xFFFFFFFF)
+    sh32 = np.uint64(32)
+    Av = np.array(A, dtype=np.uint64).reshape(TPI, LL)
+    Bv = np.array(B, dtype=np.uint64).reshape(TPI, LL)
+    pv = np.array(limbs(p, S), dtype=np.uint64).reshape(TPI, LL)
+    pinv = (-pow(p, -1, 1 << LB)) % (1 << LB)
+    hi = [np.zeros((TPI, LL), dtype=np.uint64) for _ in range(2)]
+    lo = [np.zeros((TPI, LL), dtype=np.uint64), np.array(limbs(start2, S), dtype=np.uint64).reshape(TPI, LL)]
+    mx = 0
+
+    def acc(row, prod, s):      # P[(i + s) % LL] += prod[i]; every product is < 2^58
+        prod = np.roll(prod, s, axis=1)
+        lo[row] += prod & M32
+        hi[row] += prod >> sh32
+
+    def low28(row, s):
+        return int(lo[row][0, s]) & MASK
+
+    for j, (aj, bj) in enumerate(zip(a2, b2)):
+        s = j % LL
+        acc(0, Av * np.uint64(aj), s)
+        if sqr:
+            acc(1, Av * np.uint64(2 * bj), s)
+        else:
+            acc(1, Bv * np.uint64(aj), s)
+            if bj:
+                acc(1, Av * np.uint64(bj), s)
+        q1 = (low28(0, s) * pinv) & MASK
+        lo[1][0, s] += np.uint64(MASK - q1)
+        q2 = (low28(1, s) * pinv) & MASK
+        acc(0, pv * np.uint64(q1), s)
+        acc(1, pv * np.uint64(q2), s)
+        for row in (0, 1):
+            mx = max(mx, (int((hi[row] + (lo[row] >> sh32)).max()) << 32) | 0xFFFFFFFF)   # value >> 32 is exact
+            v = [(int(hi[row][t, s]) << 32) + int(lo[row][t, s]) for t in range(TPI)]
+            assert v[0] & MASK == 0
+            for t in range(TPI):
+                c = v[t] >> LB
+                lo[row][t, (s + 1) % LL] += np.uint64(c & 0xFFFFFFFF)
+                hi[row][t, (s + 1) % LL] += np.uint64(c >> 32)
+                lo[row][t, s] = np.uint64(v[t + 1] & MASK) if t + 1 < TPI else np.uint64(0)
+                hi[row][t, s] = np.uint64(0)
+    out = []
+    for row in (0, 1):
+        out.append(sum(((int(hi[row][t, i]) << 32) + int(lo[row][t, i])) << (LB * (t * LL + i))
+                       for t in range(TPI) for i in range(LL)))
+    return out[0], out[1], mx
+
+
+def pgroup_mul(A1, B1, A2, B2, p, TPI, LL, sqr=False):
+    """pgrp::montmul<TPI, LL, SQR>: (A1 + p B1)(A2 + p B2) R^-1 mod p^2 as a pair, R = 2^(28 TPI LL); the second row
+    starts at (1 - R) mod p. Integers in, (U, Bn, mx) out."""
+    S = TPI * LL
+    R = 1 << (LB * S)
+    if sqr:
+        A2, B2 = A1, B1
+    return pgroup_pass(limbs(A1, S), limbs(B1, S), limbs(A2, S), limbs(B2, S), p, TPI, LL, sqr, (1 - R) % p)
+
+
+def pe4_pre(r, n, TPI=8, LL=19):
+    """k_pe4_pre (kernels_pe4.hpp): r R mod n^2 as a pair from r's 2 S digits: one B-free pass of the constant pair of
+    R^3 mod n^2 whose second row starts at (1 - R^2) mod n. r < 2^(28 2 S). Returns (A, B, mx)."""
+    S = TPI * LL
+    R = 1 << (LB * S)
+    r3 = pow(R, 3, n * n)
+    cA, cB = r3 % n, r3 // n
+    return pgroup_pass(limbs(cA, S), limbs(cB, S), limbs(r, 2 * S), [0] * (2 * S), n, TPI, LL, False, (1 - R * R) % n)
+
+
 if __name__ == "__main__":
     check(512)
     check(1024)
