@@ -55,6 +55,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_crtw.hpp"
 #include "engine_pe1.hpp"
 #include "engine_pe4.hpp"
+#include "engine_crt4.hpp"
 
 using namespace fpai;
 
@@ -128,6 +129,11 @@ struct pai_ctx {
   bool dec4_ok = false;
   Dec4Half* d_dec4_halves = nullptr;
   int dec4_kchunks = 0;
+  // 2049..4096-bit keys: the key holder's CRT encryption above the rows on split pairs (kernels_crt4.hpp; stage A reads
+  // setup_rows4096's d_crt_a). Calls of at most crt4_min elements stay on k_encrypt<8> (PAI_OPT_CRT4_MIN)
+  bool crt4_ok = false;
+  Crt4Half* d_crt4_b = nullptr;
+  long long crt4_min = 128;
   // public-key encryption on split pairs (kernels_pe.hpp): 2048-bit n, the default ($FLEXPAI_PAIR=0: k_encrypt)
   bool pe_ok = false;
   // public-key encryption of n <= 1024 bits on pairs over the 37 limbs of n (kernels_pe1.hpp)
@@ -1863,9 +1869,48 @@ static int setup_rows4096(pai_ctx* c, const HBig& p, const HBig& q) {
   return 0;
 }
 
+// The split-pair CRT encryption of a 2049..4096-bit key holder above the rows (kernels_crt4.hpp). Stage A runs on
+// setup_rows4096's stage-A halves (p_h, R^(K+1) mod p_h, the op list over q_h mod (p_h - 1)); stage B's halves are
+// set up here: p_h, (1 - R) mod p_h, the plain pair of the CRT coefficient, the op list over p_h. Same gates as the
+// split-pair decryption (R >= 2^24 p_h). The test build keeps its contexts -- the cross-checks' references -- on
+// k_encrypt<8>. Soft: an unusable key leaves crt4_ok = false.
+static int setup_crt4(pai_ctx* c, const HBig& p, const HBig& q) {
+  c->crt4_ok = false;
+#if FLEXPAI_XCHECK
+  return 0;
+#endif
+  const size_t RS = (size_t)LB * D4_S;
+  if (!c->fbg_ok || c->rows_sa != D4_S || !c->d_crt_a || c->tpi_e != 8 || std::max(p.bits(), q.bits()) + 24 > RS) return 0;
+  SetupTrace tr("    crt4 consts");
+  const HBig primes[2] = {p, q};
+  const HBig sq[2] = {mul(p, p), mul(q, q)};
+  Crt4Half hb[2];
+  int rc;
+  for (int h = 0; h < 2; ++h) {
+    const HBig& ph = primes[h];
+    std::vector<uint32_t> pb;
+    if (!build_lane_program(ph, pb)) return 0;
+    const HBig coef = inv_mod(sq[1 - h], sq[h]);
+    if (coef.is_zero()) return 0;
+    const HBig cb = div_big(coef, ph), ca = sub(coef, mul(cb, ph));
+    std::vector<uint32_t> cpair = ca.limbs(D4_S, LB), b = cb.limbs(D4_S, LB);
+    cpair.insert(cpair.end(), b.begin(), b.end());
+    const HBig x1 = mod(sub(add(ph, HBig(1)), mul_pow2_mod(HBig(1), RS, ph)), ph);   // (1 - R) mod p_h
+    uint32_t *dp, *dx1, *dcf, *dprog;
+    if ((rc = upload(c, ph.limbs(D4_S, LB), &dp)) || (rc = upload(c, x1.limbs(D4_S, LB), &dx1)) ||
+        (rc = upload(c, cpair, &dcf)) || (rc = upload(c, pb, &dprog)))
+      return rc;
+    hb[h] = Crt4Half{dp, dx1, dcf, dprog, (int)pb.size(), mont_prime(ph, LB)};
+  }
+  std::vector<Crt4Half> hv(hb, hb + 2);
+  if ((rc = upload(c, hv, &c->d_crt4_b))) return rc;
+  c->crt4_ok = true;
+  return 0;
+}
+
 // CRT encryption constants (kernels_crt.hpp). p < q here (sorted like keypair.py:57-62).
 static int setup_crt(pai_ctx* c, const HBig& p, const HBig& q) {
-  c->crt_ok = c->fbg_ok = c->dec_pair_ok = c->crt_pair_ok = c->dec4_ok = false;
+  c->crt_ok = c->fbg_ok = c->dec_pair_ok = c->crt_pair_ok = c->dec4_ok = c->crt4_ok = false;
   const size_t pb = std::max(p.bits(), q.bits());
   int sa = 0, sb = 0;
   for (auto cand : {std::pair<int, int>{19, 37}, std::pair<int, int>{37, 74}}) {
@@ -1877,7 +1922,8 @@ static int setup_crt(pai_ctx* c, const HBig& p, const HBig& q) {
   }
   if (!sa) {   // too large for the lane engine: fixed-base on the group engine, protocol-sized calls on rows
     int rc0 = setup_fbg(c, p, q);
-    return rc0 ? rc0 : setup_rows4096(c, p, q);
+    if (!rc0) rc0 = setup_rows4096(c, p, q);
+    return rc0 ? rc0 : setup_crt4(c, p, q);
   }
   const size_t RA = (size_t)LB * sa, RB = (size_t)LB * sb, RE = (size_t)LB * c->S_e;
   const HBig primes[2] = {p, q};
@@ -2041,7 +2087,7 @@ int pai_ctx_set_private(pai_ctx* c, const uint8_t* p_le, const uint8_t* q_le, si
     for (void* a : c->priv_allocs) (void)hipFree(a);
     c->priv_allocs.clear();
     (void)hipGetLastError();
-    c->has_priv = c->crt_ok = c->fbg_ok = c->dec_lane_ok = c->dec_pair_ok = c->crt_pair_ok = c->dec4_ok = false;
+    c->has_priv = c->crt_ok = c->fbg_ok = c->dec_lane_ok = c->dec_pair_ok = c->crt_pair_ok = c->dec4_ok = c->crt4_ok = false;
     c->d_decw = nullptr;
     c->decw_kchunks = 0;
     c->rows_sa = 0;
@@ -2122,6 +2168,10 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       if (value < 0) return fail(PAI_ERR_ARG, "PAI_OPT_ROWS_MAX must be >= 0");
       c->crtw_max = value;
       return 0;
+    case PAI_OPT_CRT4_MIN:
+      if (value < 0) return fail(PAI_ERR_ARG, "PAI_OPT_CRT4_MIN must be >= 0");
+      c->crt4_min = value;
+      return 0;
     case PAI_OPT_STAGE_TIMING: c->timing = value != 0; stage_reset(c); return 0;
     case PAI_OPT_LANE_DECRYPT: c->dec_lane_enabled = value != 0; return 0;
     case PAI_OPT_FIXED_BASE: c->fb_enabled = value != 0; return 0;
@@ -2153,6 +2203,7 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_CRT_ENCRYPT: *value = c->crt_enabled ? 1 : 0; return 0;
     case PAI_OPT_CRT_AVAILABLE: *value = c->crt_ok ? 1 : 0; return 0;
     case PAI_OPT_ROWS_MAX: *value = (int)std::min<long long>(c->crtw_max, INT32_MAX); return 0;
+    case PAI_OPT_CRT4_MIN: *value = (int)std::min<long long>(c->crt4_min, INT32_MAX); return 0;
     case PAI_OPT_STAGE_TIMING: *value = c->timing ? 1 : 0; return 0;
     case PAI_OPT_LANE_DECRYPT: *value = (c->dec_lane_ok && c->dec_lane_enabled) ? 1 : 0; return 0;
     // 1 when device-RNG encryption will use the fixed bases (tables resident, or not yet tried)
@@ -2177,7 +2228,7 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
       return 0;
     case PAI_OPT_PAIR:
       *value = ((c->dec_pair_ok || c->dec4_ok) && c->dec_lane_enabled ? 1 : 0) | (c->crt_pair_ok ? 2 : 0) |
-               (c->pe_ok || c->pe1_ok || (c->pe4_ok && !c->has_priv) ? 4 : 0);
+               (c->pe_ok || c->pe1_ok || (c->pe4_ok && !c->has_priv) ? 4 : 0) | (c->crt4_ok ? 8 : 0);
       return 0;
   }
   return fail(PAI_ERR_ARG, "pai_ctx_get_option: unknown option");
@@ -3133,6 +3184,55 @@ static int launch_crt(pai_ctx* c, const EncParams& e, hipStream_t st) {
   return 0;
 }
 
+// A 2049..4096-bit key holder's call above the rows: k_crt4_pre + k_crt4_a (stage A, one element-half per lane),
+// k_crt4_b (stage B on split pairs), k_crt_fin<8>, in chunks of CRT4_CHUNK elements (y and u: 1776 B per element,
+// 466 MB per chunk; CRT_CHUNK's 4 M would make it 7.4 GB). Stage times: stage A, stage B, finish, summed over chunks.
+constexpr long long CRT4_CHUNK = 1ll << 18;
+static int launch_crt4(pai_ctx* c, const EncParams& e, hipStream_t st) {
+  constexpr int S = D4_S;
+  const long long N = e.n;
+  const int r_words = e.obf == PAI_OBF_GIVEN ? e.r_words : e.rng_words;
+  const int kchunks = (32 * r_words + LB * S - 1) / (LB * S);
+  if (kchunks > KMAX_CHUNKS || (e.obf == PAI_OBF_RNG && r_words > RBUF_WORDS))
+    return fail(PAI_ERR_ARG, "CRT encrypt: obfuscator too wide");
+  const long long chunk = std::min(N, CRT4_CHUNK);
+  Crt4Geom g;
+  crt4_geometry(c->cus, chunk, &g);
+  int rc = ensure_scratch(c, g.scratch_bytes);
+  if (rc) return rc;
+  const size_t ybytes = (size_t)2 * S * 4;   // per element
+  if ((rc = ensure_work(c, (ybytes + (size_t)2 * 2 * S * 4) * chunk))) return rc;
+  uint32_t* y = (uint32_t*)c->d_work;
+  uint32_t* u = (uint32_t*)((char*)c->d_work + ybytes * chunk);
+  for (long long off = 0; off < N; off += chunk) {
+    const long long n = std::min(chunk, N - off);
+    Crt4Params p{};
+    p.ha = c->d_crt_a;
+    p.hb = c->d_crt4_b;
+    p.n = n;
+    p.obf = e.obf;
+    p.r = e.r ? e.r + (size_t)off * e.r_stride : nullptr;
+    p.r_stride = e.r_stride;
+    p.r_words = r_words;
+    std::memcpy(p.rng_key, e.rng_key, sizeof(p.rng_key));
+    p.index_base = e.index_base + (unsigned long long)off;
+    p.kchunks = kchunks;
+    p.y = y;
+    p.u = u;
+    p.scratch = (uint32_t*)c->d_scratch;
+    stage_mark(c, 0, st);
+    HIPCHK(crt4_launch_a(p, g, st));
+    HIPCHK(hipGetLastError());
+    stage_mark(c, 1, st);
+    HIPCHK(crt4_launch_b(p, g, st));
+    HIPCHK(hipGetLastError());
+    stage_mark(c, 2, st);
+    if ((rc = crt_finish(c, e, u, 2 * S, off, n, st))) return rc;
+    stage_mark(c, 3, st);
+  }
+  return 0;
+}
+
 int pai_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mode, int32_t fixed_exp, int obf_mode,
                     const uint32_t* d_r_words, size_t r_stride_words, size_t r_words, const uint8_t* rng_key32,
                     uint64_t index_base, uint32_t* d_ct, int32_t* d_exp, int32_t* d_status, void* stream) {
@@ -3185,6 +3285,7 @@ int pai_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mo
     if (c->crt_sa == 19) return launch_crt<19, 37>(c, p, st);
     if (c->crt_sa == 37) return launch_crt<37, 74>(c, p, st);
   }
+  if (obf_mode != PAI_OBF_NONE && c->crt4_ok && c->crt_enabled && p.n > c->crt4_min) return launch_crt4(c, p, st);
   if (obf_mode == PAI_OBF_RNG && c->pfb_enabled && pfb_supported(c) && pfb_wanted(c, p.n) && ensure_pfb(c)) {
     const int rc = launch_pfb(c, p, st);
     return rc ? rc : guard_collect(c, st);

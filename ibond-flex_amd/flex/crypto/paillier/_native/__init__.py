@@ -29,6 +29,7 @@ EL_OK, EL_INT, EL_INT_BIG, EL_OVERFLOW, EL_FLOAT_OVF, EL_ENC_RANGE = 0, 1, 2, 3,
 PAI_OPT_CRT_ENCRYPT, PAI_OPT_CRT_AVAILABLE, PAI_OPT_STAGE_TIMING, PAI_OPT_LANE_DECRYPT = 1, 2, 3, 4
 PAI_OPT_FIXED_BASE, PAI_OPT_FB_WINDOW, PAI_OPT_FB_READY, PAI_OPT_FB_PAIR, PAI_OPT_PAIR = 5, 6, 7, 8, 9
 PAI_OPT_SPLIT_SAMPLER, PAI_OPT_ROWS_MAX = 13, 14
+PAI_OPT_CRT4_MIN = 15
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
 PFB_NBASES = 33
 
@@ -342,6 +343,16 @@ class Context:
         """0 keeps every CRT encryption / decryption on the lane kernels (k_crt_a + k_crt_b_pair, k_dec_*_pair); same bits."""
         self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_ROWS_MAX, int(n)))
 
+    @property
+    def crt4_min(self) -> int:
+        """A 2049..4096-bit key holder's calls of at most this many elements (default 128) that the rows do not take stay
+        on k_encrypt<8> instead of the split-pair CRT (kernels_crt4.hpp)."""
+        return int(self._get_option(PAI_OPT_CRT4_MIN))
+
+    def set_crt4_min(self, n: int):
+        """0 sends every call above the rows through the split-pair CRT; same bits."""
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_CRT4_MIN, int(n)))
+
     def set_crt(self, enabled: bool):
         """Encrypt through the private-key CRT kernels (default when available) or the public-key one.
         The ciphertext bits are identical either way."""
@@ -401,7 +412,8 @@ class Context:
     def pair_paths(self) -> int:
         """Bit 0: decryption, bit 1: CRT encryption stage B on p-adic pairs (kernels_pair.hpp); bit 2: public-key
         encryption on pairs (n of at most 1024 bits and of 1537..2048 bits; n of 2049..4096 bits on pair groups,
-        kernels_pe4.hpp, while the context holds no private key)."""
+        kernels_pe4.hpp, while the context holds no private key); bit 3: a 2049..4096-bit key holder's encryption above the
+        rows runs the split-pair CRT (kernels_crt4.hpp)."""
         return int(self._get_option(PAI_OPT_PAIR))
 
     def prepare_fixed_base(self):

@@ -124,7 +124,11 @@ typedef struct pai_comm pai_comm;
                                     context without the private key, of 2049..4096 bits) run on p-adic pairs
                                     (kernels_pair.hpp, kernels_dec4.hpp, kernels_pe.hpp, kernels_pe1.hpp,
                                     kernels_pe4.hpp: the default; $FLEXPAI_PAIR=0 at context creation selects
-                                    the kernels they replace)                                                  */
+                                    the kernels they replace); bit 3 = this context holds a private key of
+                                    2049..4096 bits and its encryption above the rows (more than PAI_OPT_ROWS_MAX and
+                                    more than PAI_OPT_CRT4_MIN elements, explicit r or device RNG without resident
+                                    fixed-base tables) runs the split-pair CRT (kernels_crt4.hpp). A key holder's
+                                    bit 2 stays 0                                                              */
 #define PAI_OPT_PUBLIC_FB 10     /* 1 (default): PAI_OBF_RNG encryption WITHOUT the private key (2048-bit n) samples
                                   * r^n through the public fixed bases (kernels_pfb.hpp) once the break-even count
                                   * is reached (pai_ctx_public_fb_policy); get: 1 when the path is enabled and not
@@ -147,6 +151,10 @@ typedef struct pai_comm pai_comm;
                                   * k_crt_w and decryption k_dec_w, a public-key-only party's encryption k_pe_w; the
                                   * latency of protocol-sized calls) instead of one lane / lane pair each; 0
                                   * disables. Same bits either way                                               */
+#define PAI_OPT_CRT4_MIN 15      /* a 2049..4096-bit key holder's calls of at most this many elements (default 128, one
+                                  * block of lane pairs) that the rows do not take stay on the public-key kernel
+                                  * instead of the split-pair CRT (kernels_crt4.hpp); 0: every such call runs the CRT.
+                                  * Whether a lower floor would be faster has not been measured. Same bits either way */
 
 /* Number of visible GPUs (0 when there is none or the runtime cannot start). */
 int pai_device_count(int* count);
@@ -161,12 +169,14 @@ void pai_ctx_destroy(pai_ctx* ctx);
  * call (no context may be building tables concurrently). $FLEXPAI_TABLE_POOL=0: plain hipMalloc / hipFree. */
 void pai_release_table_cache(void);
 /* Encryption with the private key set uses CRT over p^2, q^2 (same ciphertext bits, ~4x fewer
- * multiply-accumulates); PAI_OPT_CRT_ENCRYPT = 0 forces the public-key kernel. */
+ * multiply-accumulates; for keys of 2049..4096 bits on split pairs above PAI_OPT_ROWS_MAX and PAI_OPT_CRT4_MIN
+ * elements, ~6x fewer); PAI_OPT_CRT_ENCRYPT = 0 forces the public-key kernel. */
 int pai_ctx_set_option(pai_ctx* ctx, int option, int value);
 int pai_ctx_get_option(const pai_ctx* ctx, int option, int* value);
 /* With PAI_OPT_STAGE_TIMING on: kernel durations (ms) of the last encrypt call, summed over all its chunks
  * (a host-buffer call's chunks included; past 64 chunks the recorded ones are folded into running sums,
- * which waits for them), in launch order (CRT: stage A, stage B, finish; public key on pairs: k_pe_pre, k_pe_pow, k_pe_fin,
+ * which waits for them), in launch order (CRT: stage A, stage B, finish -- for keys of 2049..4096 bits above the rows k_crt4_pre + k_crt4_a,
+ * k_crt4_b, k_crt_fin; public key on pairs: k_pe_pre, k_pe_pow, k_pe_fin,
  * or k_pe4_pre, k_pe4_pow, k_pe4_fin for n of 2049..4096 bits without the private key; other public-key
  * paths: the one encrypt kernel). Waits for them. */
 int pai_ctx_stage_times(pai_ctx* ctx, float* ms_out, int max_out, int* count);
