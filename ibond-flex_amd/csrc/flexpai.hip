@@ -52,6 +52,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_sgs.hpp"
 #include "engine_grp.hpp"
 #include "engine_mul.hpp"
+#include "engine_mm.hpp"
 #include "engine_crtw.hpp"
 #include "engine_pe1.hpp"
 #include "engine_pe4.hpp"
@@ -223,6 +224,16 @@ struct pai_ctx {
   size_t seg_bytes = 0;
   void* d_plain = nullptr;      // ciphertext + plaintext: the two k_add operands and their exponents
   size_t plain_bytes = 0;
+  // fused matrix product (kernels_mm.hpp): PAI_OPT_MATMUL_FUSED / PAI_OPT_MATMUL_PATH
+  bool mm_fused = true;
+  int mm_path = 0;              // last pai_matmul[_dev] call: 0 none yet, 1 term path, 2 fused
+  void* d_mmtab = nullptr;      // window tables of one block of ciphertexts (at most the table budget)
+  size_t mmtab_bytes = 0;
+  void* d_mmwork = nullptr;     // neg_row [K], the inversion's flags [m K]
+  size_t mmwork_bytes = 0;
+  void* d_mminv = nullptr;      // copy of the ciphertexts with the flagged rows' inverted (only with negative scalars)
+  size_t mminv_bytes = 0;
+  std::vector<uint8_t> mm_neg, mm_flags;   // host sides of neg_row and of the flags
   void* d_inv = nullptr;        // batch-inversion prefix products and segment products
   size_t inv_bytes = 0;
   std::vector<uint32_t> inv_host;   // top of the inversion tree (host side of an async copy)
@@ -312,6 +323,9 @@ pai_ctx::~pai_ctx() {
   if (d_scratch) (void)hipFree(d_scratch);
   if (d_work) (void)hipFree(d_work);
   if (d_mul) (void)hipFree(d_mul);
+  if (d_mmtab) (void)hipFree(d_mmtab);
+  if (d_mmwork) (void)hipFree(d_mmwork);
+  if (d_mminv) (void)hipFree(d_mminv);
   if (d_inv) (void)hipFree(d_inv);
   if (inv_async) {
     if (inv_async->pin) (void)hipHostFree(inv_async->pin);
@@ -2172,6 +2186,7 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       if (value < 0) return fail(PAI_ERR_ARG, "PAI_OPT_CRT4_MIN must be >= 0");
       c->crt4_min = value;
       return 0;
+    case PAI_OPT_MATMUL_FUSED: c->mm_fused = value != 0; return 0;
     case PAI_OPT_STAGE_TIMING: c->timing = value != 0; stage_reset(c); return 0;
     case PAI_OPT_LANE_DECRYPT: c->dec_lane_enabled = value != 0; return 0;
     case PAI_OPT_FIXED_BASE: c->fb_enabled = value != 0; return 0;
@@ -2204,6 +2219,8 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_CRT_AVAILABLE: *value = c->crt_ok ? 1 : 0; return 0;
     case PAI_OPT_ROWS_MAX: *value = (int)std::min<long long>(c->crtw_max, INT32_MAX); return 0;
     case PAI_OPT_CRT4_MIN: *value = (int)std::min<long long>(c->crt4_min, INT32_MAX); return 0;
+    case PAI_OPT_MATMUL_FUSED: *value = c->mm_fused ? 1 : 0; return 0;
+    case PAI_OPT_MATMUL_PATH: *value = c->mm_path; return 0;
     case PAI_OPT_STAGE_TIMING: *value = c->timing ? 1 : 0; return 0;
     case PAI_OPT_LANE_DECRYPT: *value = (c->dec_lane_ok && c->dec_lane_enabled) ? 1 : 0; return 0;
     // 1 when device-RNG encryption will use the fixed bases (tables resident, or not yet tried)
@@ -3915,6 +3932,138 @@ int pai_segment_add_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, 
 
 constexpr int MATMUL_CHUNK = 16;   // operands per k_add pass of the reduction tree
 
+// Bytes of window tables (kernels_mm.hpp k_mm_tab: 16 rows of S limbs per ciphertext, and as many again for the
+// inverses once a scalar is negative) that one block of the fused matrix product may hold: 9.25 KiB per ciphertext and
+// sign at 2048 bits, so 256 MiB takes 14 k ciphertexts with mixed signs (he_otp_lr's m = 1, K = batch fits many times
+// over) and bounds what a context keeps resident. A larger product is processed in blocks of rows i, and a single row
+// that is still too long in ranges of k (multiples of MM_KC, at least one chunk); every block writes its own slice of
+// the partials, so the reduction tree and the bits do not depend on the blocking.
+constexpr size_t MM_TABLE_BYTES = (size_t)256 << 20;
+
+static size_t mm_table_budget() {
+  if (const char* e = xcheck_env("FLEXPAI_MM_TABLE_BYTES")) {     // test build: blocking at small shapes
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    if (v > 0) return (size_t)v;
+  }
+  return MM_TABLE_BYTES;
+}
+
+// Which calls take the fused path (PAI_OPT_MATMUL_FUSED = 1, the default). An instance of k_mm_acc is a chain of about
+// 4 nw + 16 nw dependent products where a term of k_mul is one of about 6 nw, so the fused path is faster once the chip
+// is full of instances and slower while it is not; and its tables cost 15 products per ciphertext (36 with the inverse)
+// that only d columns share. Measured against the parent's term path on an MI355X (tools/mm_ab.py, profiles/mm_ab.json
+// and mm_ab_sweep.json; T = K m d terms, G = resident lane groups = 2 blocks x CUs x 256 / TPI): faster by more than
+// the spread at d >= 16 with T >= 2 G (1.3x .. 3.5x at 1024, 2048 and 4096 bits), slower at T <= G (0.65x .. 0.93x) and
+// at d = 1 whatever T (0.24x .. 0.67x). Calls outside that class keep the term path. The test build sends every call
+// through the fused kernels under $FLEXPAI_MM_ALWAYS=1, so that they can be checked at small shapes.
+constexpr size_t MM_MIN_D = 16;
+constexpr size_t MM_MIN_FILL = 2;
+
+static bool mm_take_fused(const pai_ctx* c, size_t m, size_t K, size_t d) {
+  if (!c->mm_fused) return false;
+  if (const char* e = xcheck_env("FLEXPAI_MM_ALWAYS"))
+    if (atoi(e) != 0) return true;
+  const double groups = 2.0 * c->cus * (BLOCK / c->tpi_e);
+  return d >= MM_MIN_D && (double)m * (double)K * (double)d >= (double)MM_MIN_FILL * groups;
+}
+
+// The fused path of pai_matmul_dev: the ceil(K / MM_KC) chunk partials of every output, [chunk][m d][W] words in
+// `part` and [chunk][m d] exponents in `pexp` (the operands of the k_add tree). k_mm_sign's row flags come back to the
+// host (one synchronisation of `st`, K bytes: the decision below needs them); only with a negative scalar does the
+// call then copy the ciphertexts and invert the flagged rows' (batch_invert: its one synchronisation, and
+// PAI_ERR_NOINV exactly where the term path raises it -- a ciphertext without inverse in a row with a negative scalar).
+static int matmul_fused(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t m, size_t K, int dtype,
+                        const void* d_x, size_t d, uint32_t* part, int32_t* pexp, hipStream_t st) {
+  const size_t W = c->ct_words, Np = m * d, nch = (K + MM_KC - 1) / MM_KC;
+  const size_t eb = mm_entry_bytes(c->tpi_e);
+  if (nch * Np >= (size_t)INT32_MAX) return fail(PAI_ERR_ARG, "pai_matmul_dev: too many partial products");
+  const size_t o_flag = align16(K);
+  int rc = ensure_buf(&c->d_mmwork, &c->mmwork_bytes, o_flag + align16(m * K));
+  if (rc) return rc;
+  uint8_t* neg_row = (uint8_t*)c->d_mmwork;
+  uint8_t* flags = neg_row + o_flag;
+  HIPCHK(hipMemsetAsync(neg_row, 0, K, st));
+  MmSignParams sp{};
+  sp.x = d_x;
+  sp.dtype = dtype;
+  sp.K = (long long)K;
+  sp.d = (long long)d;
+  sp.neg_row = neg_row;
+  HIPCHK(mm_sign_launch(sp, c->cus, st));
+  c->mm_neg.assign(K, 0);
+  HIPCHK(hipMemcpyAsync(c->mm_neg.data(), neg_row, K, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const bool any_neg = std::any_of(c->mm_neg.begin(), c->mm_neg.end(), [](uint8_t v) { return v != 0; });
+  uint32_t* inv = nullptr;
+  if (any_neg) {
+    if ((rc = ensure_buf(&c->d_mminv, &c->mminv_bytes, m * K * W * 4))) return rc;
+    inv = (uint32_t*)c->d_mminv;
+    c->mm_flags.resize(m * K);
+    for (size_t i = 0; i < m; ++i) std::memcpy(c->mm_flags.data() + i * K, c->mm_neg.data(), K);
+    HIPCHK(hipMemcpyAsync(flags, c->mm_flags.data(), m * K, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(inv, d_ct, m * K * W * 4, hipMemcpyDeviceToDevice, st));
+    if ((rc = batch_invert(c, inv, flags, (long long)(m * K), st))) return rc;
+  }
+  // blocks: rows first, then ranges of k
+  const size_t cap = std::max<size_t>(mm_table_budget() / (eb * (any_neg ? 2 : 1)), 1);   // ciphertexts per block
+  size_t mb = m, kb = K;
+  if (m * K > cap) {
+    if (K <= cap) {
+      mb = cap / K;
+    } else {
+      mb = 1;
+      kb = std::max<size_t>(cap / MM_KC, 1) * MM_KC;
+    }
+  }
+  if (mb * kb >= (size_t)INT32_MAX / 2) return fail(PAI_ERR_ARG, "pai_matmul_dev: table block too large");
+  if ((rc = ensure_buf(&c->d_mmtab, &c->mmtab_bytes, mb * kb * (any_neg ? 2 : 1) * eb))) return rc;
+  for (size_t i0 = 0; i0 < m; i0 += mb) {
+    for (size_t k0 = 0; k0 < K; k0 += kb) {
+      const size_t mbb = std::min(mb, m - i0), kbb = std::min(kb, K - k0);
+      const bool has_neg = any_neg && std::any_of(c->mm_neg.begin() + k0, c->mm_neg.begin() + k0 + kbb,
+                                                  [](uint8_t v) { return v != 0; });
+      MmTabParams tp{};
+      tp.ct = d_ct;
+      tp.inv = inv;
+      tp.neg_row = neg_row;
+      tp.K = (long long)K;
+      tp.i0 = (long long)i0;
+      tp.k0 = (long long)k0;
+      tp.mb = (long long)mbb;
+      tp.kb = (long long)kbb;
+      tp.has_neg = has_neg ? 1 : 0;
+      tp.tab = (uint32_t*)c->d_mmtab;
+      tp.N = c->d_N;
+      tp.R2 = c->d_R2;
+      tp.oneR = c->d_oneR;
+      tp.mprime = c->mprime_N;
+      tp.ct_words = c->ct_words;
+      HIPCHK(mm_tab_launch(c->tpi_e, tp, c->cus, st));
+      MmAccParams ap{};
+      ap.exp = d_exp;
+      ap.x = d_x;
+      ap.dtype = dtype;
+      ap.K = (long long)K;
+      ap.d = (long long)d;
+      ap.i0 = (long long)i0;
+      ap.k0 = (long long)k0;
+      ap.mb = (long long)mbb;
+      ap.kb = (long long)kbb;
+      ap.has_neg = tp.has_neg;
+      ap.tab = tp.tab;
+      ap.part = part;
+      ap.pexp = pexp;
+      ap.Np = (long long)Np;
+      ap.N = c->d_N;
+      ap.oneR = c->d_oneR;
+      ap.mprime = c->mprime_N;
+      ap.ct_words = c->ct_words;
+      HIPCHK(mm_acc_launch(c->tpi_e, ap, c->cus, st));
+    }
+  }
+  return 0;
+}
+
 int pai_matmul_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t m, size_t K, int dtype,
                    const void* d_x, size_t d, uint32_t* d_out, int32_t* d_exp_out, void* stream) {
   if (!c) return fail(PAI_ERR_ARG, "null ctx");
@@ -3926,10 +4075,14 @@ int pai_matmul_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_
   hipStream_t st = (hipStream_t)stream;
   const size_t W = c->ct_words, Np = m * d, T = K * Np;
   const int C = MATMUL_CHUNK;
-  const size_t Kp = K > (size_t)C ? (K + C - 1) / C * C : K;          // rows of the term buffer
+  // fused (kernels_mm.hpp): the term buffer holds the ceil(K / MM_KC) chunk partials instead of the K terms
+  const bool fused = mm_take_fused(c, m, K, d);
+  c->mm_path = fused ? 2 : 1;
+  const size_t rows = fused ? (K + MM_KC - 1) / MM_KC : K;
+  const size_t Kp = rows > (size_t)C ? (rows + C - 1) / C * C : rows;   // rows of the term buffer
   const size_t Pr = (Kp + C - 1) / C + C;                              // rows of the partial buffer
   const size_t o_terms = 0, o_texp = align16(o_terms + Kp * Np * W * 4), o_flag = align16(o_texp + Kp * Np * 4),
-               o_part = align16(o_flag + T), o_pexp = align16(o_part + Pr * Np * W * 4), total = align16(o_pexp + Pr * Np * 4);
+               o_part = align16(o_flag + (fused ? 0 : T)), o_pexp = align16(o_part + Pr * Np * W * 4), total = align16(o_pexp + Pr * Np * 4);
   int rc = ensure_buf(&c->d_mul, &c->mul_bytes, total);
   if (rc) return rc;
   char* b = (char*)c->d_mul;
@@ -3938,28 +4091,32 @@ int pai_matmul_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_
   uint8_t* flag = (uint8_t*)(b + o_flag);
   uint32_t* part = (uint32_t*)(b + o_part);
   int32_t* pexp = (int32_t*)(b + o_pexp);
-  // terms (k, i, j) = c[i][k] (x) x[k][j], k-major: the k_add layout of K operands over m d outputs
-  MulParams p{};
-  p.ct = d_ct;
-  p.exp = d_exp;
-  p.m = (long long)m;
-  p.d = (long long)d;
-  p.cs_i = (long long)K;
-  p.cs_k = 1;
-  p.xs_k = (long long)d;
-  p.xs_j = 1;
-  p.x = d_x;
-  p.dtype = dtype;
-  p.n = (long long)T;
-  p.out = terms;
-  p.out_exp = texp;
-  p.neg = flag;
-  if ((rc = launch_mul(c, p, st))) return rc;
-  if ((rc = batch_invert(c, terms, flag, (long long)T, st))) return rc;
+  if (fused) {
+    if ((rc = matmul_fused(c, d_ct, d_exp, m, K, dtype, d_x, d, terms, texp, st))) return rc;
+  } else {
+    // terms (k, i, j) = c[i][k] (x) x[k][j], k-major: the k_add layout of K operands over m d outputs
+    MulParams p{};
+    p.ct = d_ct;
+    p.exp = d_exp;
+    p.m = (long long)m;
+    p.d = (long long)d;
+    p.cs_i = (long long)K;
+    p.cs_k = 1;
+    p.xs_k = (long long)d;
+    p.xs_j = 1;
+    p.x = d_x;
+    p.dtype = dtype;
+    p.n = (long long)T;
+    p.out = terms;
+    p.out_exp = texp;
+    p.neg = flag;
+    if ((rc = launch_mul(c, p, st))) return rc;
+    if ((rc = batch_invert(c, terms, flag, (long long)T, st))) return rc;
+  }
   // reduction over k: passes of C operands (padding operands: exponent PAD_EXP), then the rest
   uint32_t* cur = terms;
   int32_t* cur_e = texp;
-  size_t Kc = K;
+  size_t Kc = rows;
   bool in_terms = true;
   while (Kc > (size_t)C) {
     const size_t Kn = (Kc + C - 1) / C;

@@ -30,6 +30,7 @@ PAI_OPT_CRT_ENCRYPT, PAI_OPT_CRT_AVAILABLE, PAI_OPT_STAGE_TIMING, PAI_OPT_LANE_D
 PAI_OPT_FIXED_BASE, PAI_OPT_FB_WINDOW, PAI_OPT_FB_READY, PAI_OPT_FB_PAIR, PAI_OPT_PAIR = 5, 6, 7, 8, 9
 PAI_OPT_SPLIT_SAMPLER, PAI_OPT_ROWS_MAX = 13, 14
 PAI_OPT_CRT4_MIN = 15
+PAI_OPT_MATMUL_FUSED, PAI_OPT_MATMUL_PATH = 16, 17
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
 PFB_NBASES = 33
 
@@ -352,6 +353,21 @@ class Context:
     def set_crt4_min(self, n: int):
         """0 sends every call above the rows through the split-pair CRT; same bits."""
         self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_CRT4_MIN, int(n)))
+
+    @property
+    def matmul_fused(self) -> bool:
+        """True when matmul runs the fused windowed multi-exponentiation (kernels_mm.hpp: the default, for products of
+        d >= 16 columns that fill the chip), False for one k_mul exponentiation per term on every call."""
+        return bool(self._get_option(PAI_OPT_MATMUL_FUSED))
+
+    def set_matmul_fused(self, enabled: bool):
+        """False keeps matmul on k_mul + batch inversion + k_add over all K m d terms; same bits."""
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_MATMUL_FUSED, 1 if enabled else 0))
+
+    @property
+    def matmul_path(self) -> int:
+        """The path of this context's last matmul call: 0 = none yet, 1 = term path, 2 = fused."""
+        return int(self._get_option(PAI_OPT_MATMUL_PATH))
 
     def set_crt(self, enabled: bool):
         """Encrypt through the private-key CRT kernels (default when available) or the public-key one.

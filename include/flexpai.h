@@ -155,6 +155,15 @@ typedef struct pai_comm pai_comm;
                                   * block of lane pairs) that the rows do not take stay on the public-key kernel
                                   * instead of the split-pair CRT (kernels_crt4.hpp); 0: every such call runs the CRT.
                                   * Whether a lower floor would be faster has not been measured. Same bits either way */
+#define PAI_OPT_MATMUL_FUSED 16  /* 1 (default): pai_matmul[_dev] runs the fused windowed multi-exponentiation
+                                  * (kernels_mm.hpp: k_mm_sign, k_mm_tab, k_mm_acc, then the k_add tree over the
+                                  * ceil(K / 16) chunk partials) for the calls it was measured faster on: d >= 16 and
+                                  * K m d of at least twice the chip's resident lane groups (131 072 terms at 1024 bits,
+                                  * 65 536 at 2048, 32 768 at 4096 on an MI355X); 0: every call runs one k_mul
+                                  * exponentiation per term (k, i, j), one batch inversion over the terms and the k_add
+                                  * tree over all of them. Read back: 1 when the fused path is in use. Same bits either way */
+#define PAI_OPT_MATMUL_PATH 17   /* read-only: the path of this context's last pai_matmul[_dev] call: 0 = none yet,
+                                  * 1 = term path, 2 = fused                                                     */
 
 /* Number of visible GPUs (0 when there is none or the runtime cannot start). */
 int pai_device_count(int* count);
@@ -268,12 +277,18 @@ int pai_segment_add(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t
                     const int64_t* seg_off, size_t nseg, uint32_t* ct_out, int32_t* exp_out);
 /* Encrypted (m x K, row-major ciphertexts + exponents) times plain (K x d, row-major, dtype as above):
  * out[i][j] = sum_k ct[i][k] (x) x[k][j] with the reference's exponent alignment (bit-identical to
- * numpy's object dot over PaillierEncryptedNumber, whose sums are order independent). */
+ * numpy's object dot over PaillierEncryptedNumber, whose sums are order independent). By default a product of
+ * d >= 16 columns that fills the chip computes every output as a fused multi-exponentiation over chunks of 16 k
+ * (PAI_OPT_MATMUL_FUSED; PAI_OPT_MATMUL_PATH reports the path taken): window tables of the m K ciphertexts, and of the inverses of those in a row k of x that holds a negative
+ * scalar, are built once and shared by the d columns. A ciphertext without inverse mod n^2 in such a row ends the call
+ * with PAI_ERR_NOINV, as on the term path. */
 int pai_matmul(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t m, size_t K, int dtype, const void* x,
                size_t d, uint32_t* ct_out, int32_t* exp_out);
 
 /* Device-resident variants (device pointers, asynchronous on `stream`, a hipStream_t; pai_mul_dev and
- * pai_matmul_dev synchronise `stream` once, for the single host-side inversion of the batch). pai_encrypt_dev never
+ * pai_matmul_dev synchronise `stream` once, for the single host-side inversion of the batch; the fused pai_matmul_dev
+ * synchronises once to read which rows of x hold a negative scalar, and a second time, for the inversion, only when
+ * one does). pai_encrypt_dev never
  * waits on the host: the public-key chain's batch inversion (chunks of >= 16384 elements) inverts its one top value
  * in a host function queued on `stream` (hipLaunchHostFunc), so the call stays asynchronous and capturable; only
  * the first device-RNG call that BUILDS a key's fixed-base tables synchronises the device (per-key setup). */
