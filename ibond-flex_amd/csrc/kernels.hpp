@@ -225,8 +225,8 @@ __device__ __forceinline__ void emit_words(uint32_t* slot, const uint32_t (&x)[L
   wave_lds_fence();
 }
 
-// Inverse of emit_words for a ciphertext-sized operand: the group copies `nwords` words (16-byte aligned,
-// nwords % 4 == 0, nwords + 2 <= S) into its LDS slot with 16-byte loads, then each lane cuts its L limbs
+// Inverse of emit_words for a ciphertext-sized operand: the group copies `nwords` words (nwords + 2 <= S) into its
+// LDS slot, with 16-byte loads where nwords % 4 == 0 (rows 16-byte aligned), then each lane cuts its L limbs
 // out of the slot (two words and one alignbit per limb). Used inside step loops, where the per-limb,
 // bounds-checked word loads of words_to_limbs (74 scalar loads, 37 branches) spill registers.
 template <int TPI>
@@ -235,7 +235,13 @@ __device__ __forceinline__ void stage_words_to_limbs(uint32_t* slot, const uint3
   const uint4* s4 = reinterpret_cast<const uint4*>(src);
   uint4* d4 = reinterpret_cast<uint4*>(slot);
   wave_lds_fence();                                   // earlier readers of the slot are done
-  for (int q = tig; q < nwords / 4; q += TPI) d4[q] = s4[q];
+  if ((nwords & 3) == 0) {
+    for (int q = tig; q < nwords / 4; q += TPI) d4[q] = s4[q];
+  } else {
+    // a key whose ciphertexts are no whole number of 16-byte rows (n of 1035 bits: 65 words, 2071 bits: 130): the rows
+    // are only 4-byte aligned, and the last nwords % 4 words lie past the last uint4
+    for (int j = tig; j < nwords; j += TPI) slot[j] = src[j];
+  }
   if (tig == 0) {
     slot[nwords] = 0u;
     slot[nwords + 1] = 0u;

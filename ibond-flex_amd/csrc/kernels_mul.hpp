@@ -173,6 +173,7 @@ __device__ __forceinline__ int encode_plain_max(int dtype, const void* x, long l
     neg = v < 0;
     mag = neg ? (uint64_t)0 - (uint64_t)v : (uint64_t)v;
     if (mag == 0) return ST_OK;
+    if (E > max_bits / 4) return ST_ENC_RANGE;   // 1 + 4 E bits are past the range already, and 4 E must not wrap
     sh = 4 * E;     // exact: numpy casts int arrays to object (Python ints) for the object add loop
   }
   if (mag != 0 && (64 - __clzll(mag)) + sh > max_bits) return ST_ENC_RANGE;

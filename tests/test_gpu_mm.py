@@ -194,7 +194,8 @@ def test_fused_equals_term_path_2048(ctxs):
 
 
 def test_fused_equals_term_path_4096(golden):
-    """Arbitrary random units mod n^2 as ciphertexts (the oracle's r^n is too slow at this size), public key only."""
+    """Arbitrary random units mod n^2 as ciphertexts (the oracle's r^n is too slow at this size), public key only. Both
+    paths share k_add<8> and the word packing, so the 6 outputs are also the oracle's."""
     N = _native()
     n = int(golden["keys"]["4096"]["n"], 16)
     ctx = N.Context(n, 0, lib=_native().load_library(_native().XCHECK_LIB_PATH))
@@ -203,7 +204,10 @@ def test_fused_equals_term_path_4096(golden):
     cs = [int.from_bytes(rng.bytes(1024), "little") % (n * n) for _ in range(m * K)]
     ct = N.ints_to_words(cs, ctx.ct_words)
     ex = rng.integers(-12, 30, m * K).astype(np.int32)
-    _both_paths(ctx, ct, ex, m, K, _scalars(K, d, np.float64, 11), d)
+    x = _scalars(K, d, np.float64, 11)
+    out, oe = _both_paths(ctx, ct, ex, m, K, x, d)
+    got = list(zip(N.words_to_ints(out), (int(e) for e in oe)))
+    assert got == _oracle_dot(cs, [int(e) for e in ex], m, K, x, d, O.Key(n))
 
 
 def test_signs(ctxs, spread):

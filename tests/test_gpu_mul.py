@@ -85,8 +85,9 @@ def _random_cts(key, count, seed):
 @pytest.mark.parametrize("nb", [1024, 2048])
 @pytest.mark.parametrize("count", [1, 64, 65, 300])
 def test_mul_vs_oracle_mixed_scalars(ctxs, nb, count):
-    """Mixed signs, zeros, tiny and huge magnitudes, float32 / float64 / int64 scalars; ragged counts
-    around the inversion segment (64) so the inversion tree has 1, 2 and 3 levels."""
+    """Mixed signs, zeros, tiny and huge magnitudes, float32 / float64 / int64 scalars; ragged counts. At these counts
+    every inversion level runs segments of 4 values (flexpai.hip batch_invert: max(4, min(INV_SEG, n / 4096))), so the
+    tree has 1, 3, 4 and 5 levels; the longer segments are in test_gpu_ops_sizes.py."""
     N = _native()
     ctx, key = ctxs[nb]
     cs, es = _random_cts(key, count, 11 + count)
