@@ -56,6 +56,17 @@ __device__ __forceinline__ int encode_int(int64_t v, bool fixed, int fexp, int64
   return ST_OK;
 }
 
+// The encoding every kernel applies to element i of a plaintext array x: dtype 0 = float32, 1 = float64, 2 = int64
+// (PAI_F32 / PAI_F64 / PAI_I64); exp_mode != 0 fixes the exponent at fexp. Returns the status; M and e are written
+// as encode_float / encode_int write them (left alone on ST_ENC_RANGE).
+__device__ __forceinline__ int encode_elem(const void* x, int dtype, int exp_mode, int fexp, long long i, int64_t& M,
+                                           int& e) {
+  const bool fixed = exp_mode != 0;
+  if (dtype == 0) return encode_float((double)((const float*)x)[i], fixed, fexp, M, e);
+  if (dtype == 1) return encode_float(((const double*)x)[i], fixed, fexp, M, e);
+  return encode_int(((const int64_t*)x)[i], fixed, fexp, M, e);
+}
+
 // ---------------------------------------------------------------- ChaCha20 (RFC 8439 §2.3)
 __device__ __forceinline__ uint32_t rotl32(uint32_t v, int c) { return (v << c) | (v >> (32 - c)); }
 #define FPAI_QR(a, b, c, d)            \
@@ -86,5 +97,13 @@ __device__ __forceinline__ void chacha20_block(const uint32_t key[8], uint32_t c
   for (int i = 0; i < 16; ++i) out[i] = x[i] + s[i];
 }
 #undef FPAI_QR
+
+// Device-RNG obfuscator (PAI_OBF_RNG): the r of element g (index_base + position in the call) is the first rng_words
+// words of the ChaCha20 stream under the call's key with nonce (g lo32, g hi32, 'flxa'); this yields its 16-word
+// block b. The one definition of that stream: every encrypt chain draws r through it.
+__device__ __forceinline__ void obf_stream_block(const uint32_t key[8], uint32_t b, unsigned long long g,
+                                                 uint32_t out[16]) {
+  chacha20_block(key, b, (uint32_t)g, (uint32_t)(g >> 32), 0x66786169u, out);
+}
 
 }  // namespace fpai

@@ -57,6 +57,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_pe1.hpp"
 #include "engine_pe4.hpp"
 #include "engine_crt4.hpp"
+#include "encrypt_route.hpp"
 
 using namespace fpai;
 
@@ -189,9 +190,6 @@ struct pai_ctx {
   long long fb_last_n = 0;
   uint64_t fb_table_bytes = 0;
   GuardRec* d_guard = nullptr;  // test build: the address guards' record (guard.hpp); null in the product
-#if defined(FBS_AB) && (FBS_AB & 4)
-  FbDigitParams* d_abdig = nullptr;   // measurement build: k_fbs's digit parameters
-#endif
   // public-key fixed-base obfuscators (kernels_pfb.hpp): device-RNG encryption without the private key.
   // Built lazily past the break-even count (or pai_ctx_public_fb_prepare); never needed for correctness.
   int pfb_state = FB_UNTRIED;
@@ -2342,6 +2340,75 @@ int pai_ctx_info(const pai_ctx* c, int* key_bits, int* ct_words, int* pt_words) 
 }
 
 // ------------------------------------------------------------------ device entry points
+// The description of elements [off, ...) of the call e (kernels.hpp: plaintext source, obfuscator source, output): every
+// launcher's chunk loop takes its slice here.
+static int enc_r_words(const EncParams& e) {   // the words of r the kernels read (EncObf::r_words)
+  return e.obf == PAI_OBF_GIVEN ? e.r_words : e.obf == PAI_OBF_RNG ? e.rng_words : 0;
+}
+struct EncSlice {
+  EncPlain src;
+  EncObf rnd;
+  EncOut dst;
+};
+static EncSlice enc_slice(const EncParams& e, long long off) {
+  EncSlice s{};
+  s.src = EncPlain{(const char*)e.x + (size_t)off * (e.dtype == PAI_F32 ? 4 : 8), e.dtype, e.exp_mode, e.fexp};
+  s.rnd.obf = e.obf;
+  s.rnd.r = e.r ? e.r + (size_t)off * e.r_stride : nullptr;
+  s.rnd.r_stride = e.r_stride;
+  s.rnd.r_words = enc_r_words(e);
+  std::memcpy(s.rnd.rng_key, e.rng_key, sizeof(s.rnd.rng_key));
+  s.rnd.index_base = e.index_base + (unsigned long long)off;
+  s.dst = EncOut{e.ct + (size_t)off * e.ct_words, e.exp + off, e.status ? e.status + off : nullptr, e.ct_words};
+  return s;
+}
+// ... into a parameter struct that keeps the fields flat (EncParams, PeParams, Pe1Params: kernels.hpp says why)
+template <class P>
+static void set_flat(P& p, const EncSlice& s) {
+  p.x = s.src.x;
+  p.dtype = s.src.dtype;
+  p.exp_mode = s.src.exp_mode;
+  p.fexp = s.src.fexp;
+  p.obf = s.rnd.obf;
+  p.r = s.rnd.r;
+  p.r_stride = s.rnd.r_stride;
+  p.r_words = p.rng_words = s.rnd.r_words;
+  std::memcpy(p.rng_key, s.rnd.rng_key, sizeof(p.rng_key));
+  p.index_base = s.rnd.index_base;
+  p.ct = s.dst.ct;
+  p.exp = s.dst.exp;
+  p.status = s.dst.status;
+  p.ct_words = s.dst.ct_words;
+}
+
+// words of r that device RNG draws per element: 64 bits more than n
+static int rng_stream_words(const pai_ctx* c) { return (c->nb + 64 + 31) / 32; }
+
+// What encrypt_route (encrypt_route.hpp) reads of a context.
+static pai_route_facts route_facts(const pai_ctx* c) {
+  pai_route_facts f{};
+  f.has_priv = c->has_priv;
+  f.crt_enabled = c->crt_enabled;
+  f.fb_enabled = c->fb_enabled;
+  f.pfb_enabled = c->pfb_enabled;
+  f.crt_ok = c->crt_ok;
+  f.crt_sa = c->crt_sa;
+  f.fbg_ok = c->fbg_ok;
+  f.rows_sa = c->rows_sa;
+  f.crt4_ok = c->crt4_ok;
+  f.pe_ok = c->pe_ok;
+  f.pe1_ok = c->pe1_ok;
+  f.pe4_ok = c->pe4_ok;
+  f.pew_ok = c->d_pew_prog != nullptr;
+  f.pfb_supported = pfb_supported(c);
+  f.ct_words = c->ct_words;
+  // the rows stage r in crtw::RW_WORDS words and reduce it in at most KMAX_CHUNKS chunks of rows_sa limbs
+  f.rows_r_max = std::min(crtw::RW_WORDS, KMAX_CHUNKS * LB * c->rows_sa / 32);
+  f.crtw_max = c->crtw_max;
+  f.crt4_min = c->crt4_min;
+  return f;
+}
+
 template <int TPI>
 static int launch_encrypt(pai_ctx* c, EncParams& p, hipStream_t st) {
   constexpr int S = TPI * L;
@@ -2410,13 +2477,13 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
   if (const char* ds = getenv("FLEXPAI_DEBUG_SGS_STAGE")) dbg_stage = atoi(ds);
 #endif
   uint32_t* sgs_bcc = (uint32_t*)(sgs_bsum + (size_t)2 * 16 * chunk);
-  const size_t esz = e.dtype == PAI_F32 ? 4 : 8;
   for (long long off = 0; off < N; off += chunk) {
     const long long n = std::min(chunk, N - off);
+    const EncSlice sl = enc_slice(e, off);
     FbDigitParams pd{};
     pd.n = n;
-    std::memcpy(pd.rng_key, e.rng_key, sizeof(pd.rng_key));
-    pd.index_base = e.index_base + (unsigned long long)off;
+    std::memcpy(pd.rng_key, sl.rnd.rng_key, sizeof(pd.rng_key));
+    pd.index_base = sl.rnd.index_base;
     pd.K = c->fb_K;
     pd.W = c->fb_W_used;
     pd.raw_bits = c->fb_raw_bits;
@@ -2426,11 +2493,7 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
     pd.g = guard_args(c, 0, dig_words, 0, 0);
     const int gD = (int)std::min<long long>((long long)8 * c->cus, (n + FB_DIG_BLOCK - 1) / FB_DIG_BLOCK);
     stage_mark(c, 0, st);
-#if defined(FBS_AB) && (FBS_AB & 4)
-    if (!c->fb_shoup) HIPCHK(fb_launch_digits(pd, gD, st));   // (k_fbs draws its own)
-#else
     HIPCHK(fb_launch_digits(pd, gD, st));
-#endif
     stage_mark(c, 1, st);
     FbParams pf{};
     pf.halves = c->d_fb_halves;
@@ -2439,27 +2502,18 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
     pf.W = c->fb_W_used;
     pf.digits = digits;
     pf.out = w;
-    pf.x = (const char*)e.x + (size_t)off * esz;
-    pf.dtype = e.dtype;
-    pf.exp_mode = e.exp_mode;
-    pf.fexp = e.fexp;
-    pf.exp = e.exp + off;
-    pf.status = e.status ? e.status + off : nullptr;
+    pf.src = sl.src;
+    pf.dst = sl.dst;
     const int gF = (int)std::min<long long>(gxF, (n + EPB - 1) / EPB);
     if (c->fb_pair_s) {
-      FbpParams pp{c->d_fbp_halves, n, pf.K, pf.W, digits, w, pf.x, pf.dtype, pf.exp_mode, pf.fexp, pf.exp, pf.status};
+      FbpParams pp{c->d_fbp_halves, n, pf.K, pf.W, digits, w, sl.src, sl.dst};
       pp.g = guard_args(c, (unsigned long long)pf.K << pf.W, dig_words, w_words, 0);
-#if defined(FBS_AB) && (FBS_AB & 4)
-      if (!c->d_abdig && hipMalloc((void**)&c->d_abdig, sizeof(FbDigitParams)) != hipSuccess) return fail(PAI_ERR_HIP, "abD");
-      HIPCHK(hipMemcpyAsync(c->d_abdig, &pd, sizeof(pd), hipMemcpyHostToDevice, st));
-      pp.dig = c->d_abdig;
-#endif
 #if FLEXPAI_XCHECK
       if (!c->fb_shoup) HIPCHK(fbp_launch(c->fb_pair_s, pp, gF, st));
 #endif
       if (c->fb_shoup) HIPCHK(fbs_launch(c->fb_pair_s, pp, gF, st));
     } else if (grp && c->fb_gpair) {
-      const FbgpParams pg{c->d_fbgp_halves, n, pf.K, pf.W, digits, w, pf.x, pf.dtype, pf.exp_mode, pf.fexp, pf.exp, pf.status};
+      const FbgpParams pg{c->d_fbgp_halves, n, pf.K, pf.W, digits, w, sl.src, sl.dst};
       if (c->d_sgs_fb) {   // split pairs on Shoup rows (kernels_sgs.hpp), then the b sums applied
         int occS = 1;
         sgs_occupancy(&occS);
@@ -2467,13 +2521,12 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
         sp.g = guard_args(c, (unsigned long long)pf.K << pf.W, dig_words, w_words, 0);
         const long long nb = (n + SGP_PAIRS - 1) / SGP_PAIRS;
         HIPCHK(sgs_launch(sp, (int)std::max<long long>(1, std::min<long long>(nb, (long long)occS * c->cus / 2)), 2, st));
-        const SgsFinParams sf{c->d_sgs_fb, n, w, sgs_bsum, sgs_bcc, pf.x, pf.dtype, pf.exp_mode, pf.fexp, pf.exp, pf.status,
-                              dbg_stage};
+        const SgsFinParams sf{c->d_sgs_fb, n, w, sgs_bsum, sgs_bcc, sl.src, sl.dst.exp, sl.dst.status, dbg_stage};
         if (dbg_stage != 1) HIPCHK(sgs_launch_bfin(sf, 2, c->cus, st));
       } else if (c->d_sgp_fb) {   // split pairs (kernels_sgp.hpp): SGP_PAIRS elements per block, grid (gx, 2)
         int occS = 1;
         sgp_occupancy(&occS);
-        SgpParams sp{c->d_sgp_fb, n, pf.K, pf.W, digits, w, pf.x, pf.dtype, pf.exp_mode, pf.fexp, pf.exp, pf.status};
+        SgpParams sp{c->d_sgp_fb, n, pf.K, pf.W, digits, w, sl.src, sl.dst};
         sp.g = guard_args(c, (unsigned long long)pf.K << pf.W, dig_words, w_words, 0);
         const long long nb = (n + SGP_PAIRS - 1) / SGP_PAIRS;
         HIPCHK(sgp_launch(sp, (int)std::max<long long>(1, std::min<long long>(nb, (long long)occS * c->cus / 2)), 2, st));
@@ -2497,7 +2550,7 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
         sw.out = w;
         HIPCHK(sgp_launch_w(sw, 2, c->cus, st));
       } else if (c->fb_gpair) {
-        const FbgpParams pg{c->d_fbgp_halves, n, pf.K, pf.W, digits, w, pf.x, pf.dtype, pf.exp_mode, pf.fexp, pf.exp, pf.status};
+        const FbgpParams pg{c->d_fbgp_halves, n, pf.K, pf.W, digits, w, sl.src, sl.dst};
         const long long gb4 = (n + BLOCK / 4 - 1) / (BLOCK / 4);
         HIPCHK(fbgp_launch_w(pg, (int)std::max<long long>(1, std::min<long long>(gb4, (long long)occH * c->cus / 2)), st));
       }
@@ -2507,10 +2560,10 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
       // c = w_q + q^2 h on lanes (kernels_sgp.hpp k_sgp_fin): its intermediates' top 2S rows go to the digit buffer
       // (2K rows, dead by now; K >= S at every window the ladder has)
       if (c->d_sgp_q && c->ct_words == SGPF_CT_WORDS && pf.K >= SGP_S && sgp_fin_enabled()) {
-        const SgpFinParams sf{w, digits, n, c->d_sgp_q, e.ct + (size_t)off * c->ct_words, c->ct_words};
+        const SgpFinParams sf{w, digits, n, c->d_sgp_q, sl.dst.ct, c->ct_words};
         HIPCHK(sgp_launch_fin(sf, c->cus, st));
       } else {
-        FbgFinParams gf{w, SB, n, c->d_N, c->d_fb_q2Rn, c->mprime_N, e.ct + (size_t)off * c->ct_words, c->ct_words};
+        FbgFinParams gf{w, SB, n, c->d_N, c->d_fb_q2Rn, c->mprime_N, sl.dst.ct, c->ct_words};
         HIPCHK(grp_launch_fin(gf, (int)std::max<long long>(1, std::min<long long>(gb8, (long long)occC * c->cus)), st));
       }
       stage_mark(c, 3, st);
@@ -2519,7 +2572,7 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
     if (c->fb_pair_s) {   // Garner on pairs (kernels_fbp.hpp)
       int occP = 1;
       fbp_fin_occupancy(c->fb_pair_s, &occP);
-      FbpFinParams pp{w, n, c->d_fbp_fin_p, c->d_fbp_fin_cs, c->fbp_fin_mprime, e.ct + (size_t)off * c->ct_words,
+      FbpFinParams pp{w, n, c->d_fbp_fin_p, c->d_fbp_fin_cs, c->fbp_fin_mprime, sl.dst.ct,
                       c->ct_words};
       pp.g = guard_args(c, 0, 0, (unsigned long long)n * c->ct_words, w_words);
       const long long nb = (n + LANE_BLOCK - 1) / LANE_BLOCK;
@@ -2800,13 +2853,13 @@ static int launch_pfb(pai_ctx* c, const EncParams& e, hipStream_t st) {
   if ((rc = ensure_work(c, (dbytes + xbytes) * chunk))) return rc;
   uint32_t* digits = (uint32_t*)c->d_work;
   uint32_t* xw = (uint32_t*)((char*)c->d_work + dbytes * chunk);
-  const size_t esz = e.dtype == PAI_F32 ? 4 : 8;
   for (long long off = 0; off < N; off += chunk) {
     const long long n = std::min(chunk, N - off);
+    const EncSlice sl = enc_slice(e, off);
     PfbDigitParams pd{};
     pd.n = n;
-    std::memcpy(pd.rng_key, e.rng_key, sizeof(pd.rng_key));
-    pd.index_base = e.index_base + (unsigned long long)off;
+    std::memcpy(pd.rng_key, sl.rnd.rng_key, sizeof(pd.rng_key));
+    pd.index_base = sl.rnd.index_base;
     pd.K = c->pfb_K;
     pd.W = c->pfb_W_used;
     pd.digits = digits;
@@ -2814,13 +2867,11 @@ static int launch_pfb(pai_ctx* c, const EncParams& e, hipStream_t st) {
     stage_mark(c, 0, st);
     HIPCHK(pfb_launch_digits(pd, gD, st));
     stage_mark(c, 1, st);
-    const PfbParams pp{c->d_pfb, n, digits, (const char*)e.x + (size_t)off * esz, e.dtype, e.exp_mode, e.fexp,
-                       e.exp + off, e.status ? e.status + off : nullptr, xw};
+    const PfbParams pp{c->d_pfb, n, digits, sl.src, sl.dst, xw};
     if (c->d_sgp_pfb) {   // split pairs (kernels_sgp.hpp)
       int occS = 1;
       sgp_occupancy(&occS);
-      SgpParams sp{c->d_sgp_pfb, n, c->pfb_K, c->pfb_W_used, digits, xw, pp.x, pp.dtype, pp.exp_mode, pp.fexp, pp.exp,
-                   pp.status};
+      SgpParams sp{c->d_sgp_pfb, n, c->pfb_K, c->pfb_W_used, digits, xw, sl.src, sl.dst};
       sp.g = guard_args(c, (unsigned long long)c->pfb_K << c->pfb_W_used, (unsigned long long)c->pfb_K * chunk,
                         (unsigned long long)2 * PFB_SP * chunk, 0);
       const long long nb = (n + SGP_PAIRS - 1) / SGP_PAIRS;
@@ -2835,8 +2886,8 @@ static int launch_pfb(pai_ctx* c, const EncParams& e, hipStream_t st) {
     pf.k = c->d_pe;
     pf.n = n;
     pf.xw = xw;
-    pf.ct = e.ct + (size_t)off * c->ct_words;
-    pf.ct_words = c->ct_words;
+    pf.ct = sl.dst.ct;
+    pf.ct_words = sl.dst.ct_words;
     HIPCHK(pe_launch_fin(pf, c->cus, st));
     stage_mark(c, 3, st);
   }
@@ -2928,7 +2979,7 @@ static long long pef_min_elems() {
 static int launch_pe1(pai_ctx* c, const EncParams& e, hipStream_t st) {
   const long long N = e.n;
   const long long chunk = std::min(N, CRT_CHUNK);
-  const int RW = e.obf == PAI_OBF_GIVEN ? e.r_words : e.rng_words;
+  const int RW = enc_r_words(e);
   const int kchunks = 2;   // r's digits in two chunks of S (zeros past its words): the constant is the pair of R^3
   if (RW <= 0 || 32 * RW > kchunks * LB * PE1_S) return fail(PAI_ERR_ARG, "1024-bit pair encrypt: obfuscator too wide");
   int occ = 1;
@@ -2939,23 +2990,12 @@ static int launch_pe1(pai_ctx* c, const EncParams& e, hipStream_t st) {
   if (rc) return rc;
   const size_t rwb = (size_t)RW * 4, xwb = (size_t)2 * PE1_S * 4;   // per element
   if ((rc = ensure_work(c, (rwb + xwb) * chunk))) return rc;
-  const size_t esz = e.dtype == PAI_F32 ? 4 : 8;
   for (long long off = 0; off < N; off += chunk) {
     const long long n = std::min(chunk, N - off);
     hipEvent_t* ev = stage_chunk(c);
     if (ev) c->nev = 4;
     Pe1Params p{};
-    p.x = (const char*)e.x + (size_t)off * esz;
-    p.dtype = e.dtype;
-    p.exp_mode = e.exp_mode;
-    p.fexp = e.fexp;
-    p.obf = e.obf;
-    p.r = e.r ? e.r + (size_t)off * e.r_stride : nullptr;
-    p.r_stride = e.r_stride;
-    p.r_words = e.r_words;
-    p.rng_words = e.rng_words;
-    std::memcpy(p.rng_key, e.rng_key, sizeof(p.rng_key));
-    p.index_base = e.index_base + (unsigned long long)off;
+    set_flat(p, enc_slice(e, off));
     p.n = n;
     p.nl = c->d_pe1_n;
     p.one = c->d_pe1_one;
@@ -2967,10 +3007,6 @@ static int launch_pe1(pai_ctx* c, const EncParams& e, hipStream_t st) {
     p.rw_words = RW;
     p.xw = (uint32_t*)((char*)c->d_work + rwb * chunk);
     p.scratch = (uint32_t*)c->d_scratch;
-    p.ct = e.ct + (size_t)off * c->ct_words;
-    p.exp = e.exp + off;
-    p.status = e.status ? e.status + off : nullptr;
-    p.ct_words = c->ct_words;
     const DecPairPreParams pre{c->d_pe1_half, n, p.rw, RW, kchunks, p.xw};
     HIPCHK(pe1_launch(p, pre, gx, c->cus, st, ev));
   }
@@ -2987,32 +3023,17 @@ static int launch_pe(pai_ctx* c, const EncParams& e, hipStream_t st) {
   const size_t xbytes = (size_t)2 * D4_S * 4;   // per element, + 8 for M
   const size_t awbytes = c->pef_ok ? (size_t)c->pt_words * 4 : 0, iobytes = c->pef_ok ? (size_t)D4_S * 4 : 0;
   if ((rc = ensure_work(c, (xbytes + 8 + awbytes + iobytes) * chunk))) return rc;
-  const size_t esz = e.dtype == PAI_F32 ? 4 : 8;
   for (long long off = 0; off < N; off += chunk) {
     const long long n = std::min(chunk, N - off);
     hipEvent_t* ev = stage_chunk(c);
     if (ev) c->nev = 4;
     PeParams p{};
     p.k = c->d_pe;
-    p.x = (const char*)e.x + (size_t)off * esz;
-    p.dtype = e.dtype;
-    p.exp_mode = e.exp_mode;
-    p.fexp = e.fexp;
-    p.obf = e.obf;
-    p.r = e.r ? e.r + (size_t)off * e.r_stride : nullptr;
-    p.r_stride = e.r_stride;
-    p.r_words = e.r_words;
-    p.rng_words = e.rng_words;
-    std::memcpy(p.rng_key, e.rng_key, sizeof(p.rng_key));
-    p.index_base = e.index_base + (unsigned long long)off;
+    set_flat(p, enc_slice(e, off));
     p.n = n;
     p.xw = (uint32_t*)c->d_work;
     p.M = (int64_t*)((char*)c->d_work + xbytes * chunk);
     p.scratch = (uint32_t*)c->d_scratch;
-    p.ct = e.ct + (size_t)off * c->ct_words;
-    p.ct_words = c->ct_words;
-    p.exp = e.exp + off;
-    p.status = e.status ? e.status + off : nullptr;
     if (!c->pef_ok || n < pef_min_elems()) {
       HIPCHK(pe_launch(p, g, st, ev));
       continue;
@@ -3038,7 +3059,7 @@ static int launch_pe(pai_ctx* c, const EncParams& e, hipStream_t st) {
 static int launch_pe4(pai_ctx* c, const EncParams& e, hipStream_t st) {
   const long long N = e.n;
   const long long chunk = std::min(N, CRT_CHUNK);
-  const int RW = e.obf == PAI_OBF_GIVEN ? e.r_words : e.rng_words;
+  const int RW = enc_r_words(e);
   if (RW <= 0 || 32 * RW > 2 * LB * PE4_S)   // r's 2 S digits (its words are staged in the same 2 S slot words)
     return fail(PAI_ERR_ARG, "4096-bit pair encrypt: obfuscator too wide");
   Pe4Geom g;
@@ -3047,32 +3068,20 @@ static int launch_pe4(pai_ctx* c, const EncParams& e, hipStream_t st) {
   if (rc) return rc;
   const size_t xbytes = (size_t)2 * PE4_S * 4;   // per element, + 8 for M
   if ((rc = ensure_work(c, (xbytes + 8) * chunk))) return rc;
-  const size_t esz = e.dtype == PAI_F32 ? 4 : 8;
   for (long long off = 0; off < N; off += chunk) {
     const long long n = std::min(chunk, N - off);
     hipEvent_t* ev = stage_chunk(c);
     if (ev) c->nev = 4;
     Pe4Params p{};
     p.k = c->d_pe4;
-    p.x = (const char*)e.x + (size_t)off * esz;
-    p.dtype = e.dtype;
-    p.exp_mode = e.exp_mode;
-    p.fexp = e.fexp;
-    p.obf = e.obf;
-    p.r = e.r ? e.r + (size_t)off * e.r_stride : nullptr;
-    p.r_stride = e.r_stride;
-    p.r_words = e.r_words;
-    p.rng_words = e.rng_words;
-    std::memcpy(p.rng_key, e.rng_key, sizeof(p.rng_key));
-    p.index_base = e.index_base + (unsigned long long)off;
+    const EncSlice sl = enc_slice(e, off);
+    p.src = sl.src;
+    p.rnd = sl.rnd;
+    p.dst = sl.dst;
     p.n = n;
     p.xw = (uint32_t*)c->d_work;
     p.M = (int64_t*)((char*)c->d_work + xbytes * chunk);
     p.scratch = (uint32_t*)c->d_scratch;
-    p.ct = e.ct + (size_t)off * c->ct_words;
-    p.ct_words = c->ct_words;
-    p.exp = e.exp + off;
-    p.status = e.status ? e.status + off : nullptr;
     HIPCHK(pe4_launch(p, g, st, ev));
   }
   return 0;
@@ -3081,12 +3090,10 @@ static int launch_pe4(pai_ctx* c, const EncParams& e, hipStream_t st) {
 // k_crt_fin over elements [off, off + n) of the call: c = (u_p q^2 + u_q p^2) c0 mod n^2 from u [2][sb][n]
 static int crt_finish(pai_ctx* c, const EncParams& e, const uint32_t* u, int sb, long long off, long long n,
                       hipStream_t st) {
-  const size_t esz = e.dtype == PAI_F32 ? 4 : 8;
+  const EncSlice sl = enc_slice(e, off);
   CrtFinParams f{};
-  f.x = (const char*)e.x + (size_t)off * esz;
-  f.dtype = e.dtype;
-  f.exp_mode = e.exp_mode;
-  f.fexp = e.fexp;
+  f.src = sl.src;
+  f.dst = sl.dst;
   f.u = u;
   f.sb = sb;
   f.n = n;
@@ -3095,10 +3102,6 @@ static int crt_finish(pai_ctx* c, const EncParams& e, const uint32_t* u, int sb,
   f.kq = c->d_kq;
   f.kp = c->d_kp;
   f.mprime = c->mprime_N;
-  f.ct = e.ct + (size_t)off * c->ct_words;
-  f.exp = e.exp + off;
-  f.status = e.status ? e.status + off : nullptr;
-  f.ct_words = c->ct_words;
   switch (c->tpi_e) {
     case 2: return launch_crt_fin<2>(c, f, st);
     case 4: return launch_crt_fin<4>(c, f, st);
@@ -3109,7 +3112,7 @@ static int crt_finish(pai_ctx* c, const EncParams& e, const uint32_t* u, int sb,
 
 // A call of at most crtw_max elements: both exponentiations on 16-lane rows (k_crt_w, kernels_crtw.hpp), then
 // k_crt_fin. Same constants, op lists and output as k_crt_a + k_crt_b_pair; stage times: k_crt_w, k_crt_fin.
-static int launch_crtw(pai_ctx* c, const EncParams& e, int sa, int sb, int r_words, int kchunks, hipStream_t st) {
+static int launch_crtw(pai_ctx* c, const EncParams& e, int sa, int sb, int kchunks, hipStream_t st) {
   const long long N = e.n;
   int rc = ensure_work(c, (size_t)2 * sb * 4 * N);
   if (rc) return rc;
@@ -3118,12 +3121,7 @@ static int launch_crtw(pai_ctx* c, const EncParams& e, int sa, int sb, int r_wor
   p.ha = c->d_crt_a;
   p.hb = c->d_crt_b;
   p.n = N;
-  p.obf = e.obf;
-  p.r = e.r;
-  p.r_stride = e.r_stride;
-  p.r_words = r_words;
-  std::memcpy(p.rng_key, e.rng_key, sizeof(p.rng_key));
-  p.index_base = e.index_base;
+  p.rnd = enc_slice(e, 0).rnd;
   p.kchunks = kchunks;
   p.out = u;
   stage_mark(c, 0, st);
@@ -3135,18 +3133,14 @@ static int launch_crtw(pai_ctx* c, const EncParams& e, int sa, int sb, int r_wor
 }
 
 template <int SA, int SB>
-static int launch_crt(pai_ctx* c, const EncParams& e, hipStream_t st) {
+static int launch_crt(pai_ctx* c, const EncParams& e, bool rows, hipStream_t st) {
   static_assert(SB == 2 * SA || SB == 2 * SA - 1, "stage sizes");
-  if (e.obf == PAI_OBF_RNG && c->fb_enabled && fb_wanted(c, e.n) && ensure_fb(c)) {
-    const int rc = launch_fb(c, e, st);
-    return rc ? rc : guard_collect(c, st);
-  }
   const long long N = e.n;
-  const int r_words = e.obf == PAI_OBF_GIVEN ? e.r_words : e.rng_words;
+  const int r_words = enc_r_words(e);
   const int kchunks = (32 * r_words + LB * SA - 1) / (LB * SA);
   if (kchunks > KMAX_CHUNKS || (e.obf == PAI_OBF_RNG && r_words > RBUF_WORDS))
     return fail(PAI_ERR_ARG, "CRT encrypt: obfuscator too wide");
-  if (N <= c->crtw_max) return launch_crtw(c, e, SA, SB, r_words, kchunks, st);
+  if (rows) return launch_crtw(c, e, SA, SB, kchunks, st);
   const long long chunk = std::min(N, CRT_CHUNK);
   int occA = 1, occB = 1;
   if (crt_lane_occupancy(SA, &occA, &occB)) return fail(PAI_ERR_KEY, "CRT encrypt: unsupported size");
@@ -3171,12 +3165,7 @@ static int launch_crt(pai_ctx* c, const EncParams& e, hipStream_t st) {
     CrtParams pa{};
     pa.halves = c->d_crt_a;
     pa.n = n;
-    pa.obf = e.obf;
-    pa.r = e.r ? e.r + (size_t)off * e.r_stride : nullptr;
-    pa.r_stride = e.r_stride;
-    pa.r_words = r_words;
-    std::memcpy(pa.rng_key, e.rng_key, sizeof(pa.rng_key));
-    pa.index_base = e.index_base + (unsigned long long)off;
+    pa.rnd = enc_slice(e, off).rnd;
     pa.kchunks = kchunks;
     pa.out = y;
     pa.scratch = (uint32_t*)c->d_scratch;
@@ -3208,7 +3197,7 @@ constexpr long long CRT4_CHUNK = 1ll << 18;
 static int launch_crt4(pai_ctx* c, const EncParams& e, hipStream_t st) {
   constexpr int S = D4_S;
   const long long N = e.n;
-  const int r_words = e.obf == PAI_OBF_GIVEN ? e.r_words : e.rng_words;
+  const int r_words = enc_r_words(e);
   const int kchunks = (32 * r_words + LB * S - 1) / (LB * S);
   if (kchunks > KMAX_CHUNKS || (e.obf == PAI_OBF_RNG && r_words > RBUF_WORDS))
     return fail(PAI_ERR_ARG, "CRT encrypt: obfuscator too wide");
@@ -3227,12 +3216,7 @@ static int launch_crt4(pai_ctx* c, const EncParams& e, hipStream_t st) {
     p.ha = c->d_crt_a;
     p.hb = c->d_crt4_b;
     p.n = n;
-    p.obf = e.obf;
-    p.r = e.r ? e.r + (size_t)off * e.r_stride : nullptr;
-    p.r_stride = e.r_stride;
-    p.r_words = r_words;
-    std::memcpy(p.rng_key, e.rng_key, sizeof(p.rng_key));
-    p.index_base = e.index_base + (unsigned long long)off;
+    p.rnd = enc_slice(e, off).rnd;
     p.kchunks = kchunks;
     p.y = y;
     p.u = u;
@@ -3272,7 +3256,7 @@ int pai_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mo
   p.r = d_r_words;
   p.r_stride = (long long)r_stride_words;
   p.r_words = (int)r_words;
-  p.rng_words = (c->nb + 64 + 31) / 32;
+  p.rng_words = rng_stream_words(c);
   if (rng_key32)
     for (int i = 0; i < 8; ++i) std::memcpy(&p.rng_key[i], rng_key32 + 4 * i, 4);
   p.index_base = index_base;
@@ -3288,34 +3272,34 @@ int pai_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mo
   p.nprog = c->nprog;
   p.ct_words = c->ct_words;
   hipStream_t st = (hipStream_t)stream;
-  if (obf_mode == PAI_OBF_RNG && c->fbg_ok && c->crt_enabled && c->fb_enabled && fb_wanted(c, p.n) && ensure_fb(c)) {
+  const int r_eff = enc_r_words(p);
+  const EncryptRoute rt = encrypt_route(route_facts(c), obf_mode, p.n, r_eff);
+  // the impure steps: a call counts towards a sampler's break-even, and builds its tables, only for the sampler named
+  if (rt.sampler == PAI_SAMPLER_KEY && fb_wanted(c, p.n) && ensure_fb(c)) {
     const int rc = launch_fb(c, p, st);
     return rc ? rc : guard_collect(c, st);
   }
-  if (obf_mode != PAI_OBF_NONE && c->rows_sa && c->crt_enabled && p.n <= c->crtw_max) {   // 4096 bits, protocol-sized
-    const int r_words = obf_mode == PAI_OBF_GIVEN ? p.r_words : p.rng_words;
-    const int kchunks = (32 * r_words + LB * c->rows_sa - 1) / (LB * c->rows_sa);
-    if (kchunks <= KMAX_CHUNKS && r_words <= crtw::RW_WORDS)
-      return launch_crtw(c, p, c->rows_sa, 2 * c->rows_sa, r_words, kchunks, st);
-  }
-  if (obf_mode != PAI_OBF_NONE && c->crt_ok && c->crt_enabled) {
-    if (c->crt_sa == 19) return launch_crt<19, 37>(c, p, st);
-    if (c->crt_sa == 37) return launch_crt<37, 74>(c, p, st);
-  }
-  if (obf_mode != PAI_OBF_NONE && c->crt4_ok && c->crt_enabled && p.n > c->crt4_min) return launch_crt4(c, p, st);
-  if (obf_mode == PAI_OBF_RNG && c->pfb_enabled && pfb_supported(c) && pfb_wanted(c, p.n) && ensure_pfb(c)) {
+  if (rt.sampler == PAI_SAMPLER_PUBLIC && pfb_wanted(c, p.n) && ensure_pfb(c)) {
     const int rc = launch_pfb(c, p, st);
     return rc ? rc : guard_collect(c, st);
   }
-  if (obf_mode != PAI_OBF_NONE && p.n <= c->crtw_max && c->d_pew_prog) {   // protocol-sized: k_pe_w on rows
-    stage_mark(c, 0, st);
-    HIPCHK(pew_launch(c->S_e, p, c->d_pew_prog, c->pew_nprog, st));
-    stage_mark(c, 1, st);
-    return 0;
+  switch (rt.chain) {
+    case PAI_CHAIN_CRT_ROWS4:
+      return launch_crtw(c, p, c->rows_sa, 2 * c->rows_sa, (32 * r_eff + LB * c->rows_sa - 1) / (LB * c->rows_sa), st);
+    case PAI_CHAIN_CRT_ROWS:
+    case PAI_CHAIN_CRT_LANE:
+      return c->crt_sa == 19 ? launch_crt<19, 37>(c, p, rt.chain == PAI_CHAIN_CRT_ROWS, st)
+                             : launch_crt<37, 74>(c, p, rt.chain == PAI_CHAIN_CRT_ROWS, st);
+    case PAI_CHAIN_CRT4: return launch_crt4(c, p, st);
+    case PAI_CHAIN_PE_ROWS:
+      stage_mark(c, 0, st);
+      HIPCHK(pew_launch(c->S_e, p, c->d_pew_prog, c->pew_nprog, st));
+      stage_mark(c, 1, st);
+      return 0;
+    case PAI_CHAIN_PE: return launch_pe(c, p, st);
+    case PAI_CHAIN_PE1: return launch_pe1(c, p, st);
+    case PAI_CHAIN_PE4: return launch_pe4(c, p, st);
   }
-  if (obf_mode != PAI_OBF_NONE && c->pe_ok && c->ct_words == 2 * 64) return launch_pe(c, p, st);
-  if (obf_mode != PAI_OBF_NONE && c->pe1_ok) return launch_pe1(c, p, st);
-  if (obf_mode != PAI_OBF_NONE && c->pe4_ok && !c->has_priv) return launch_pe4(c, p, st);
   switch (c->tpi_e) {
     case 2: return launch_encrypt<2>(c, p, st);
     case 4: return launch_encrypt<4>(c, p, st);
@@ -4360,8 +4344,12 @@ int pai_encrypt(pai_ctx* c, int dtype, const void* x, size_t N, int exp_mode, in
   // not depend on how it is chunked
   HostCall hc(c);
   if (obf_mode == PAI_OBF_RNG) {
-    if ((c->crt_ok || c->fbg_ok) && c->crt_enabled) c->fb_call = fb_wanted(c, (long long)N) ? 1 : -1;
-    else if (c->pfb_enabled && pfb_supported(c)) c->pfb_call = pfb_wanted(c, (long long)N) ? 1 : -1;
+    const int sampler = encrypt_route(route_facts(c), obf_mode, (long long)N, rng_stream_words(c)).sampler;
+    if (sampler == PAI_SAMPLER_KEY) c->fb_call = fb_wanted(c, (long long)N) ? 1 : -1;
+    // not through the route: a key holder's call counts towards the key holder's break-even here with the fixed base
+    // switched off too, which the device entry does not do (pai_ctx_fixed_base_policy's `seen` reports it)
+    else if ((c->crt_ok || c->fbg_ok) && c->crt_enabled) c->fb_call = fb_wanted(c, (long long)N) ? 1 : -1;
+    else if (sampler == PAI_SAMPLER_PUBLIC) c->pfb_call = pfb_wanted(c, (long long)N) ? 1 : -1;
   }
   // every chunk's kernels are queued first; the copy stream then drains chunk i while i+1.. compute
   for (int i = 0; i < nch; ++i) {
@@ -4489,7 +4477,17 @@ int pai_decrypt(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, do
   return 0;
 }
 
-// ------------------------------------------------------------------ debugging hook (tests / tools only)
+// ------------------------------------------------------------------ debugging hooks (tests / tools only)
+// The encrypt route of a context with these facts (encrypt_route.hpp); needs no context and no device.
+int pai_debug_encrypt_route(const pai_route_facts* facts, int obf_mode, long long n, int r_words, int* sampler,
+                            int* chain) {
+  if (!facts || obf_mode < 0 || obf_mode > 2) return fail(PAI_ERR_ARG, "pai_debug_encrypt_route: bad arguments");
+  const EncryptRoute rt = encrypt_route(*facts, obf_mode, n, r_words);
+  if (sampler) *sampler = rt.sampler;
+  if (chain) *chain = rt.chain;
+  return 0;
+}
+
 // Copies the per-half sampler outputs (c0 G_h^a_h mod h^2) of the last fixed-base chunk: limbs [2][SB][n] (k_fb,
 // k_fbg), or canonical pairs [2][2S][n] with *sb = 2S for the pair tables (k_fbs/k_fbp; the p half times q^-2).
 extern "C" int pai_debug_fb_w(pai_ctx* c, uint32_t* out, size_t max_words, long long* n, int* sb) {

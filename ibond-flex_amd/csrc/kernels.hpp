@@ -11,6 +11,33 @@ constexpr int TABLE_ODD = 16;   // sliding window k=5: odd powers x^1..x^31
 constexpr int TABLE_FIX = 32;   // fixed window k=5: x^0..x^31
 constexpr int32_t PAD_EXP = INT32_MIN;   // exponent of a padding operand of k_add (the value 1, skipped)
 
+// An encrypt call, described once: the chains' parameter structs embed the groups they read (src, rnd, dst), and the
+// host cuts them to a chunk's elements in one place (enc_slice, flexpai.hip). EncParams, PeParams and Pe1Params keep the
+// same fields flat, and SgsFinParams its exp / status: embedded, the fields land at other kernarg offsets, and the SGPR or
+// VGPR spill counts of k_encrypt, k_pe_w, k_pe_pre, k_pe1_words and k_sgs_bfin moved; the host fills those from the same
+// slice (set_flat).
+struct EncPlain {        // the plaintext source
+  const void* x;         // element i at index i of an array of dtype
+  int dtype, exp_mode, fexp;   // PAI_F32 / PAI_F64 / PAI_I64; PAI_EXP_*; the exponent of PAI_EXP_FIXED (encode_elem)
+};
+struct EncObf {          // the obfuscator source
+  int obf;               // PAI_OBF_*
+  const uint32_t* r;     // PAI_OBF_GIVEN: element i's words at r + i * r_stride
+  long long r_stride;    // words
+  // The words of r per element that the kernels read, whichever the source: the caller's width for PAI_OBF_GIVEN, the
+  // first words of the element's ChaCha20 stream for PAI_OBF_RNG ((key bits + 64 + 31) / 32), 0 for PAI_OBF_NONE. The
+  // flat structs still name the two sources apart (r_words, rng_words); the host sets both to this count.
+  int r_words;
+  uint32_t rng_key[8];   // PAI_OBF_RNG: the stream's key and the global index of element 0 (obf_stream_block)
+  unsigned long long index_base;
+};
+struct EncOut {          // the output
+  uint32_t* ct;          // element i at ct + i * ct_words
+  int32_t* exp;
+  int32_t* status;       // nullable
+  int ct_words;
+};
+
 struct EncParams {
   const void* x;
   int dtype, exp_mode, fexp, obf;
@@ -284,11 +311,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_encrypt(EncParams p) {
     const bool valid = inst < p.n;
     const long long ii = valid ? inst : p.n - 1;
     int64_t M = 0;
-    int e = 0, st;
-    const bool fixed = p.exp_mode != 0;
-    if (p.dtype == 0) st = encode_float((double)((const float*)p.x)[ii], fixed, p.fexp, M, e);
-    else if (p.dtype == 1) st = encode_float(((const double*)p.x)[ii], fixed, p.fexp, M, e);
-    else st = encode_int(((const int64_t*)p.x)[ii], fixed, p.fexp, M, e);
+    int e = 0;
+    const int st = encode_elem(p.x, p.dtype, p.exp_mode, p.fexp, ii, M, e);
 
     uint32_t a[L];
     make_c0<TPI>(M, p.nl, m, a, lane, tig);
@@ -302,7 +326,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_encrypt(EncParams p) {
         wave_lds_fence();
         for (int b = tig; b * 16 < p.rng_words; b += TPI) {
           uint32_t blk[16];
-          chacha20_block(p.rng_key, (uint32_t)b, (uint32_t)gidx, (uint32_t)(gidx >> 32), 0x66786169u, blk);
+          obf_stream_block(p.rng_key, b, gidx, blk);
 #pragma unroll
           for (int w = 0; w < 16; ++w) slot[b * 16 + w] = blk[w];
         }

@@ -52,14 +52,8 @@ struct CrtHalf {
 struct CrtParams {
   const CrtHalf* halves;    // [2]
   long long n;              // elements
-  // stage A inputs: obfuscator r
-  int obf;                  // PAI_OBF_GIVEN (1) or PAI_OBF_RNG (2)
-  const uint32_t* r;        // GIVEN: words, element i at r + i * r_stride
-  long long r_stride;
-  int r_words;              // words of r (GIVEN) or of the ChaCha stream (RNG)
-  uint32_t rng_key[8];
-  unsigned long long index_base;
-  int kchunks;              // stage A: ceil(32 r_words / (LB SA)) <= KMAX_CHUNKS
+  EncObf rnd;               // stage A input: PAI_OBF_GIVEN or PAI_OBF_RNG
+  int kchunks;              // stage A: ceil(32 rnd.r_words / (LB SA)) <= KMAX_CHUNKS
   const uint32_t* yin;      // stage B input  [2][SA][n]
   uint32_t* out;            // stage A: y [2][SA][n]; stage B: u [2][SB][n]
   uint32_t* scratch;        // per-lane tiles
@@ -206,13 +200,13 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_OCC) void k_crt_a(CrtParams p) {
     const long long i = base + threadIdx.x;
     const long long ii = i < p.n ? i : p.n - 1;
     // r words: the caller's (GIVEN) or this element's ChaCha stream staged in the lane scratch
-    const bool given = p.obf == 1;
-    const uint32_t* rg = p.r + (given ? ii * p.r_stride : 0);
+    const bool given = p.rnd.obf == 1;
+    const uint32_t* rg = p.rnd.r + (given ? ii * p.rnd.r_stride : 0);
     if (!given) {
-      const unsigned long long g = p.index_base + (unsigned long long)ii;
-      for (int b = 0; b * 16 < p.r_words; ++b) {
+      const unsigned long long g = p.rnd.index_base + (unsigned long long)ii;
+      for (int b = 0; b * 16 < p.rnd.r_words; ++b) {
         uint32_t blk[16];
-        chacha20_block(p.rng_key, (uint32_t)b, (uint32_t)g, (uint32_t)(g >> 32), 0x66786169u, blk);
+        obf_stream_block(p.rnd.rng_key, b, g, blk);
 #pragma unroll
         for (int w = 0; w < 4; ++w)
           tl.quad(LANE_NTILE * tile_quads<SA>() + b * 4 + w) =
@@ -232,7 +226,7 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_OCC) void k_crt_a(CrtParams p) {
       uint64_t P[SA];
 #pragma unroll
       for (int j = 0; j < SA; ++j) P[j] = 0;
-      const int nw = p.r_words;
+      const int nw = p.rnd.r_words;
 #pragma unroll 1
       for (int k = 0; k < p.kchunks; ++k) {
         uint32_t b[SA], cst[SA];
@@ -260,8 +254,8 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_OCC) void k_crt_a(CrtParams p) {
 
 // ---------------------------------------------------------------- finish: c = (u_p q^2 + u_q p^2) c0 mod n^2
 struct CrtFinParams {
-  const void* x;
-  int dtype, exp_mode, fexp;
+  EncPlain src;
+  EncOut dst;
   const uint32_t* u;        // [2][SB][n]
   int sb;
   long long n;
@@ -270,10 +264,6 @@ struct CrtFinParams {
   const uint32_t* kq;       // q^2 R^2 mod n^2
   const uint32_t* kp;       // p^2 R^2 mod n^2
   uint32_t mprime;
-  uint32_t* ct;
-  int32_t* exp;
-  int32_t* status;
-  int ct_words;
 };
 
 template <int TPI>
@@ -292,11 +282,8 @@ __global__ __launch_bounds__(BLOCK, 1) void k_crt_fin(CrtFinParams p) {
     const bool valid = inst < p.n;
     const long long ii = valid ? inst : p.n - 1;
     int64_t M = 0;
-    int e = 0, st;
-    const bool fixed = p.exp_mode != 0;
-    if (p.dtype == 0) st = encode_float((double)((const float*)p.x)[ii], fixed, p.fexp, M, e);
-    else if (p.dtype == 1) st = encode_float(((const double*)p.x)[ii], fixed, p.fexp, M, e);
-    else st = encode_int(((const int64_t*)p.x)[ii], fixed, p.fexp, M, e);
+    int e = 0;
+    const int st = encode_elem(p.src.x, p.src.dtype, p.src.exp_mode, p.src.fexp, ii, M, e);
     // step 0: acc = u_p * q^2 R ; step 1: acc += u_q * p^2 R ; step 2: acc * c0
     uint32_t acc[L];
     for (int step = 0; step < 3; ++step) {
@@ -332,10 +319,10 @@ __global__ __launch_bounds__(BLOCK, 1) void k_crt_fin(CrtFinParams p) {
       }
     }
     cond_sub<TPI>(acc, m, lane, tig);
-    emit_words<TPI>(slot, acc, p.ct + ii * p.ct_words, p.ct_words, valid, tig);
+    emit_words<TPI>(slot, acc, p.dst.ct + ii * p.dst.ct_words, p.dst.ct_words, valid, tig);
     if (valid && tig == 0) {
-      p.exp[ii] = e;
-      if (p.status) p.status[ii] = st;
+      p.dst.exp[ii] = e;
+      if (p.dst.status) p.dst.status[ii] = st;
     }
   }
 }

@@ -33,13 +33,8 @@ struct Crt4Params {
   const CrtHalf* ha;       // [2] stage A: p_h, R^(K+1) mod p_h, op list over q_h mod (p_h - 1)
   const Crt4Half* hb;      // [2] stage B
   long long n;             // elements
-  int obf;                 // PAI_OBF_GIVEN (1) or PAI_OBF_RNG (2)
-  const uint32_t* r;       // GIVEN: words, element i at r + i * r_stride
-  long long r_stride;
-  int r_words;             // words of r (GIVEN) or of the ChaCha stream (RNG, <= RBUF_WORDS)
-  uint32_t rng_key[8];
-  unsigned long long index_base;
-  int kchunks;             // ceil(32 r_words / (LB S)) <= KMAX_CHUNKS
+  EncObf rnd;              // PAI_OBF_GIVEN or PAI_OBF_RNG (then rnd.r_words <= RBUF_WORDS)
+  int kchunks;             // ceil(32 rnd.r_words / (LB S)) <= KMAX_CHUNKS
   uint32_t* y;             // [2][S][n]: y_h R mod p_h (< 2 p_h)
   uint32_t* u;             // [2][2 S][n]
   uint32_t* scratch;       // per-lane tiles (LaneScratch, tile_quads<S> quads per tile)
@@ -77,18 +72,18 @@ __global__ __launch_bounds__(LANE_BLOCK, 1) void k_crt4_pre(Crt4Params p) {
   const uint32_t* cK = H->c0 + (size_t)(p.kchunks - 1) * S;    // R^(K+1) mod p_h
   uint32_t* row = lds + threadIdx.x * C4_ROW;
   const LaneScratch tl = lane_scratch(p.scratch);
-  const bool given = p.obf == 1;
-  const int nw = p.r_words;
+  const bool given = p.rnd.obf == 1;
+  const int nw = p.rnd.r_words;
   for (long long base = (long long)blockIdx.x * LANE_BLOCK; base < p.n; base += (long long)gridDim.x * LANE_BLOCK) {
     const long long i = base + threadIdx.x;
     const long long ii = i < p.n ? i : p.n - 1;
     // r's words: the caller's (GIVEN) or this element's ChaCha stream staged in the lane scratch (as k_crt_a)
-    const uint32_t* rg = given ? p.r + ii * p.r_stride : nullptr;
+    const uint32_t* rg = given ? p.rnd.r + ii * p.rnd.r_stride : nullptr;
     if (!given) {
-      const unsigned long long g = p.index_base + (unsigned long long)ii;
+      const unsigned long long g = p.rnd.index_base + (unsigned long long)ii;
       for (int b = 0; b * 16 < nw; ++b) {
         uint32_t blk[16];
-        chacha20_block(p.rng_key, (uint32_t)b, (uint32_t)g, (uint32_t)(g >> 32), 0x66786169u, blk);
+        obf_stream_block(p.rnd.rng_key, b, g, blk);
 #pragma unroll
         for (int w = 0; w < 4; ++w)
           tl.quad(LANE_NTILE * TQ + b * 4 + w) = make_uint4(blk[4 * w], blk[4 * w + 1], blk[4 * w + 2], blk[4 * w + 3]);

@@ -291,13 +291,8 @@ struct Params {
   const CrtHalf* ha;            // [2] stage A halves (p_h, R^(K+1) mod p_h, 1, op list)
   const CrtHalf* hb;            // [2] stage B halves, 2S-limb lane constants (p_h^2, R^2, coef, op list; R = 2^(28 KB))
   long long n;
-  int obf;                      // PAI_OBF_GIVEN (1) or PAI_OBF_RNG (2)
-  const uint32_t* r;            // GIVEN: words, element i at r + i * r_stride
-  long long r_stride;
-  int r_words;                  // words of r (GIVEN) or of the ChaCha stream (RNG)
-  uint32_t rng_key[8];
-  unsigned long long index_base;
-  int kchunks;                  // ceil(32 r_words / (28 KA)) <= KMAX_CHUNKS
+  EncObf rnd;                   // PAI_OBF_GIVEN or PAI_OBF_RNG
+  int kchunks;                  // ceil(32 rnd.r_words / (28 KA)) <= KMAX_CHUNKS
   uint32_t* out;                // u [2][KB][n]
 };
 
@@ -340,7 +335,7 @@ __global__ __launch_bounds__(BLOCK_W) void k_crt_w(Params p) {
   const uint32_t* progA = uniform_ptr(HA->prog);
   const uint32_t* progB = uniform_ptr(HB->prog);
   const int nA = __builtin_amdgcn_readfirstlane(HA->nprog), nB = __builtin_amdgcn_readfirstlane(HB->nprog);
-  const bool given = p.obf == 1;
+  const bool given = p.rnd.obf == 1;
   for (long long base = (long long)blockIdx.x * GPW; base < p.n; base += (long long)gridDim.x * GPW) {
     const long long i = base + g;
     const long long ii = i < p.n ? i : p.n - 1;
@@ -349,19 +344,19 @@ __global__ __launch_bounds__(BLOCK_W) void k_crt_w(Params p) {
     uint32_t* RL = T + RW_WORDS;
     wave_lds_fence();
     if (given) {
-      const uint32_t* rg = p.r + ii * p.r_stride;
-      for (int w = tig; w < p.r_words; w += TPI) RW[w] = rg[w];
+      const uint32_t* rg = p.rnd.r + ii * p.rnd.r_stride;
+      for (int w = tig; w < p.rnd.r_words; w += TPI) RW[w] = rg[w];
     } else {
-      const unsigned long long gi = p.index_base + (unsigned long long)ii;
-      for (int b = tig; b * 16 < p.r_words; b += TPI) {
+      const unsigned long long gi = p.rnd.index_base + (unsigned long long)ii;
+      for (int b = tig; b * 16 < p.rnd.r_words; b += TPI) {
         uint32_t blk[16];
-        chacha20_block(p.rng_key, (uint32_t)b, (uint32_t)gi, (uint32_t)(gi >> 32), 0x66786169u, blk);
+        obf_stream_block(p.rnd.rng_key, b, gi, blk);
 #pragma unroll
         for (int w = 0; w < 16; ++w) RW[b * 16 + w] = blk[w];
       }
     }
     wave_lds_fence();
-    const int nw = p.r_words;
+    const int nw = p.rnd.r_words;
     for (int j = tig; j < p.kchunks * KA; j += TPI) {
       const int bit = j * LB, wi = bit >> 5, sh = bit & 31;
       const uint64_t lo = wi < nw ? (uint64_t)RW[wi] : 0ull;
@@ -539,11 +534,8 @@ __global__ __launch_bounds__(BLOCK_W) void k_pe_w(EncParams p, const uint32_t* p
     const bool valid = i < p.n;
     const long long ii = valid ? i : p.n - 1;
     int64_t M = 0;
-    int e = 0, st;
-    const bool fixed = p.exp_mode != 0;
-    if (p.dtype == 0) st = encode_float((double)((const float*)p.x)[ii], fixed, p.fexp, M, e);
-    else if (p.dtype == 1) st = encode_float(((const double*)p.x)[ii], fixed, p.fexp, M, e);
-    else st = encode_int(((const int64_t*)p.x)[ii], fixed, p.fexp, M, e);
+    int e = 0;
+    const int st = encode_elem(p.x, p.dtype, p.exp_mode, p.fexp, ii, M, e);
     {   // c0 = 1 + n M mod n^2 (n^2 - n |M| + 1 for M < 0: raw_encrypt.py's "sneaky inverse" gives the same value)
       const bool neg = M < 0;
       const uint64_t mag = neg ? (uint64_t)0 - (uint64_t)M : (uint64_t)M;
@@ -575,7 +567,7 @@ __global__ __launch_bounds__(BLOCK_W) void k_pe_w(EncParams p, const uint32_t* p
       const unsigned long long gi = p.index_base + (unsigned long long)ii;
       for (int b = tig; b * 16 < nw; b += TPI) {
         uint32_t blk[16];
-        chacha20_block(p.rng_key, (uint32_t)b, (uint32_t)gi, (uint32_t)(gi >> 32), 0x66786169u, blk);
+        obf_stream_block(p.rng_key, b, gi, blk);
 #pragma unroll
         for (int w = 0; w < 16; ++w) RW[b * 16 + w] = blk[w];
       }

@@ -69,10 +69,8 @@ struct FbParams {
   int K, W;                // digit positions, digit bits
   const uint32_t* digits;  // [2][K][n] (k_fb_digits)
   uint32_t* out;           // w [2][SB][n]: c0 G_h^a_h mod p_h^2 (< 2 p_h^2)
-  const void* x;           // plaintexts (encode: fixedpoint_number.py:46-90)
-  int dtype, exp_mode, fexp;
-  int32_t* exp;            // written by the p-half
-  int32_t* status;         // nullable
+  EncPlain src;
+  EncOut dst;              // exp and status, written by half 0 (ct: the finish kernels')
 };
 
 struct FbDigitParams {
@@ -113,7 +111,7 @@ __device__ __forceinline__ FbDigitKey fb_digit_key(const FbDigitParams& p, int h
 }
 
 // element i of half `half`: its raw stream staged in the LDS row a (ROW words), reduced modulo D_h in place, cut into
-// the K digits (k_fb_digits; and, in a measurement build, k_fbs's prologue, kernels_fbs.hpp FBS_AB & 4)
+// the K digits (k_fb_digits)
 template <int ROW>
 __device__ __forceinline__ void fb_digits_elem(const FbDigitParams& p, const FbDigitKey& dk, int half, long long i, uint32_t* a) {
   const FbRed* R = dk.R;

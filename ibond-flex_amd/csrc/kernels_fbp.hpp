@@ -66,14 +66,9 @@ struct FbpParams {
   int K, W;
   const uint32_t* digits;  // [2][K][n]
   uint32_t* out;           // canonical pairs (A limbs, then B) for k_fbp_fin in 64-element tiles (fbp_pair_index)
-  const void* x;
-  int dtype, exp_mode, fexp;
-  int32_t* exp;
-  int32_t* status;
+  EncPlain src;
+  EncOut dst;              // exp and status, written by half 0 (ct: the finish kernels')
   GuardArgs g;             // test build (guard.hpp): rows = K 2^W, digits = 2 K n, out = the pair tiles' words
-#if defined(FBS_AB) && (FBS_AB & 4)
-  const FbDigitParams* dig;   // measurement build (kernels_fbs.hpp FBS_AB & 4): k_fbs draws its own digits
-#endif
 };
 
 // LDS words at a byte offset from this lane's row base (offsets past the 16-bit immediate take a second base)
@@ -428,19 +423,19 @@ __global__ __launch_bounds__(LANE_BLOCK, 2) void k_fbp(FbpParams p) {
     uint32_t dn = K > 1 ? dg[p.n] : 0u;
     double xv;
     int64_t xi = 0;
-    if (p.dtype == 0) xv = (double)((const float*)p.x)[ii];
-    else if (p.dtype == 1) xv = ((const double*)p.x)[ii];
-    else { xi = ((const int64_t*)p.x)[ii]; xv = 0.0; }
+    if (p.src.dtype == 0) xv = (double)((const float*)p.src.x)[ii];
+    else if (p.src.dtype == 1) xv = ((const double*)p.src.x)[ii];
+    else { xi = ((const int64_t*)p.src.x)[ii]; xv = 0.0; }
     asm volatile("" : "+v"(d0), "+v"(dn), "+v"(xv), "+v"(xi));
     fb_row_to_lds<TQ>(table, d0, brow);
     int64_t M = 0;
     int e = 0, st;
-    const bool fixed = p.exp_mode != 0;
-    if (p.dtype == 2) st = encode_int(xi, fixed, p.fexp, M, e);
-    else st = encode_float(xv, fixed, p.fexp, M, e);
+    const bool fixed = p.src.exp_mode != 0;
+    if (p.src.dtype == 2) st = encode_int(xi, fixed, p.src.fexp, M, e);
+    else st = encode_float(xv, fixed, p.src.fexp, M, e);
     if (half == 0 && i < p.n) {
-      p.exp[i] = e;
-      if (p.status) p.status[i] = st;
+      p.dst.exp[i] = e;
+      if (p.dst.status) p.dst.status[i] = st;
     }
     uint32_t A[S], B[S];
     fbp_c0<S>(M, H, A, B);

@@ -39,32 +39,6 @@ struct FbsGeom<37> {   // 2048-bit keys: p_h < 2^1024, R = 2^1036
 template <int S>
 constexpr int fbs_row_quads() { return FbsGeom<S>::QA + FbsGeom<S>::QAP + FbsGeom<S>::QB; }
 
-// Row-layout A/B (round 5; tools/ab_fbs_rows.sh): builds of this header with FBS_AB set are
-// measurement-only libraries, never the product. FBS_AB & 1 ("T", traffic): rows addressed at a 384-B stride (three
-// aligned 128-B lines) and only the b R quads that fit in them fetched (the rest zero) -- the bytes of packed 384-B
-// rows, wrong ciphertexts; FBS_AB & 2 ("I", instructions): every digit of a and a' costs the v_alignbit + v_and that
-// cutting a 28-bit digit out of packed 32-bit words costs (on the same digit: same ciphertexts).
-// FBS_AB & 4 ("D"): k_fb_digits fused into k_fbs -- each element-half's even lane draws and reduces
-// its exponent and cuts the digits in a prologue (kernels_fb.hpp fb_digits_elem, staged in the wave's second row
-// buffer), stores them, and the product loop reads them back from L2 (agent-scope loads: another block may hold the
-// line in its L1); the host launches no k_fb_digits. Same digits, same ciphertexts.
-#ifndef FBS_AB
-#define FBS_AB 0
-#endif
-template <int S>
-constexpr int fbs_row_stride() { return (FBS_AB & 1) && S == 37 ? 24 : fbs_row_quads<S>(); }   // quads between rows
-template <int S>
-constexpr int fbs_b_fetch() { return (FBS_AB & 1) ? FbsGeom<S>::QB / 4 : FbsGeom<S>::QB / 2; }   // b R quads per lane
-__device__ __forceinline__ uint32_t fbs_ab_extract(uint32_t d) {
-#if FBS_AB & 2
-  uint32_t r, z = 0;
-  asm volatile("v_alignbit_b32 %0, %1, %2, %3" : "=v"(r) : "v"(d), "v"(d), "v"(z));
-  asm volatile("v_and_b32 %0, 0x0fffffff, %0" : "+v"(r));
-  return r;
-#else
-  return d;
-#endif
-}
 template <int S>
 constexpr int fbs_lds_quads() { return FbsGeom<S>::QA + FbsGeom<S>::QAP; }
 
@@ -244,7 +218,7 @@ struct FbsPairReader {
       static_assert(pending >= 0 && pending <= 15, "lgkmcnt range");
       asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(q[g]) : "i"(pending));
     }
-    return fbs_ab_extract(quad_word<J % 4>(q[g]));
+    return quad_word<J % 4>(q[g]);
   }
 };
 
@@ -260,10 +234,10 @@ __device__ __forceinline__ void fbs_row_fetch(const uint4* row, uint32_t lb, int
     asm volatile("" : "+s"(dst));
     __builtin_amdgcn_global_load_lds((const void*)(src + 2 * g), (__attribute__((address_space(3))) void*)(size_t)dst, 16, 0, 0);
   }
-  constexpr int QH = G::QB / 2, QF = fbs_b_fetch<S>();
-  const fbp_u32x4* b = reinterpret_cast<const fbp_u32x4*>(row + G::QA + G::QAP + QF * tig);
+  constexpr int QH = G::QB / 2;
+  const fbp_u32x4* b = reinterpret_cast<const fbp_u32x4*>(row + G::QA + G::QAP + QH * tig);
 #pragma unroll
-  for (int q = 0; q < QH; ++q) bv[q] = q < QF ? b[q] : fbp_u32x4{0u, 0u, 0u, 0u};
+  for (int q = 0; q < QH; ++q) bv[q] = b[q];
 }
 
 #if FLEXPAI_XCHECK
@@ -275,9 +249,6 @@ __device__ __forceinline__ uint32_t fbs_guard_digit(const FbpParams& p, int h, i
 }
 #define FBS_DIGIT(k) fbs_guard_digit(p, half, (k), ee, GS_FBS_DIGIT, GS_FBS_DVAL)
 #define FBS_ROW(k, d) FPAI_GUARD_IDX(p.g, GS_FBS_ROW, ((size_t)(k) << W) + (d), p.g.rows, ee)
-#elif FBS_AB & 4
-#define FBS_DIGIT(k) __hip_atomic_load(const_cast<uint32_t*>(dg + (size_t)(k) * p.n), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define FBS_ROW(k, d) (((size_t)(k) << W) + (d))
 #else
 #define FBS_DIGIT(k) dg[(size_t)(k) * p.n]
 #define FBS_ROW(k, d) (((size_t)(k) << W) + (d))
@@ -286,7 +257,7 @@ __device__ __forceinline__ uint32_t fbs_guard_digit(const FbpParams& p, int h, i
 template <int S>
 __global__ __launch_bounds__(LANE_BLOCK, 2) void k_fbs(FbpParams p) {
   using G = FbsGeom<S>;
-  constexpr int PW = G::PW, TQ = fbs_row_stride<S>(), WB = fbs_wave_buf_bytes<S>();
+  constexpr int PW = G::PW, TQ = fbs_row_quads<S>(), WB = fbs_wave_buf_bytes<S>();
   static_assert(PW == 32 || PW == 16, "b sum halves");
   constexpr int HW = PW / 2;   // b sum words per lane
   __shared__ __attribute__((aligned(16))) uint8_t lbuf[(LANE_BLOCK / 64) * 2 * WB];
@@ -311,14 +282,11 @@ __global__ __launch_bounds__(LANE_BLOCK, 2) void k_fbs(FbpParams p) {
     const bool valid = e < p.n;
     const long long ee = valid ? e : p.n - 1;
     int64_t M = 0;
-    int ex = 0, stt;
-    const bool fixed = p.exp_mode != 0;
-    if (p.dtype == 0) stt = encode_float((double)((const float*)p.x)[ee], fixed, p.fexp, M, ex);
-    else if (p.dtype == 1) stt = encode_float(((const double*)p.x)[ee], fixed, p.fexp, M, ex);
-    else stt = encode_int(((const int64_t*)p.x)[ee], fixed, p.fexp, M, ex);
+    int ex = 0;
+    const int stt = encode_elem(p.src.x, p.src.dtype, p.src.exp_mode, p.src.fexp, ee, M, ex);
     if (half == 0 && valid && !odd) {
-      p.exp[e] = ex;
-      if (p.status) p.status[e] = stt;
+      p.dst.exp[e] = ex;
+      if (p.dst.status) p.dst.status[e] = stt;
     }
     uint32_t X[S];   // even lane: A; odd lane: B -- (a_0, 0) from the first row (below)
     const uint32_t* dg = p.digits + (size_t)half * K * p.n + ee;
@@ -328,17 +296,6 @@ __global__ __launch_bounds__(LANE_BLOCK, 2) void k_fbs(FbpParams p) {
     static_assert(G::QB / 2 == HW / 4, "b R quads per lane");
     fbp_u32x4 bv[G::QB / 2];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the previous element's reads of both buffers are done
-#if FBS_AB & 4
-    {   // this element-half's digits (the even lane; staged in the wave's second row buffer), stored and waited
-      // (the parameters from device memory through an opaque pointer: held in registers across the element loop, they
-      // had spilled 140 VGPRs, 15 scratch accesses of them inside the product loop)
-      const FbDigitParams* dp = reinterpret_cast<const FbDigitParams*>(opaque_uniform(reinterpret_cast<const uint32_t*>(p.dig)));
-      const FbDigitKey dk = fb_digit_key(*dp, half);
-      uint32_t* arow = reinterpret_cast<uint32_t*>(lbuf + (threadIdx.x >> 6) * 2 * WB + WB) + (lane >> 1) * 37;
-      if (!odd) fb_digits_elem<37>(*dp, dk, half, ee, arow);
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    }
-#endif
     fbs_row_fetch<S>(table + (size_t)FBS_ROW(0, FBS_DIGIT(0)) * TQ, wbase, tig, bv);
     uint32_t dn = K > 1 ? FBS_DIGIT(1) : 0u;
     for (int k = 0; k < K; ++k) {

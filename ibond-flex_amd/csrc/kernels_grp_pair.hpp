@@ -43,10 +43,8 @@ struct FbgpParams {
   int K, W;
   const uint32_t* digits;  // [2][K][n]
   uint32_t* out;           // [2][148][n]: the pair [A: 74][B: 74], then w_h in place (k_fbgp_w)
-  const void* x;
-  int dtype, exp_mode, fexp;
-  int32_t* exp;
-  int32_t* status;
+  EncPlain src;
+  EncOut dst;              // exp and status, written by half 0 (ct: the finish kernels')
 };
 
 template <int TPI, int LL>
@@ -311,14 +309,11 @@ __global__ __launch_bounds__(BLOCK, 2) void k_fbgp(FbgpParams p) {
     const long long ii = valid ? inst : p.n - 1;
     const uint32_t* dg = p.digits + (size_t)half * K * p.n + ii;
     int64_t M = 0;
-    int e = 0, st;
-    const bool fixed = p.exp_mode != 0;
-    if (p.dtype == 0) st = encode_float((double)((const float*)p.x)[ii], fixed, p.fexp, M, e);
-    else if (p.dtype == 1) st = encode_float(((const double*)p.x)[ii], fixed, p.fexp, M, e);
-    else st = encode_int(((const int64_t*)p.x)[ii], fixed, p.fexp, M, e);
+    int e = 0;
+    const int st = encode_elem(p.src.x, p.src.dtype, p.src.exp_mode, p.src.fexp, ii, M, e);
     if (half == 0 && valid && tig == 0) {
-      p.exp[ii] = e;
-      if (p.status) p.status[ii] = st;
+      p.dst.exp[ii] = e;
+      if (p.dst.status) p.dst.status[ii] = st;
     }
     // c0 = the pair (1, (n / p_h) M mod p_h): the sum over the 16-bit chunks of |M| (< 2^18 p_h; negative M:
     // 2^20 p_h - sum), a valid operand (R >= 2^24 p_h)

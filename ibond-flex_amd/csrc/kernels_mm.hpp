@@ -33,13 +33,9 @@ constexpr int MM_KC = 16;
 
 // The reference's scalar encoding as k_mul applies it: status != OK -> M = 0.
 __device__ __forceinline__ void mm_encode(int dtype, const void* x, long long xi, int64_t& M, int& es) {
-  int st;
   M = 0;
   es = 0;
-  if (dtype == 0) st = encode_float((double)((const float*)x)[xi], false, 0, M, es);
-  else if (dtype == 1) st = encode_float(((const double*)x)[xi], false, 0, M, es);
-  else st = encode_int(((const int64_t*)x)[xi], false, 0, M, es);
-  if (st != ST_OK) M = 0;
+  if (encode_elem(x, dtype, 0, 0, xi, M, es) != ST_OK) M = 0;
 }
 
 struct MmSignParams {

@@ -64,10 +64,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_mul(MulParams p) {
     const long long ci = i * p.cs_i + k * p.cs_k;
     const long long xi = i * p.xs_i + k * p.xs_k + j * p.xs_j;
     int64_t M = 0;
-    int es = 0, st;
-    if (p.dtype == 0) st = encode_float((double)((const float*)p.x)[xi], false, 0, M, es);
-    else if (p.dtype == 1) st = encode_float(((const double*)p.x)[xi], false, 0, M, es);
-    else st = encode_int(((const int64_t*)p.x)[xi], false, 0, M, es);
+    int es = 0;
+    const int st = encode_elem(p.x, p.dtype, 0, 0, xi, M, es);
     if (st != ST_OK) M = 0;
     const bool negs = M < 0;
     const uint64_t e = negs ? (uint64_t)0 - (uint64_t)M : (uint64_t)M;

@@ -84,11 +84,8 @@ __global__ __launch_bounds__(LANE_BLOCK, 1) void k_pe_pre(PeParams p) {
     const long long ee = valid ? e : p.n - 1;
     if (valid && tig == 0) {   // encode (fixedpoint_number.py:46-90): M for k_pe_pow's final product
       int64_t M = 0;
-      int ex = 0, stt;
-      const bool fixed = p.exp_mode != 0;
-      if (p.dtype == 0) stt = encode_float((double)((const float*)p.x)[ee], fixed, p.fexp, M, ex);
-      else if (p.dtype == 1) stt = encode_float(((const double*)p.x)[ee], fixed, p.fexp, M, ex);
-      else stt = encode_int(((const int64_t*)p.x)[ee], fixed, p.fexp, M, ex);
+      int ex = 0;
+      const int stt = encode_elem(p.x, p.dtype, p.exp_mode, p.fexp, ee, M, ex);
       p.M[e] = M;
       p.exp[e] = ex;
       if (p.status) p.status[e] = stt;
@@ -106,7 +103,7 @@ __global__ __launch_bounds__(LANE_BLOCK, 1) void k_pe_pre(PeParams p) {
       const unsigned long long g = p.index_base + (unsigned long long)ee;
       for (int b = tig; b * 16 < nw; b += 2) {
         uint32_t blk[16];
-        chacha20_block(p.rng_key, (uint32_t)b, (uint32_t)g, (uint32_t)(g >> 32), 0x66786169u, blk);
+        obf_stream_block(p.rng_key, b, g, blk);
 #pragma unroll
         for (int w = 0; w < 16; ++w)
           if (b * 16 + w < nw) wbuf[b * 16 + w] = blk[w];

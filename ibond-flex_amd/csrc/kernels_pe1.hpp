@@ -50,7 +50,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_pe1_words(Pe1Params p) {
       const unsigned long long g = p.index_base + (unsigned long long)i;
       for (int b = 0; b * 16 < p.rw_words; ++b) {
         uint32_t blk[16];
-        chacha20_block(p.rng_key, (uint32_t)b, (uint32_t)g, (uint32_t)(g >> 32), 0x66786169u, blk);
+        obf_stream_block(p.rng_key, b, g, blk);
 #pragma unroll
         for (int w = 0; w < 16; ++w)
           if (b * 16 + w < p.rw_words) o[b * 16 + w] = blk[w];
@@ -115,11 +115,8 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_pe1_fin(Pe1Params p) {
   constexpr int S2 = 2 * S;
   for (long long i = (long long)blockIdx.x * LANE_BLOCK + threadIdx.x; i < p.n; i += (long long)gridDim.x * LANE_BLOCK) {
     int64_t M = 0;
-    int e = 0, st;
-    const bool fixed = p.exp_mode != 0;
-    if (p.dtype == 0) st = encode_float((double)((const float*)p.x)[i], fixed, p.fexp, M, e);
-    else if (p.dtype == 1) st = encode_float(((const double*)p.x)[i], fixed, p.fexp, M, e);
-    else st = encode_int(((const int64_t*)p.x)[i], fixed, p.fexp, M, e);
+    int e = 0;
+    const int st = encode_elem(p.x, p.dtype, p.exp_mode, p.fexp, i, M, e);
     uint32_t m[S], A[S], B[S], t[S], u[S];
 #pragma unroll
     for (int j = 0; j < S; ++j) {

@@ -43,21 +43,13 @@ struct Pe4Const {
 
 struct Pe4Params {
   const Pe4Const* k;
-  const void* x;
-  int dtype, exp_mode, fexp, obf;
-  const uint32_t* r;       // GIVEN: words, element i at r + i r_stride
-  long long r_stride;
-  int r_words, rng_words;
-  uint32_t rng_key[8];
-  unsigned long long index_base;
+  EncPlain src;
+  EncObf rnd;
+  EncOut dst;
   long long n;
   uint32_t* xw;            // [n][2 S] pairs ([A: S][B: S] per element)
   int64_t* M;              // [n] encodings (k_pe4_pre -> k_pe4_pow)
   uint32_t* scratch;       // k_pe4_pow's tiles (LaneScratch, PE4_TQ quads per lane per tile)
-  uint32_t* ct;
-  int ct_words;
-  int32_t* exp;
-  int32_t* status;
 };
 
 template <int TPI, int LL>
@@ -143,27 +135,24 @@ __global__ __launch_bounds__(BLOCK) void k_pe4_pre(Pe4Params p) {
     const long long ee = valid ? e : p.n - 1;
     if (valid && tig == 0) {   // encode (fixedpoint_number.py:46-90): M for k_pe4_pow's final product
       int64_t M = 0;
-      int ex = 0, stt;
-      const bool fixed = p.exp_mode != 0;
-      if (p.dtype == 0) stt = encode_float((double)((const float*)p.x)[ee], fixed, p.fexp, M, ex);
-      else if (p.dtype == 1) stt = encode_float(((const double*)p.x)[ee], fixed, p.fexp, M, ex);
-      else stt = encode_int(((const int64_t*)p.x)[ee], fixed, p.fexp, M, ex);
+      int ex = 0;
+      const int stt = encode_elem(p.src.x, p.src.dtype, p.src.exp_mode, p.src.fexp, ee, M, ex);
       p.M[e] = M;
-      p.exp[e] = ex;
-      if (p.status) p.status[e] = stt;
+      p.dst.exp[e] = ex;
+      if (p.dst.status) p.dst.status[e] = stt;
     }
     wave_lds_fence();
     int nw;
-    if (p.obf == 1) {
-      nw = p.r_words;
-      const uint32_t* rg = p.r + ee * p.r_stride;
+    if (p.rnd.obf == 1) {
+      nw = p.rnd.r_words;
+      const uint32_t* rg = p.rnd.r + ee * p.rnd.r_stride;
       for (int w = tig; w < nw; w += TPI) slot[w] = rg[w];
     } else {
-      nw = p.rng_words;
-      const unsigned long long g = p.index_base + (unsigned long long)ee;
+      nw = p.rnd.r_words;
+      const unsigned long long g = p.rnd.index_base + (unsigned long long)ee;
       for (int b = tig; b * 16 < nw; b += TPI) {
         uint32_t blk[16];
-        chacha20_block(p.rng_key, (uint32_t)b, (uint32_t)g, (uint32_t)(g >> 32), 0x66786169u, blk);
+        obf_stream_block(p.rnd.rng_key, b, g, blk);
 #pragma unroll
         for (int w = 0; w < 16; ++w)
           if (b * 16 + w < nw) slot[b * 16 + w] = blk[w];
@@ -342,7 +331,7 @@ __global__ __launch_bounds__(BLOCK) void k_pe4_fin(Pe4Params p) {
     normalize<TPI>(P, t, lane, tig);
     cond_sub<TPI>(t, m2, lane, tig);
     cond_sub<TPI>(t, m2, lane, tig);
-    emit_words<TPI>(slot, t, p.ct + ee * p.ct_words, p.ct_words, valid, tig);
+    emit_words<TPI>(slot, t, p.dst.ct + ee * p.dst.ct_words, p.dst.ct_words, valid, tig);
   }
 }
 

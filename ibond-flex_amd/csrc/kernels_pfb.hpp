@@ -50,10 +50,8 @@ struct PfbParams {
   const PfbConst* c;
   long long n;
   const uint32_t* digits;  // [K][n]
-  const void* x;
-  int dtype, exp_mode, fexp;
-  int32_t* exp;
-  int32_t* status;
+  EncPlain src;
+  EncOut dst;              // exp and status (ct: the finish kernels')
   uint32_t* xw;            // [2 PFB_SP][n]: canonical pair limbs for k_pe_fin
 };
 
@@ -244,14 +242,11 @@ __global__ __launch_bounds__(BLOCK, 2) void k_pfb(PfbParams p) {
     const long long ii = valid ? inst : p.n - 1;
     const uint32_t* dg = p.digits + ii;
     int64_t M = 0;
-    int e = 0, st;
-    const bool fixed = p.exp_mode != 0;
-    if (p.dtype == 0) st = encode_float((double)((const float*)p.x)[ii], fixed, p.fexp, M, e);
-    else if (p.dtype == 1) st = encode_float(((const double*)p.x)[ii], fixed, p.fexp, M, e);
-    else st = encode_int(((const int64_t*)p.x)[ii], fixed, p.fexp, M, e);
+    int e = 0;
+    const int st = encode_elem(p.src.x, p.src.dtype, p.src.exp_mode, p.src.fexp, ii, M, e);
     if (valid && tig == 0) {
-      p.exp[ii] = e;
-      if (p.status) p.status[ii] = st;
+      p.dst.exp[ii] = e;
+      if (p.dst.status) p.dst.status[ii] = st;
     }
     // c0 = 1 + n M: the pair (1, M mod n) (M < 0: n - |M|)
     uint32_t A[LL], B[LL];

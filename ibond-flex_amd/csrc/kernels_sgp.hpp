@@ -48,10 +48,8 @@ struct SgpParams {
   int K, W;
   const uint32_t* digits;  // [gridDim.y][K][n]
   uint32_t* out;           // [gridDim.y][2 S][n]: the pair [A: S][B: S], A < 2m, B < 4m
-  const void* x;
-  int dtype, exp_mode, fexp;
-  int32_t* exp;            // written by half 0
-  int32_t* status;
+  EncPlain src;
+  EncOut dst;              // exp and status, written by half 0 (ct: the finish kernels')
   GuardArgs g;             // test build (guard.hpp): rows = K 2^W, digits = halves K n, out = halves 2 S n
 };
 
@@ -205,14 +203,11 @@ __global__ __launch_bounds__(LANE_BLOCK, 2) void k_sgp(SgpParams p) {
     const bool valid = e < p.n;
     const long long ee = valid ? e : p.n - 1;
     int64_t M = 0;
-    int ex = 0, stt;
-    const bool fixed = p.exp_mode != 0;
-    if (p.dtype == 0) stt = encode_float((double)((const float*)p.x)[ee], fixed, p.fexp, M, ex);
-    else if (p.dtype == 1) stt = encode_float(((const double*)p.x)[ee], fixed, p.fexp, M, ex);
-    else stt = encode_int(((const int64_t*)p.x)[ee], fixed, p.fexp, M, ex);
+    int ex = 0;
+    const int stt = encode_elem(p.src.x, p.src.dtype, p.src.exp_mode, p.src.fexp, ee, M, ex);
     if (half == 0 && valid && !odd) {
-      p.exp[e] = ex;
-      if (p.status) p.status[e] = stt;
+      p.dst.exp[e] = ex;
+      if (p.dst.status) p.dst.status[e] = stt;
     }
     // the start: c0 C = (C_A, C_B + gamma C_A); gamma C_A = sum_c nmc_c |M|_c (16-bit chunks, < 2^18 m), negative
     // M: 2^20 m - that sum

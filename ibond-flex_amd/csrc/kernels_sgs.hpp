@@ -63,8 +63,7 @@ struct SgsFinParams {
   uint32_t* out;           // in: k_sgs's pairs; out: A < m, B < m (k_sgp_w's / k_pe_fin's input)
   const uint4* bsum;
   const uint32_t* bcc;
-  const void* x;
-  int dtype, exp_mode, fexp;
+  EncPlain src;
   int32_t* exp;            // written by half 0
   int32_t* status;
   int dbg;                 // test-build debugging: 3 = write the b sum's words over the pair rows and stop, 4 = the pair times c_A
@@ -329,11 +328,8 @@ __global__ __launch_bounds__(LANE_BLOCK, 2) void k_sgs_bfin(SgsFinParams p) {
     const bool valid = e < p.n;
     const long long ee = valid ? e : p.n - 1;
     int64_t M = 0;
-    int ex = 0, stt;
-    const bool fixed = p.exp_mode != 0;
-    if (p.dtype == 0) stt = encode_float((double)((const float*)p.x)[ee], fixed, p.fexp, M, ex);
-    else if (p.dtype == 1) stt = encode_float(((const double*)p.x)[ee], fixed, p.fexp, M, ex);
-    else stt = encode_int(((const int64_t*)p.x)[ee], fixed, p.fexp, M, ex);
+    int ex = 0;
+    const int stt = encode_elem(p.src.x, p.src.dtype, p.src.exp_mode, p.src.fexp, ee, M, ex);
     if (half == 0 && valid && !odd) {
       p.exp[e] = ex;
       if (p.status) p.status[e] = stt;

@@ -42,7 +42,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_encrypt", "pai_add", "pai_decrypt", "pai_encrypt_dev", "pai_add_dev", "pai_decrypt_dev",
             "pai_mul", "pai_mul_dev", "pai_matmul", "pai_matmul_dev", "pai_add_plain", "pai_add_plain_dev",
             "pai_segment_add", "pai_segment_add_dev", "pai_comm_unique_id", "pai_comm_create", "pai_comm_destroy",
-            "pai_allgather_dev", "pai_allgather_shards_dev", "pai_release_table_cache")
+            "pai_allgather_dev", "pai_allgather_shards_dev", "pai_release_table_cache", "pai_debug_encrypt_route")
 PAI_COMM_ID_BYTES = 128
 
 _lib = None
@@ -108,6 +108,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_comm_destroy.restype = None
         lib.pai_allgather_dev.argtypes = [P, P, S, P, P]
         lib.pai_allgather_shards_dev.argtypes = [P, P, P, S, I, P, P, P]
+        lib.pai_debug_encrypt_route.argtypes = [P, I, ctypes.c_longlong, I, P, P]
         lib.pai_release_table_cache.argtypes = []
         lib.pai_release_table_cache.restype = None
         for name in EXPORTED:

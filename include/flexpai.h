@@ -128,7 +128,7 @@ typedef struct pai_comm pai_comm;
                                     2049..4096 bits and its encryption above the rows (more than PAI_OPT_ROWS_MAX and
                                     more than PAI_OPT_CRT4_MIN elements, explicit r or device RNG without resident
                                     fixed-base tables) runs the split-pair CRT (kernels_crt4.hpp). A key holder's
-                                    bit 2 stays 0                                                              */
+                                    bit 2 stays 0. The whole order: csrc/encrypt_route.hpp                     */
 #define PAI_OPT_PUBLIC_FB 10     /* 1 (default): PAI_OBF_RNG encryption WITHOUT the private key (2048-bit n) samples
                                   * r^n through the public fixed bases (kernels_pfb.hpp) once the break-even count
                                   * is reached (pai_ctx_public_fb_policy); get: 1 when the path is enabled and not
@@ -150,11 +150,13 @@ typedef struct pai_comm pai_comm;
                                   * each residue on a 16-lane row (kernels_crtw.hpp: the key holder's CRT encryption
                                   * k_crt_w and decryption k_dec_w, a public-key-only party's encryption k_pe_w; the
                                   * latency of protocol-sized calls) instead of one lane / lane pair each; 0
-                                  * disables. Same bits either way                                               */
+                                  * disables. Same bits either way. Where the rows stand in the order of encrypt
+                                  * paths: csrc/encrypt_route.hpp                                                */
 #define PAI_OPT_CRT4_MIN 15      /* a 2049..4096-bit key holder's calls of at most this many elements (default 128, one
                                   * block of lane pairs) that the rows do not take stay on the public-key kernel
                                   * instead of the split-pair CRT (kernels_crt4.hpp); 0: every such call runs the CRT.
-                                  * Whether a lower floor would be faster has not been measured. Same bits either way */
+                                  * Whether a lower floor would be faster has not been measured. Same bits either way
+                                  * (the order of encrypt paths: csrc/encrypt_route.hpp)                         */
 #define PAI_OPT_MATMUL_FUSED 16  /* 1 (default): pai_matmul[_dev] runs the fused windowed multi-exponentiation
                                   * (kernels_mm.hpp: k_mm_sign, k_mm_tab, k_mm_acc, then the k_add tree over the
                                   * ceil(K / 16) chunk partials) for the calls it was measured faster on: d >= 16 and
@@ -324,6 +326,37 @@ int pai_allgather_dev(pai_comm* comm, const void* d_send, size_t bytes_per_rank,
  * launch: d_ct_all [world * n_per_rank][ct_words], d_exp_all [world * n_per_rank]. */
 int pai_allgather_shards_dev(pai_comm* comm, const uint32_t* d_ct, const int32_t* d_exp, size_t n_per_rank,
                              int ct_words, uint32_t* d_ct_all, int32_t* d_exp_all, void* stream);
+
+/* Debugging. Which kernels pai_encrypt[_dev] runs a call on is decided by one pure function of the facts below
+ * (csrc/encrypt_route.hpp, which documents the order); this hook evaluates it and needs neither a context nor a
+ * device. The library's other debugging hooks (pai_debug_fb_w, pai_debug_engine) are test interfaces and are not
+ * declared here. */
+typedef struct pai_route_facts {
+  int has_priv;                       /* the private key is set */
+  int crt_enabled, fb_enabled, pfb_enabled; /* PAI_OPT_CRT_ENCRYPT, PAI_OPT_FIXED_BASE, PAI_OPT_PUBLIC_FB */
+  int crt_ok, crt_sa;                 /* 1024/2048-bit key holder: lane CRT constants, limbs of a prime (19 / 37) */
+  int fbg_ok, rows_sa, crt4_ok;       /* 2049..4096-bit key holder: sampler constants, row limbs (74), k_crt4_* */
+  int pe_ok, pe1_ok, pe4_ok, pew_ok;  /* public-key chains: k_pe_*, k_pe1_*, k_pe4_*, the k_pe_w op list */
+  int pfb_supported;                  /* the public fixed-base kernels take this n */
+  int ct_words;
+  int rows_r_max;                     /* most words of r the 4096-bit rows stage */
+  long long crtw_max, crt4_min;       /* PAI_OPT_ROWS_MAX, PAI_OPT_CRT4_MIN */
+} pai_route_facts;
+#define PAI_SAMPLER_NONE 0
+#define PAI_SAMPLER_KEY 1      /* the key holder's fixed-base tables (pai_ctx_fixed_base_policy counts the call) */
+#define PAI_SAMPLER_PUBLIC 2   /* the public fixed-base tables (pai_ctx_public_fb_policy counts the call) */
+#define PAI_CHAIN_ENCRYPT 0    /* k_encrypt */
+#define PAI_CHAIN_CRT_ROWS 1   /* k_crt_w, 1024/2048-bit key holder */
+#define PAI_CHAIN_CRT_ROWS4 2  /* k_crt_w<74, 148>, 2049..4096-bit key holder */
+#define PAI_CHAIN_CRT_LANE 3   /* k_crt_a, k_crt_b_pair */
+#define PAI_CHAIN_CRT4 4       /* k_crt4_* */
+#define PAI_CHAIN_PE_ROWS 5    /* k_pe_w */
+#define PAI_CHAIN_PE 6         /* k_pe_* */
+#define PAI_CHAIN_PE1 7        /* k_pe1_* */
+#define PAI_CHAIN_PE4 8        /* k_pe4_* */
+/* sampler: the tables the call is eligible for (used once wanted and built); chain: the per-element kernels otherwise */
+int pai_debug_encrypt_route(const pai_route_facts* facts, int obf_mode, long long n, int r_words, int* sampler,
+                            int* chain);
 
 #ifdef __cplusplus
 }
