@@ -95,14 +95,56 @@ def next_prime(x: int) -> int:
     return c
 
 
-def getprimeover(n: int, seed=None) -> int:          # gmpy_math.py:77-87
+def prime_start(n: int, seed=None) -> int:
+    """getprimeover's draw (gmpy_math.py:78-85): the number the search starts above."""
     if not seed:
         r = random.SystemRandom().getrandbits(n)
     else:
         random.seed(seed)
         r = random.getrandbits(n)
-    r |= 1 << (n - 1)
-    return next_prime(r)
+    return r | 1 << (n - 1)
+
+
+# Prime sizes whose search goes to the GPU by default (csrc/kernels_prime.hpp k_mr_w): those the device path was
+# measured at under half the host's median time on (DESIGN.md §3 "Key generation"). $FLEXPAI_KEYGEN_GPU=0 keeps
+# every search on the host.
+DEVICE_PRIME_BITS = (256, 512, 1024, 2048)
+_device_state = None          # None: not looked yet; True / False: a GPU and the library are there
+
+
+def keygen_on_device(bits: int) -> bool:
+    """True when next_primes(starts, bits) searches on the GPU: the library is loaded, a GPU is visible, the size is
+    one the kernel is built for and $FLEXPAI_KEYGEN_GPU is not 0. Otherwise the host search runs, silently."""
+    global _device_state
+    import os
+    if os.environ.get("FLEXPAI_KEYGEN_GPU", "1") == "0" or bits not in DEVICE_PRIME_BITS:
+        return False
+    if _device_state is None:
+        try:
+            from . import _native
+            _device_state = _native.device_count() > 0
+        except Exception:   # noqa: BLE001 - no library, no runtime: the host path
+            _device_state = False
+    return _device_state
+
+
+def next_primes(starts, bits: int):
+    """next_prime of every start (each with bit `bits - 1` set): one batch on the GPU where keygen_on_device(bits),
+    else -- and for a start the device hands back, whose window would pass 2^bits -- the host search."""
+    starts = list(starts)
+    if not keygen_on_device(bits):
+        return [next_prime(s) for s in starts]
+    from . import _native
+    primes, _ = _native.next_prime_batch(starts, bits)
+    for i, p in enumerate(primes):
+        if p is None:
+            _native.count_host_fallback()
+            primes[i] = next_prime(starts[i])
+    return primes
+
+
+def getprimeover(n: int, seed=None) -> int:          # gmpy_math.py:77-87
+    return next_primes([prime_start(n, seed)], n)[0]
 
 
 def isqrt(n: int) -> int:                            # gmpy_math.py:90-93

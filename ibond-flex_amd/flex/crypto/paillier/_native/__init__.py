@@ -42,7 +42,8 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_encrypt", "pai_add", "pai_decrypt", "pai_encrypt_dev", "pai_add_dev", "pai_decrypt_dev",
             "pai_mul", "pai_mul_dev", "pai_matmul", "pai_matmul_dev", "pai_add_plain", "pai_add_plain_dev",
             "pai_segment_add", "pai_segment_add_dev", "pai_comm_unique_id", "pai_comm_create", "pai_comm_destroy",
-            "pai_allgather_dev", "pai_allgather_shards_dev", "pai_release_table_cache", "pai_debug_encrypt_route")
+            "pai_allgather_dev", "pai_allgather_shards_dev", "pai_release_table_cache", "pai_debug_encrypt_route",
+            "pai_next_prime", "pai_prime_last_times", "pai_prime_test", "pai_debug_prime_sieve")
 PAI_COMM_ID_BYTES = 128
 
 _lib = None
@@ -110,6 +111,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_allgather_shards_dev.argtypes = [P, P, P, S, I, P, P, P]
         lib.pai_debug_encrypt_route.argtypes = [P, I, ctypes.c_longlong, I, P, P]
         lib.pai_release_table_cache.argtypes = []
+        lib.pai_next_prime.argtypes = [I, I, P, S, S, ctypes.c_uint32, P, P]
+        lib.pai_prime_last_times.argtypes = [P, P, P, P]
+        lib.pai_prime_test.argtypes = [I, I, P, S, S, P, S, P]
+        lib.pai_debug_prime_sieve.argtypes = [I, P, S, ctypes.c_uint32, P, S, P]
         lib.pai_release_table_cache.restype = None
         for name in EXPORTED:
             if name not in ("pai_ctx_destroy", "pai_last_error", "pai_comm_destroy", "pai_release_table_cache"):
@@ -687,3 +692,79 @@ def ints_to_words(vals, nwords: int) -> np.ndarray:
         nbytes = nwords * 4
         buf = b"".join(int(v).to_bytes(nbytes, "little") for v in vals)
     return np.frombuffer(buf, dtype="<u4").reshape(len(vals), nwords).copy()
+
+
+# ---------------------------------------------------------------- key generation: the prime search on the device
+PRIME_BITS = (256, 512, 1024, 2048)      # the sizes k_mr_w is built for (csrc/kernels_prime.hpp)
+PAI_PRIME_OVERFLOW = 1
+_prime_stats = collections.Counter()
+
+
+def prime_stats() -> dict:
+    """Which path the prime searches of this process took: device searches (starts answered by pai_next_prime), the
+    windows those used, host fallbacks (starts an eligible call handed back to _bigint.next_prime)."""
+    return {k: _prime_stats[k] for k in ("device_searches", "windows", "host_fallbacks")}
+
+
+def count_host_fallback(n: int = 1) -> None:
+    _prime_stats["host_fallbacks"] += n
+
+
+def prime_sieve(x: int, bits: int, window: int = 0):
+    """pai_debug_prime_sieve: the offsets the device search would test in (x, x + window], or None when the window
+    crosses 2^bits. Host only."""
+    lib = load_library()
+    nbytes = bits // 8
+    cap = (window or 4 * bits) // 2 + 1
+    out = np.zeros(cap, dtype=np.uint32)
+    cnt = ctypes.c_size_t()
+    rc = lib.pai_debug_prime_sieve(bits, int_to_le(x, nbytes), nbytes, window, _ptr(out), cap, ctypes.byref(cnt))
+    if rc == PAI_PRIME_OVERFLOW:
+        return None
+    _check(rc, lib)
+    return [int(v) for v in out[:cnt.value]]
+
+
+def prime_test(cands, bits: int, bases, device: int = 0) -> np.ndarray:
+    """pai_prime_test: the [len(cands), len(bases)] uint8 matrix of strong-probable-prime verdicts (k_mr_w)."""
+    global _runtime_started
+    lib = load_library()
+    cands = list(cands)
+    nbytes = bits // 8
+    buf = b"".join(int_to_le(c, nbytes) for c in cands)
+    b = np.ascontiguousarray(bases, dtype=np.uint32)
+    out = np.zeros((len(cands), b.size), dtype=np.uint8)
+    _runtime_started = True
+    _check(lib.pai_prime_test(device, bits, buf, nbytes, len(cands), _ptr(b), b.size, _ptr(out)), lib)
+    return out
+
+
+def next_prime_batch(starts, bits: int, window: int = 0, device: int = 0):
+    """pai_next_prime: for every start (bit `bits - 1` set) the smallest prime above it, as _bigint.next_prime finds
+    it, searched on the device in one batch. Returns (primes, passes): primes[i] is None, and passes[i] is -1, where
+    the start's window would cross 2^bits (the caller searches that one on the host)."""
+    global _runtime_started
+    lib = load_library()
+    starts = list(starts)
+    nbytes = bits // 8
+    buf = b"".join(int_to_le(s, nbytes) for s in starts)
+    out = ctypes.create_string_buffer(nbytes * len(starts))
+    passes = np.zeros(len(starts), dtype=np.int32)
+    _runtime_started = True
+    rc = lib.pai_next_prime(device, bits, buf, nbytes, len(starts), window, out, _ptr(passes))
+    if rc != PAI_PRIME_OVERFLOW:
+        _check(rc, lib)
+    raw = out.raw
+    primes = [None if passes[i] < 0 else int.from_bytes(raw[i * nbytes:(i + 1) * nbytes], "little")
+              for i in range(len(starts))]
+    _prime_stats["device_searches"] += sum(p is not None for p in primes)
+    _prime_stats["windows"] += int(passes[passes > 0].sum())
+    return primes, [int(v) for v in passes]
+
+
+def prime_last_times():
+    """(pass-1 ms, pass-2 ms, pass-1 launches, pass-2 launches) of this thread's last next_prime_batch."""
+    a, b = ctypes.c_float(), ctypes.c_float()
+    c, d = ctypes.c_int(), ctypes.c_int()
+    _check(load_library().pai_prime_last_times(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+    return a.value, b.value, c.value, d.value

@@ -5,8 +5,9 @@
 #  CONDITIONS OF ANY KIND, either express or implied.
 """Paillier keys — same classes, slots and behaviour as flex/crypto/paillier/keypair.py:20-127.
 
-Key generation is host-side and one-time; the seeded path reproduces the
-reference's keys (random.seed + getrandbits + next_prime), checked against golden vectors."""
+Key generation: the seeded path reproduces the reference's keys (random.seed +
+getrandbits + next_prime), checked against golden vectors. The prime search runs on the GPU where one is
+visible (_bigint.next_primes -> pai_next_prime), on the host otherwise: the same primes either way."""
 from . import _bigint as gmpy_math
 
 
@@ -68,16 +69,30 @@ class PaillierPrivateKey(object):
 
 
 def generate_paillier_keypair(n_length: int = 1024, seed: int = None):
-    """keypair.py:93-127: returns (PaillierPublicKey, PaillierPrivateKey)."""
+    """keypair.py:93-127: returns (PaillierPublicKey, PaillierPrivateKey).
+
+    Where the prime search runs on the GPU (_bigint.keygen_on_device), p's and the first q's searches of an iteration
+    go there as one batch: both starts are drawn first, p's then q's, which leaves the same primes and the same state
+    of the random module as searching in between, since the search draws nothing."""
     p = q = n = None
     n_len = 0
     i = 1
+    batch = gmpy_math.keygen_on_device(n_length // 2)
     while n_len != n_length:
-        if seed:
-            p = gmpy_math.getprimeover(n_length // 2, seed)
+        if batch:
+            sp = gmpy_math.prime_start(n_length // 2, seed)
+            if seed:
+                sq = gmpy_math.prime_start(n_length // 2, seed + i)
+                i += 1
+            else:
+                sq = gmpy_math.prime_start(n_length // 2)
+            p, q = gmpy_math.next_primes([sp, sq], n_length // 2)
         else:
-            p = gmpy_math.getprimeover(n_length // 2)
-        q = p
+            if seed:
+                p = gmpy_math.getprimeover(n_length // 2, seed)
+            else:
+                p = gmpy_math.getprimeover(n_length // 2)
+            q = p
         while q == p:
             if seed:
                 q = gmpy_math.getprimeover(n_length // 2, seed + i)

@@ -24,6 +24,14 @@
  *   pai_matmul[_dev]      <- ndarray.dot of encrypted by plain (he_otp_lr_ft1/train.py:160,
  *                            he_otp_lr_ft2/train.py:188): per output sum_k c_ik (x) x_kj, i.e. __mul__ then
  *                            __add__ (encrypted_number.py:65-69, 86-113, 166-185)
+ *   pai_next_prime        <- gmpy2.next_prime(r) of getprimeover    flex/crypto/gmpy_math.py:77-87, the two prime
+ *                            searches of generate_paillier_keypair  flex/crypto/paillier/keypair.py:93-127 (one batch):
+ *                            a sieve by the odd primes below 2000 on the host, then Miller-Rabin on 16-lane rows
+ *                            (kernels_prime.hpp k_mr_w: base 3 over every survivor of a window, the other 39 bases
+ *                            over the smallest one left). Same primes as the package's host search
+ *                            (_bigint.next_prime), which reproduces the reference's seeded keys
+ *   pai_prime_test        <- (no reference counterpart) the strong-probable-prime verdicts of that kernel for
+ *                            given candidates and bases; pai_debug_prime_sieve: the sieve alone, on the host
  *   pai_comm_* / pai_allgather_*  <- (no reference counterpart: the reference encrypts on one host's CPU
  *                            pool, encryptor.py:71-97) reassembly of ciphertext shards encrypted on
  *                            several GPUs, one RCCL all-gather over xGMI
@@ -326,6 +334,36 @@ int pai_allgather_dev(pai_comm* comm, const void* d_send, size_t bytes_per_rank,
  * launch: d_ct_all [world * n_per_rank][ct_words], d_exp_all [world * n_per_rank]. */
 int pai_allgather_shards_dev(pai_comm* comm, const uint32_t* d_ct, const int32_t* d_exp, size_t n_per_rank,
                              int ct_words, uint32_t* d_ct_all, int32_t* d_exp_all, void* stream);
+
+/* Key generation: the prime search on the device (csrc/engine_prime.hip, kernels_prime.hpp). These entry points take
+ * no context -- a key does not exist yet -- but a device number; they are synchronous and keep one stream and one
+ * scratch buffer per device for themselves. `bits` is the size of the primes: 256, 512, 1024 or 2048 (the halves of
+ * 512- to 4096-bit keys); anything else is PAI_ERR_ARG. Integers are little-endian bytes.
+ *
+ * pai_next_prime: for each of the nstarts starts x (start_bytes each, bit `bits - 1` set, as getprimeover's
+ * r | 1 << (bits - 1)) the smallest c > x that is divisible by no odd prime below 2000 and is a strong probable
+ * prime to each of the first 40 odd primes -- gmpy_math.py:77-87's next_prime(r) as this package restates it.
+ * The search goes window by window: the sieve's survivors in (x, x + window] meet base 3 in one launch for all
+ * starts (pass 1), then each start's smallest survivor meets the other 39 bases in one launch (pass 2), the next
+ * survivor if it fails, the next window when none is left. window = 0: the default, 4 * bits (5.8 mean prime gaps:
+ * a window holds no prime with probability about e^-5.8 = 0.3 %). out_le: nstarts primes of start_bytes each;
+ * passes_out (nullable): the windows used per start. A start whose window would cross 2^bits is not searched: its
+ * output is zero, its passes_out is -1 and the call returns PAI_PRIME_OVERFLOW (the other starts are complete); the
+ * caller searches that one on the host. */
+#define PAI_PRIME_OVERFLOW 1
+int pai_next_prime(int device, int bits, const uint8_t* starts_le, size_t start_bytes, size_t nstarts, uint32_t window,
+                   uint8_t* out_le, int32_t* passes_out);
+/* Kernel time (ms) and launches of pass 1 and of pass 2 in this thread's last pai_next_prime. */
+int pai_prime_last_times(float* pass1_ms, float* pass2_ms, int* pass1_launches, int* pass2_launches);
+/* verdict_u8[i * nbases + j] = 1 when candidate i (odd, bit `bits - 1` set) is a strong probable prime to base j:
+ * with n - 1 = 2^s d, a^d is 1 or n - 1, or a^(2^r d) is n - 1 for some 0 < r < s. No sieving. */
+int pai_prime_test(int device, int bits, const uint8_t* cands_le, size_t cand_bytes, size_t ncand,
+                   const uint32_t* bases_u32, size_t nbases, uint8_t* verdict_u8);
+/* The sieve alone, on the host (no device): the offsets 0 < off <= window (0: the default) with x + off odd and
+ * divisible by no odd prime below 2000, ascending. *count is their number; the first max_out are written.
+ * PAI_PRIME_OVERFLOW when x + window reaches 2^bits. */
+int pai_debug_prime_sieve(int bits, const uint8_t* x_le, size_t bytes, uint32_t window, uint32_t* offsets_out,
+                          size_t max_out, size_t* count);
 
 /* Debugging. Which kernels pai_encrypt[_dev] runs a call on is decided by one pure function of the facts below
  * (csrc/encrypt_route.hpp, which documents the order); this hook evaluates it and needs neither a context nor a
