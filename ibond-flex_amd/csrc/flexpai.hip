@@ -53,6 +53,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_grp.hpp"
 #include "engine_mul.hpp"
 #include "engine_mm.hpp"
+#include "engine_obf.hpp"
 #include "engine_crtw.hpp"
 #include "engine_pe1.hpp"
 #include "engine_pe4.hpp"
@@ -222,6 +223,11 @@ struct pai_ctx {
   size_t seg_bytes = 0;
   void* d_plain = nullptr;      // ciphertext + plaintext: the two k_add operands and their exponents
   size_t plain_bytes = 0;
+  // re-randomisation (pai_obfuscate_dev): the zero plaintexts, scratch exponents and statuses of the encryption that
+  // yields r^n, and, for in-place calls, r^n of one slice of obf_chunk elements (PAI_OPT_OBF_CHUNK)
+  void* d_obf = nullptr;
+  size_t obf_bytes = 0;
+  int obf_chunk = 262144;
   // fused matrix product (kernels_mm.hpp): PAI_OPT_MATMUL_FUSED / PAI_OPT_MATMUL_PATH
   bool mm_fused = true;
   int mm_path = 0;              // last pai_matmul[_dev] call: 0 none yet, 1 term path, 2 fused
@@ -256,6 +262,7 @@ struct pai_ctx {
   size_t hostio_bytes = 0;
   hipStream_t s_comp = nullptr, s_copy = nullptr;
   std::vector<hipEvent_t> hev, pev;   // per chunk: kernels done / staging copy done
+  std::vector<hipEvent_t> oev;        // pai_obfuscate, whose hev mark the uploads: per chunk, kernels done
   void* h_pin[2] = {nullptr, nullptr};  // pinned staging slots (PCIe at full rate, truly asynchronous)
   size_t pin_bytes = 0;
   // thread safety (CtxLock below): one call at a time per context, and the device work of successive calls
@@ -305,6 +312,7 @@ pai_ctx::~pai_ctx() {
       if (e) (void)hipEventDestroy(e);
   for (auto& e : hev) (void)hipEventDestroy(e);
   for (auto& e : pev) (void)hipEventDestroy(e);
+  for (auto& e : oev) (void)hipEventDestroy(e);
   for (void* p : h_pin)
     if (p) (void)hipHostFree(p);
   if (s_comp) (void)hipStreamDestroy(s_comp);
@@ -330,6 +338,7 @@ pai_ctx::~pai_ctx() {
     delete inv_async;
   }
   if (d_plain) (void)hipFree(d_plain);
+  if (d_obf) (void)hipFree(d_obf);
   if (d_seg) (void)hipFree(d_seg);
   if (d_addplan) (void)hipFree(d_addplan);
 }
@@ -2185,6 +2194,10 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       c->crt4_min = value;
       return 0;
     case PAI_OPT_MATMUL_FUSED: c->mm_fused = value != 0; return 0;
+    case PAI_OPT_OBF_CHUNK:
+      if (value < 64) return fail(PAI_ERR_ARG, "PAI_OPT_OBF_CHUNK must be >= 64");
+      c->obf_chunk = value;
+      return 0;
     case PAI_OPT_STAGE_TIMING: c->timing = value != 0; stage_reset(c); return 0;
     case PAI_OPT_LANE_DECRYPT: c->dec_lane_enabled = value != 0; return 0;
     case PAI_OPT_FIXED_BASE: c->fb_enabled = value != 0; return 0;
@@ -2219,6 +2232,7 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_CRT4_MIN: *value = (int)std::min<long long>(c->crt4_min, INT32_MAX); return 0;
     case PAI_OPT_MATMUL_FUSED: *value = c->mm_fused ? 1 : 0; return 0;
     case PAI_OPT_MATMUL_PATH: *value = c->mm_path; return 0;
+    case PAI_OPT_OBF_CHUNK: *value = c->obf_chunk; return 0;
     case PAI_OPT_STAGE_TIMING: *value = c->timing ? 1 : 0; return 0;
     case PAI_OPT_LANE_DECRYPT: *value = (c->dec_lane_ok && c->dec_lane_enabled) ? 1 : 0; return 0;
     // 1 when device-RNG encryption will use the fixed bases (tables resident, or not yet tried)
@@ -3234,6 +3248,10 @@ static int launch_crt4(pai_ctx* c, const EncParams& e, hipStream_t st) {
   return 0;
 }
 
+static int encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mode, int32_t fixed_exp, int obf_mode,
+                       const uint32_t* d_r_words, size_t r_stride_words, size_t r_words, const uint8_t* rng_key32,
+                       uint64_t index_base, uint32_t* d_ct, int32_t* d_exp, int32_t* d_status, hipStream_t st);
+
 int pai_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mode, int32_t fixed_exp, int obf_mode,
                     const uint32_t* d_r_words, size_t r_stride_words, size_t r_words, const uint8_t* rng_key32,
                     uint64_t index_base, uint32_t* d_ct, int32_t* d_exp, int32_t* d_status, void* stream) {
@@ -3245,6 +3263,15 @@ int pai_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mo
     return fail(PAI_ERR_ARG, "pai_encrypt_dev: r must be given with 0 < r_words <= ct_words");
   if (obf_mode == PAI_OBF_RNG && !rng_key32) return fail(PAI_ERR_ARG, "pai_encrypt_dev: rng key required");
   if (obf_mode < 0 || obf_mode > 2) return fail(PAI_ERR_ARG, "pai_encrypt_dev: bad obf_mode");
+  return encrypt_dev(c, dtype, d_x, N, exp_mode, fixed_exp, obf_mode, d_r_words, r_stride_words, r_words, rng_key32,
+                     index_base, d_ct, d_exp, d_status, (hipStream_t)stream);
+}
+
+// pai_encrypt_dev below its argument checks (the caller holds the context's lock): the route, the samplers' break-even
+// counters and tables, the launches. pai_obfuscate_dev runs it on zeros for its r^n.
+static int encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mode, int32_t fixed_exp, int obf_mode,
+                       const uint32_t* d_r_words, size_t r_stride_words, size_t r_words, const uint8_t* rng_key32,
+                       uint64_t index_base, uint32_t* d_ct, int32_t* d_exp, int32_t* d_status, hipStream_t st) {
   HIPCHK(hipSetDevice(c->device));
   stage_reset(c);
   EncParams p{};
@@ -3271,7 +3298,6 @@ int pai_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mo
   p.prog = c->d_prog;
   p.nprog = c->nprog;
   p.ct_words = c->ct_words;
-  hipStream_t st = (hipStream_t)stream;
   const int r_eff = enc_r_words(p);
   const EncryptRoute rt = encrypt_route(route_facts(c), obf_mode, p.n, r_eff);
   // the impure steps: a call counts towards a sampler's break-even, and builds its tables, only for the sampler named
@@ -3306,6 +3332,98 @@ int pai_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mo
     case 8: return launch_encrypt<8>(c, p, st);
   }
   return fail(PAI_ERR_KEY, "unsupported group size");
+}
+
+// ------------------------------------------------------------------ re-randomisation (kernels_obf.hpp)
+// One sampler decision and one stage-timing record for every slice or chunk of a pai_obfuscate[_dev] call, as HostCall
+// keeps them for pai_encrypt's chunks: the bits of a call do not depend on how it is cut. Nested (the host-buffer
+// call around its chunks' device calls) the outer scope's decision stands and only the outer scope drops it.
+struct ObfCall {
+  pai_ctx* c;
+  bool own_keep = false, own_fb = false, own_pfb = false;
+  ObfCall(pai_ctx* ctx, int obf_mode, long long N) : c(ctx) {
+    if (!c->stage_keep) {
+      stage_reset(c);
+      c->stage_keep = own_keep = true;
+    }
+    if (obf_mode != PAI_OBF_RNG || c->fb_call || c->pfb_call) return;
+    const int sampler = encrypt_route(route_facts(c), obf_mode, N, rng_stream_words(c)).sampler;
+    if (sampler == PAI_SAMPLER_KEY) {
+      c->fb_call = fb_wanted(c, N) ? 1 : -1;
+      own_fb = true;
+    } else if (sampler == PAI_SAMPLER_PUBLIC) {
+      c->pfb_call = pfb_wanted(c, N) ? 1 : -1;
+      own_pfb = true;
+    }
+  }
+  ~ObfCall() {
+    if (own_keep) c->stage_keep = false;
+    if (own_fb) c->fb_call = 0;
+    if (own_pfb) c->pfb_call = 0;
+  }
+};
+
+// out <- ct s mod n^2 over n elements (out may be ct or s)
+static int launch_obf_mul(pai_ctx* c, const uint32_t* ct, const uint32_t* s, uint32_t* out, long long n, hipStream_t st) {
+  int occ = 1;
+  if (obf_occupancy(c->tpi_e, &occ)) return fail(PAI_ERR_KEY, "unsupported group size");
+  const int gpb = BLOCK / c->tpi_e;
+  const int grid = (int)std::max<long long>(1, std::min<long long>((n + gpb - 1) / gpb, (long long)occ * c->cus));
+  ObfMulParams p{};
+  p.c = ct;
+  p.s = s;
+  p.out = out;
+  p.n = n;
+  p.N = c->d_N;
+  p.R2 = c->d_R2;
+  p.mprime = c->mprime_N;
+  p.ct_words = c->ct_words;
+  HIPCHK(obf_launch(c->tpi_e, p, grid, st));
+  return 0;
+}
+
+// r^n is the encryption of the integer 0 (c0 = 1) by the same route as pai_encrypt_dev takes for these N elements, this
+// obfuscator and this index_base; then one k_obf_mul. Out of place r^n goes straight into d_out; in place the call walks
+// slices of obf_chunk elements through a buffer of its own (not ensure_work's: the encrypt chains reallocate that one
+// for their intermediates while r^n is being produced).
+int pai_obfuscate_dev(pai_ctx* c, const uint32_t* d_ct, size_t N, int obf_mode, const uint32_t* d_r_words,
+                      size_t r_stride_words, size_t r_words, const uint8_t* rng_key32, uint64_t index_base,
+                      uint32_t* d_out, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (N == 0) return 0;
+  if (!d_ct || !d_out) return fail(PAI_ERR_ARG, "pai_obfuscate_dev: bad arguments");
+  if (obf_mode != PAI_OBF_GIVEN && obf_mode != PAI_OBF_RNG)
+    return fail(PAI_ERR_ARG, "pai_obfuscate_dev: obf_mode must be PAI_OBF_GIVEN or PAI_OBF_RNG");
+  if (obf_mode == PAI_OBF_GIVEN && (!d_r_words || r_words == 0 || r_words > (size_t)c->ct_words))
+    return fail(PAI_ERR_ARG, "pai_obfuscate_dev: r must be given with 0 < r_words <= ct_words");
+  if (obf_mode == PAI_OBF_RNG && !rng_key32) return fail(PAI_ERR_ARG, "pai_obfuscate_dev: rng key required");
+  const size_t W = c->ct_words;
+  const bool in_place = d_out == d_ct;
+  if (!in_place && d_out < d_ct + N * W && d_ct < d_out + N * W)
+    return fail(PAI_ERR_ARG, "pai_obfuscate_dev: d_out must be d_ct or not overlap it");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t CH = in_place ? std::min(N, (size_t)c->obf_chunk) : N;
+  const size_t rn_bytes = in_place ? align16(CH * W * 4) : 0, x_bytes = align16(CH * 8), e_bytes = align16(CH * 4);
+  int rc = ensure_buf(&c->d_obf, &c->obf_bytes, rn_bytes + x_bytes + 2 * e_bytes);
+  if (rc) return rc;
+  uint32_t* rn = (uint32_t*)c->d_obf;
+  int64_t* zeros = (int64_t*)((char*)c->d_obf + rn_bytes);
+  int32_t* ex = (int32_t*)((char*)zeros + x_bytes);
+  int32_t* status = (int32_t*)((char*)ex + e_bytes);
+  HIPCHK(hipMemsetAsync(zeros, 0, CH * 8, st));
+  ObfCall oc(c, obf_mode, (long long)N);
+  for (size_t off = 0; off < N; off += CH) {
+    const size_t n = std::min(CH, N - off);
+    uint32_t* s = in_place ? rn : d_out + off * W;
+    if ((rc = encrypt_dev(c, PAI_I64, zeros, n, PAI_EXP_AUTO, 0, obf_mode,
+                          d_r_words ? d_r_words + off * r_stride_words : nullptr, r_stride_words, r_words, rng_key32,
+                          index_base + off, s, ex, status, st)))
+      return rc;
+    if ((rc = launch_obf_mul(c, d_ct + off * W, s, d_out + off * W, (long long)n, st))) return rc;
+  }
+  return 0;
 }
 
 template <int TPI>
@@ -4242,7 +4360,7 @@ static int host_pipe(pai_ctx* c, size_t N, size_t dev_bytes, size_t stage_per_el
   k = std::max(k, (N * stage_per_elem + PIN_SLOT_MAX - 1) / PIN_SLOT_MAX);
   *chunk = (N + k - 1) / k;
   *nch = (int)((N + *chunk - 1) / *chunk);
-  for (auto* v : {&c->hev, &c->pev})
+  for (auto* v : {&c->hev, &c->pev, &c->oev})
     while (v->size() < (size_t)*nch) {
       hipEvent_t e;
       HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -4430,6 +4548,74 @@ int pai_add(pai_ctx* c, const uint32_t* const* cts, const int32_t* const* exps, 
   HIPCHK(hipMemcpyAsync(ct_out, dout, N * W * 4, hipMemcpyDeviceToHost, sc));
   HIPCHK(hipMemcpyAsync(exp_out, dexp, N * 4, hipMemcpyDeviceToHost, sc));
   HIPCHK(hipStreamSynchronize(sc));
+  return 0;
+}
+
+// Inputs cross host-to-device per chunk ahead of the kernels (as in pai_add), every chunk is re-randomised in place on
+// the device, and the outputs drain through the two pinned slots (as in pai_encrypt) once the last upload has left them.
+int pai_obfuscate(pai_ctx* c, const uint32_t* ct, size_t N, int obf_mode, const uint8_t* r_le, size_t r_stride_bytes,
+                  size_t r_bytes, const uint8_t* rng_key32, uint64_t index_base, uint32_t* ct_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  if (N == 0) return 0;
+  if (!ct || !ct_out) return fail(PAI_ERR_ARG, "pai_obfuscate: null buffer");
+  if (obf_mode != PAI_OBF_GIVEN && obf_mode != PAI_OBF_RNG)
+    return fail(PAI_ERR_ARG, "pai_obfuscate: obf_mode must be PAI_OBF_GIVEN or PAI_OBF_RNG");
+  if (obf_mode == PAI_OBF_GIVEN && (!r_le || r_bytes == 0 || r_bytes > (size_t)c->ct_words * 4))
+    return fail(PAI_ERR_ARG, "pai_obfuscate: r must be given with 0 < r_bytes <= 4 ct_words");
+  if (obf_mode == PAI_OBF_RNG && !rng_key32) return fail(PAI_ERR_ARG, "pai_obfuscate: rng key required");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t W = c->ct_words;
+  const size_t r_words = obf_mode == PAI_OBF_GIVEN ? (r_bytes + 3) / 4 : 0;
+  const size_t r_cnt = obf_mode == PAI_OBF_GIVEN ? (r_stride_bytes ? N : 1) : 0;
+  size_t CH;
+  int nch, rc;
+  if ((rc = host_pipe(c, N, carve_bytes({N * W * 4, r_cnt * r_words * 4}), W * 4, &CH, &nch))) return rc;
+  Carve cv{(char*)c->d_hostio};
+  uint32_t* dct = cv.take<uint32_t>(N * W);
+  uint32_t* dr = cv.take<uint32_t>(r_cnt * r_words);
+  hipStream_t sc = c->s_comp, sy = c->s_copy;
+  if (r_cnt) {
+    std::vector<uint32_t> hr(r_cnt * r_words, 0);
+    for (size_t i = 0; i < r_cnt; ++i) std::memcpy(&hr[i * r_words], r_le + i * r_stride_bytes, r_bytes);
+    HIPCHK(hipMemcpyAsync(dr, hr.data(), hr.size() * 4, hipMemcpyHostToDevice, sc));
+    HIPCHK(hipStreamSynchronize(sc));   // hr is released at the end of this scope
+  }
+  const size_t r_stride_words = r_stride_bytes ? r_words : 0;
+  ObfCall oc(c, obf_mode, (long long)N);   // one sampler decision for the call, whatever its chunks
+  for (int i = 0; i < nch; ++i) {
+    const size_t off = (size_t)i * CH, n = std::min(CH, N - off);
+    if (i >= 2) HIPCHK(hipEventSynchronize(c->hev[i - 2]));   // the slot's previous upload is done
+    par_copy(c->h_pin[i & 1], ct + off * W, n * W * 4);
+    HIPCHK(hipMemcpyAsync(dct + off * W, c->h_pin[i & 1], n * W * 4, hipMemcpyHostToDevice, sy));
+    HIPCHK(hipEventRecord(c->hev[i], sy));
+    HIPCHK(hipStreamWaitEvent(sc, c->hev[i], 0));
+    rc = pai_obfuscate_dev(c, dct + off * W, n, obf_mode, r_cnt ? dr + off * r_stride_words : nullptr, r_stride_words,
+                           r_words, rng_key32, index_base + off, dct + off * W, sc);
+    if (rc) {
+      (void)hipStreamSynchronize(sc);
+      (void)hipStreamSynchronize(sy);
+      return rc;
+    }
+    HIPCHK(hipEventRecord(c->oev[i], sc));
+  }
+  HIPCHK(hipEventSynchronize(c->hev[nch - 1]));   // every upload has left the slots: they now carry the outputs
+  auto d2h = [&](int i) -> int {
+    const size_t off = (size_t)i * CH, n = std::min(CH, N - off);
+    HIPCHK(hipStreamWaitEvent(sy, c->oev[i], 0));
+    HIPCHK(hipMemcpyAsync(c->h_pin[i & 1], dct + off * W, n * W * 4, hipMemcpyDeviceToHost, sy));
+    HIPCHK(hipEventRecord(c->pev[i], sy));
+    return 0;
+  };
+  if ((rc = d2h(0))) return rc;
+  for (int i = 0; i < nch; ++i) {
+    if (i + 1 < nch && (rc = d2h(i + 1))) return rc;   // its slot's previous chunk (i - 1) is consumed
+    const size_t off = (size_t)i * CH, n = std::min(CH, N - off);
+    HIPCHK(hipEventSynchronize(c->pev[i]));
+    par_copy(ct_out + off * W, c->h_pin[i & 1], n * W * 4);
+  }
+  HIPCHK(hipStreamSynchronize(sc));
+  HIPCHK(hipStreamSynchronize(sy));
   return 0;
 }
 

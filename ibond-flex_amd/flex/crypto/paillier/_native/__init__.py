@@ -31,6 +31,7 @@ PAI_OPT_FIXED_BASE, PAI_OPT_FB_WINDOW, PAI_OPT_FB_READY, PAI_OPT_FB_PAIR, PAI_OP
 PAI_OPT_SPLIT_SAMPLER, PAI_OPT_ROWS_MAX = 13, 14
 PAI_OPT_CRT4_MIN = 15
 PAI_OPT_MATMUL_FUSED, PAI_OPT_MATMUL_PATH = 16, 17
+PAI_OPT_OBF_CHUNK = 18
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
 PFB_NBASES = 33
 
@@ -43,7 +44,8 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_mul", "pai_mul_dev", "pai_matmul", "pai_matmul_dev", "pai_add_plain", "pai_add_plain_dev",
             "pai_segment_add", "pai_segment_add_dev", "pai_comm_unique_id", "pai_comm_create", "pai_comm_destroy",
             "pai_allgather_dev", "pai_allgather_shards_dev", "pai_release_table_cache", "pai_debug_encrypt_route",
-            "pai_next_prime", "pai_prime_last_times", "pai_prime_test", "pai_debug_prime_sieve")
+            "pai_next_prime", "pai_prime_last_times", "pai_prime_test", "pai_debug_prime_sieve",
+            "pai_obfuscate", "pai_obfuscate_dev")
 PAI_COMM_ID_BYTES = 128
 
 _lib = None
@@ -95,6 +97,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_encrypt_dev.argtypes = [P, I, P, S, I, ctypes.c_int32, I, P, S, S, P, U64, P, P, P, P]
         lib.pai_add_dev.argtypes = [P, P, P, I, S, P, P, P]
         lib.pai_decrypt_dev.argtypes = [P, P, P, S, P, P, P, P, P]
+        lib.pai_obfuscate.argtypes = [P, P, S, I, P, S, S, P, U64, P]
+        lib.pai_obfuscate_dev.argtypes = [P, P, S, I, P, S, S, P, U64, P, P]
         lib.pai_mul.argtypes = [P, P, P, S, I, P, S, P, P, P]
         lib.pai_mul_dev.argtypes = [P, P, P, S, I, P, S, P, P, P, P]
         lib.pai_add_plain.argtypes = [P, P, P, S, I, P, S, P, P, P]
@@ -375,6 +379,15 @@ class Context:
         """The path of this context's last matmul call: 0 = none yet, 1 = term path, 2 = fused."""
         return int(self._get_option(PAI_OPT_MATMUL_PATH))
 
+    @property
+    def obf_chunk(self) -> int:
+        """Elements per slice of an in-place pai_obfuscate_dev (default 262 144)."""
+        return int(self._get_option(PAI_OPT_OBF_CHUNK))
+
+    def set_obf_chunk(self, n: int):
+        """At least 64; same bits for every value."""
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_OBF_CHUNK, int(n)))
+
     def set_crt(self, enabled: bool):
         """Encrypt through the private-key CRT kernels (default when available) or the public-key one.
         The ciphertext bits are identical either way."""
@@ -557,6 +570,34 @@ class Context:
                                     _ptr(r_buf) if r_buf is not None else None, r_stride, r_bytes,
                                     key, index_base, _ptr(ct), _ptr(ex), _ptr(st)))
         return ct, ex, st
+
+    def obfuscate(self, ct: np.ndarray, obf_mode: int = PAI_OBF_RNG, r: Optional[Sequence[int]] = None,
+                  r_scalar: Optional[int] = None, rng_key: Optional[bytes] = None, index_base: int = 0,
+                  out: Optional[np.ndarray] = None) -> np.ndarray:
+        """ct_i * r_i^n mod n^2 over [N, ct_words] words (pai_obfuscate; include/flexpai.h states which r). `out` may
+        be `ct` itself (in place) or another C-contiguous uint32 [N, ct_words] array, else a fresh one. Returns the
+        words."""
+        ct = np.ascontiguousarray(ct, dtype=np.uint32)
+        if ct.ndim != 2 or ct.shape[1] != self.ct_words:
+            raise ValueError(f"ciphertext buffer shape {ct.shape} does not match (N, {self.ct_words})")
+        N = ct.shape[0]
+        if out is None:
+            out = np.empty_like(ct)
+        elif not (out.dtype == np.uint32 and out.shape == ct.shape and out.flags.c_contiguous):
+            raise ValueError("out must be C-contiguous uint32 [N, ct_words]")
+        r_buf, r_stride, r_bytes = None, 0, 0
+        if obf_mode == PAI_OBF_GIVEN:
+            r_bytes = self.ct_words * 4
+            if r_scalar is not None:
+                r_buf = np.frombuffer(int_to_le(r_scalar, r_bytes), dtype=np.uint8).copy()
+            else:
+                r_buf = np.frombuffer(b"".join(int_to_le(v, r_bytes) for v in r), dtype=np.uint8).copy()
+                r_stride = r_bytes
+        key = rng_key if rng_key is not None else os.urandom(32)
+        self.calls["pai_obfuscate"] += 1
+        self._chk(self.lib.pai_obfuscate(self._h, _ptr(ct), N, obf_mode, _ptr(r_buf) if r_buf is not None else None,
+                                         r_stride, r_bytes, key, index_base, _ptr(out)))
+        return out
 
     def add(self, cts: Sequence[np.ndarray], exps: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
         k = len(cts)

@@ -107,6 +107,40 @@ class PaillierArray(np.ndarray):
             return None
         return pk
 
+    def apply_obfuscation(self):
+        """PaillierEncryptedNumber.apply_obfuscation (encrypted_number.py:58-63) on every element that is not yet
+        obfuscated, in place and in ONE GPU call (pai_obfuscate) instead of one encryption of 0 per element. Elements
+        already flagged keep their bits; the others keep their identity and get a fresh ciphertext and the flag, so a
+        later ``e.ciphertext()`` costs nothing. A second call makes no GPU call. Returns self."""
+        from . import _runtime
+        from .obfuscator import apply_obfuscation_array
+        A, pk = _encrypted_operand(self)
+        if A is None:
+            if np.asarray(self).size == 0:
+                return self
+            raise TypeError("apply_obfuscation needs an array of PaillierEncryptedNumber with one public key")
+        flat = A.reshape(-1)
+        todo = np.flatnonzero(np.fromiter((not e._is_obfuscated() for e in flat), dtype=bool, count=flat.size))
+        if todo.size == 0:
+            return self
+        words, exps, ints = pack(self, pk)
+        if todo.size == flat.size:
+            new_words = apply_obfuscation_array(words, pk)
+        else:
+            new_words = words.copy()
+            new_words[todo] = apply_obfuscation_array(words[todo], pk)
+        if todo.size == flat.size:
+            new_ints = _runtime.words_to_ints(new_words)
+            for e, c in zip(flat, new_ints):
+                e._set_obfuscated(c)
+        else:
+            new_ints = list(ints)
+            for i, c in zip(todo.tolist(), _runtime.words_to_ints(new_words[todo])):
+                flat[i]._set_obfuscated(c)
+                new_ints[i] = c
+        self._packed = _Packed(pk.n, new_words, np.asarray(exps, dtype=np.int64), new_ints)
+        return self
+
     def __add__(self, other):
         res = add_encrypted(self, other)
         if res is NotImplemented:
@@ -504,15 +538,21 @@ def _wire_bytes(n: int, shape, exps, obf, words) -> bytes:
                             np.ascontiguousarray(words, dtype="<u4").tobytes()])
 
 
-def to_wire(arr) -> bytes:
+def to_wire(arr, be_secure: bool = False) -> bytes:
     """Serialise an array of PaillierEncryptedNumber (one public key), or a CiphertextBuffer, into the
-    bulk format."""
+    bulk format. be_secure=True first re-randomises, in place and in one GPU call, every element that is not yet
+    obfuscated (the array form of ``ciphertext(be_secure=True)``, encrypted_number.py:50-56), so every shipped flag
+    is 1; the default ships the ciphertexts as they are."""
     from .cipher_buffer import CiphertextBuffer
     if isinstance(arr, CiphertextBuffer):
-        return arr.to_wire()
+        return arr.to_wire(be_secure)
     A, pk = _encrypted_operand(arr)
     if A is None:
         raise TypeError("to_wire needs a non-empty array of PaillierEncryptedNumber with one public key")
+    if be_secure:
+        if not isinstance(arr, PaillierArray):
+            arr = PaillierArray(A)          # a view of the same element objects
+        arr.apply_obfuscation()
     words, exps, _ = pack(arr if isinstance(arr, PaillierArray) else A, pk)
     obf = np.fromiter((e._is_obfuscated() for e in A.reshape(-1)), dtype=np.uint8, count=A.size)
     return _wire_bytes(pk.n, A.shape, exps, obf, words)

@@ -63,8 +63,28 @@ class CiphertextBuffer(object):
         from .cipher_array import materialize
         return materialize(self.public_key, self.words, self.exps, self.shape, obfuscated=self.obfuscated != 0)
 
-    def to_wire(self) -> bytes:
+    def apply_obfuscation(self) -> "CiphertextBuffer":
+        """Re-randomise, in place and in ONE GPU call (pai_obfuscate), every ciphertext whose flag is not set, and
+        set the flags: PaillierEncryptedNumber.apply_obfuscation (encrypted_number.py:58-63) per element, with no
+        object built. Flagged elements keep their bits; a second call makes no GPU call. Returns self."""
+        from .obfuscator import apply_obfuscation_array
+        todo = np.flatnonzero(self.obfuscated == 0)
+        if todo.size == 0:
+            return self
+        if todo.size == self.size:
+            self.words = apply_obfuscation_array(self.words, self.public_key)
+        else:
+            words = self.words.copy()
+            words[todo] = apply_obfuscation_array(self.words[todo], self.public_key)
+            self.words = words
+        self.obfuscated[todo] = 1
+        return self
+
+    def to_wire(self, be_secure: bool = False) -> bytes:
+        """be_secure=True: apply_obfuscation() first, so every shipped flag is 1."""
         from .cipher_array import _wire_bytes
+        if be_secure:
+            self.apply_obfuscation()
         return _wire_bytes(self.public_key.n, self.shape, self.exps, self.obfuscated, self.words)
 
     def reshape(self, *shape) -> "CiphertextBuffer":

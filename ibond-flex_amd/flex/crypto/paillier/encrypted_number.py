@@ -45,6 +45,12 @@ class PaillierEncryptedNumber(object):
     def _is_obfuscated(self) -> bool:
         return self.__is_obfuscator
 
+    def _set_obfuscated(self, ciphertext: int) -> None:
+        """The array paths' apply_obfuscation (cipher_array.PaillierArray.apply_obfuscation): the re-randomised
+        ciphertext computed for this element in a batch."""
+        self.__ciphertext = ciphertext
+        self.__is_obfuscator = True
+
     def __add__(self, other):
         if isinstance(other, __class__):
             return self.__add_encryptednumber(other)

@@ -20,6 +20,21 @@ def obfuscator_power(pub_key, random_value: int = None) -> int:
     return _native.words_to_ints(ct)[0]
 
 
+def apply_obfuscation_array(words, pub_key, random_value: int = None) -> np.ndarray:
+    """The array twin of apply_obfuscation: [N, W] little-endian uint32 ciphertext words -> the words of
+    c_i * r_i^n mod n^2, in ONE GPU call (pai_obfuscate: r^n by the encrypt chains, one product kernel). random_value
+    None (or 0, as in obfuscator_power): a fresh device-CSPRNG r per element; an int: that r for every element, reduced
+    mod n^2 as PaillierEncryptor._encrypt_numpy reduces it; 1: a copy (mulmod(c, 1, n^2))."""
+    from . import _native, _runtime
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    if random_value == 1:
+        return words.copy()
+    ctx = _runtime.context(pub_key)
+    if random_value:
+        return ctx.obfuscate(words, obf_mode=_native.PAI_OBF_GIVEN, r_scalar=int(random_value) % pub_key.nsquare)
+    return ctx.obfuscate(words, obf_mode=_native.PAI_OBF_RNG)
+
+
 def apply_obfuscation(ciphertext: int, pub_key, random_value: int = None) -> int:
     if random_value == 1:
         return gmpy_math.mulmod(ciphertext, 1, pub_key.nsquare)     # gmpy_math.powmod(1, ...) == 1

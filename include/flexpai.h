@@ -24,6 +24,8 @@
  *   pai_matmul[_dev]      <- ndarray.dot of encrypted by plain (he_otp_lr_ft1/train.py:160,
  *                            he_otp_lr_ft2/train.py:188): per output sum_k c_ik (x) x_kj, i.e. __mul__ then
  *                            __add__ (encrypted_number.py:65-69, 86-113, 166-185)
+ *   pai_obfuscate[_dev]   <- PaillierEncryptedNumber.apply_obfuscation / ciphertext(be_secure=True) over arrays
+ *                            (encrypted_number.py:50-63 -> apply_obfuscation obfuscator.py:23-37): c * r^n mod n^2
  *   pai_next_prime        <- gmpy2.next_prime(r) of getprimeover    flex/crypto/gmpy_math.py:77-87, the two prime
  *                            searches of generate_paillier_keypair  flex/crypto/paillier/keypair.py:93-127 (one batch):
  *                            a sieve by the odd primes below 2000 on the host, then Miller-Rabin on 16-lane rows
@@ -175,6 +177,9 @@ typedef struct pai_comm pai_comm;
 #define PAI_OPT_MATMUL_PATH 17   /* read-only: the path of this context's last pai_matmul[_dev] call: 0 = none yet,
                                   * 1 = term path, 2 = fused                                                     */
 
+#define PAI_OPT_OBF_CHUNK 18     /* elements per slice of an in-place pai_obfuscate_dev (default 262 144, at least 64): the
+                                  * call keeps r^n of one slice in a buffer of the context. Same bits for every value */
+
 /* Number of visible GPUs (0 when there is none or the runtime cannot start). */
 int pai_device_count(int* count);
 /* Free and total device memory of `device` (bytes). */
@@ -259,6 +264,22 @@ int pai_encrypt(pai_ctx* ctx, int dtype, const void* x, size_t N, int exp_mode, 
 int pai_add(pai_ctx* ctx, const uint32_t* const* cts, const int32_t* const* exps, int k, size_t N,
             uint32_t* ct_out, int32_t* exp_out);
 
+/* Re-randomise N ciphertexts: ct_out_i = ct_i * r_i^n mod n^2 (apply_obfuscation, obfuscator.py:23-37, over an array).
+ * obf_mode is PAI_OBF_GIVEN (r_le, r_stride_bytes, r_bytes as for pai_encrypt) or PAI_OBF_RNG (rng_key32; element i
+ * uses the global index index_base + i); PAI_OBF_NONE is PAI_ERR_ARG. Exponents are not touched and not passed.
+ * Inputs must be < n^2, as for pai_add. ct_out may be ct.
+ *
+ * The bits contract: out[i] = ct[i] * E0[i] mod n^2, where E0 is what pai_encrypt_dev writes for N int64 zeros
+ * (PAI_EXP_AUTO) on the same context state with the same obf_mode, r, rng key, index_base and N. The call takes the
+ * route of that encryption (csrc/encrypt_route.hpp): it counts its N elements towards the same break-even counters
+ * (pai_ctx_fixed_base_policy, pai_ctx_public_fb_policy), builds the same tables and draws the same r per global
+ * element index. The sampler is decided once per call, for all N, so the bits depend neither on PAI_OPT_OBF_CHUNK nor
+ * on the host-buffer call's chunks; a call cut in two by the caller (index_base advanced by the first part's count)
+ * gives the same bits whenever both parts meet the same sampler (tables resident, or never wanted). */
+int pai_obfuscate(pai_ctx* ctx, const uint32_t* ct, size_t N, int obf_mode,
+                  const uint8_t* r_le, size_t r_stride_bytes, size_t r_bytes,
+                  const uint8_t* rng_key32, uint64_t index_base, uint32_t* ct_out);
+
 /* Decrypt + decode. val_out: float64 value (status OK/INT), mant_out: signed mantissa when it
  * fits int64 (nullable), status_out (required), raw_out: N * pt_words canonical plaintexts
  * m = D(c) in [0, n) (nullable).                                                              */
@@ -311,6 +332,12 @@ int pai_add_dev(pai_ctx* ctx, const uint32_t* d_cts, const int32_t* d_exps, int 
                 uint32_t* d_out, int32_t* d_exp_out, void* stream);
 int pai_decrypt_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, double* d_val,
                     int64_t* d_mant, int32_t* d_status, uint32_t* d_raw, void* stream);
+/* pai_obfuscate on device buffers (r as for pai_encrypt_dev); the bits contract above. d_out == d_ct re-randomises in
+ * place, in slices of PAI_OPT_OBF_CHUNK elements; a d_out that does not overlap d_ct receives r^n first and the
+ * product over it, with no further buffer; a partial overlap is PAI_ERR_ARG. As asynchronous as pai_encrypt_dev. */
+int pai_obfuscate_dev(pai_ctx* ctx, const uint32_t* d_ct, size_t N, int obf_mode,
+                      const uint32_t* d_r_words, size_t r_stride_words, size_t r_words,
+                      const uint8_t* rng_key32, uint64_t index_base, uint32_t* d_out, void* stream);
 int pai_mul_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int dtype, const void* d_x,
                 size_t x_stride, uint32_t* d_out, int32_t* d_exp_out, int32_t* d_status, void* stream);
 int pai_add_plain_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int dtype,
