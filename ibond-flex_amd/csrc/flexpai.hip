@@ -79,6 +79,61 @@ static int fail(int code, const std::string& msg) {
 // The test build keeps 0, so that its contexts -- the cross-checks' references -- stay on the kernels the rows stand in for.
 constexpr long long CRTW_DEFAULT_MAX = FLEXPAI_XCHECK ? 0 : 4096;
 
+// Device allocations that are released together: plain hipMalloc blocks (constants) and TableArena blocks (tables)
+static void free_device(std::vector<void*>& mem, std::vector<void*>& tables) {
+  for (void* p : mem) (void)hipFree(p);
+  for (void* p : tables) TableArena::get().free(p);
+  mem.clear();
+  tables.clear();
+}
+
+// Everything one build of the key holder's fixed-base tables produced (ensure_fb). release() frees the memory and
+// returns every field to its default, so nothing of a released build can be read again.
+struct FbTables {
+  int K = 0;                    // digit positions
+  int W_used = 0;               // window of the resident tables (may be below pai_ctx::fb_W under a memory cap)
+  int raw_bits = 0;
+  FbRed* d_red = nullptr;       // [2] k_fb_digits: the exponent reduction mod p_h - 1
+  // 1024/2048-bit keys: pair tables over the S limbs of p_h
+  int pair_s = 0;               // S (19 / 37); 0 = no pair tables
+  bool shoup = false;           // Shoup rows (kernels_fbs.hpp, k_fbs); the test build's $FLEXPAI_FBS=0: Montgomery rows (k_fbp)
+  FbpHalf* d_fbp = nullptr;     // [2]
+  FbsConst* d_fbs_cst = nullptr;   // [2] k_fbs_fill's constants (table construction only)
+  uint32_t* d_fbp_fin_cs = nullptr;        // k_fbp_fin: its 12 S constant words,
+  const uint32_t* d_fbp_fin_p = nullptr;   //   p
+  uint32_t fbp_fin_mprime = 0;
+  // 4096-bit keys: pair-group tables (kernels_grp_pair.hpp)
+  bool gpair = false;
+  FbgpHalf* d_fbgp = nullptr;   // [2]
+  SgpHalf* d_sgp = nullptr;     // [2] the split-pair sampler over the same tables (kernels_sgp.hpp)
+  SgsHalf* d_sgs = nullptr;     // [2]   ... on Shoup rows (kernels_sgs.hpp)
+  const uint32_t* d_sgp_q = nullptr;   // q's S limbs (k_sgp_fin)
+  const uint32_t* d_m0 = nullptr;                 // k_fbg_garner: p^2 (FbgpHalf::p2 of the p half),
+  uint32_t *d_m8 = nullptr, *d_coefR = nullptr;   //   8 p^2, (q^2)^-1 R mod p^2
+  uint32_t mprime0 = 0;         //   ... and p^2's Montgomery constant
+  uint32_t* d_q2Rn = nullptr;   // q^2 R mod n^2 (k_fbg_fin)
+  std::vector<void*> mem;       // the constants above
+  std::vector<void*> tables;    // the tables themselves (TableArena: pooled device memory)
+  float host_ms = 0.f, dev_ms = 0.f;
+  uint64_t table_bytes = 0;
+  void release() {
+    free_device(mem, tables);
+    *this = FbTables();
+  }
+};
+
+// The same for the public-key tables (ensure_pfb)
+struct PfbTables {
+  int K = 0, K0 = 0, W_used = 0;   // digit positions (K0 of them e_0's), window
+  PfbConst* d_pfb = nullptr;
+  SgpHalf* d_sgp = nullptr;        // the split-pair sampler over the public tables (kernels_sgp.hpp)
+  std::vector<void*> mem, tables;
+  void release() {
+    free_device(mem, tables);
+    *this = PfbTables();
+  }
+};
+
 struct pai_ctx {
   int device = 0;
   int nb = 0;
@@ -162,49 +217,22 @@ struct pai_ctx {
   int fb_state = FB_UNTRIED;
   std::string fb_reason;        // why the fixed-base path is unavailable
   bool fb_enabled = true;
-  int fb_K = 0;
-  int fb_W = 0;                 // digit window (bits); 0 = not chosen yet ($FLEXPAI_FB_WINDOW, default 16)
-  int fb_W_used = 0;            // window of the resident tables (may be below fb_W under a memory cap)
-  int fb_raw_bits = 0;
-  FbHalf* d_fb_halves = nullptr;
-  FbpHalf* d_fbp_halves = nullptr;  // pair tables (kernels_fbp.hpp): the default for 1024/2048-bit keys
-  uint32_t *d_fbp_fin_cs = nullptr, *d_fbp_fin_p = nullptr;   // k_fbp_fin: its 12 S constant words, p
-  uint32_t fbp_fin_mprime = 0;
-  int fb_pair_s = 0;            // limbs of p_h of the resident pair tables; 0 = k_fb tables
-  bool fb_shoup = false;        // the pair tables hold Shoup rows (kernels_fbs.hpp, k_fbs) instead of Montgomery rows
-  FbsConst* d_fbs_cst = nullptr;   // [2] k_fbs_fill's constants (table construction only)
-  FbgpHalf* d_fbgp_halves = nullptr;  // 4096-bit keys: pair-group tables (kernels_grp_pair.hpp)
-  bool fb_gpair = false;
-  SgpHalf* d_sgp_fb = nullptr;  // 4096-bit keys: the split-pair sampler over the same tables (kernels_sgp.hpp)
-  SgsHalf* d_sgs_fb = nullptr;  //   ... on Shoup rows ($FLEXPAI_SGS=1, kernels_sgs.hpp)
-  const uint32_t* d_sgp_q = nullptr;   //   q's S limbs (k_sgp_fin)
-  FbRed* d_fb_red = nullptr;
-  uint32_t *d_fb_m8 = nullptr, *d_fb_coefR = nullptr, *d_fb_q2 = nullptr, *d_fb_m0 = nullptr;
-  uint32_t* d_fb_q2Rn = nullptr;  // 4096-bit keys: q^2 R mod n^2 (k_fbg_fin)
-  uint32_t fb_mprime0 = 0;      // p^2 (Garner)
+  int fb_W = 0;                 // requested digit window (bits); 0 = not chosen yet ($FLEXPAI_FB_WINDOW, default 16)
   uint32_t fb_g[2] = {0, 0};   // the bases g_p, g_q (generators of Z_p*, Z_q*)
-  std::vector<void*> fb_mem;    // the tables' constants and build scratch (rebuilt when the window changes)
-  std::vector<void*> fb_tables; // the tables themselves (TableArena: pooled device memory)
   HBig fb_p, fb_q;              // p < q
-  float fb_host_ms = 0.f, fb_dev_ms = 0.f;
-  uint32_t* fb_last_w = nullptr;  // debugging: k_fb output of the last chunk ([2][SB][fb_last_n])
+  FbTables fb;                  // the resident tables and their constants (rebuilt when the window changes)
+  uint32_t* fb_last_w = nullptr;  // debugging: the sampler's output of the last chunk (pai_debug_fb_w), in d_work
   long long fb_last_n = 0;
-  uint64_t fb_table_bytes = 0;
   GuardRec* d_guard = nullptr;  // test build: the address guards' record (guard.hpp); null in the product
   // public-key fixed-base obfuscators (kernels_pfb.hpp): device-RNG encryption without the private key.
   // Built lazily past the break-even count (or pai_ctx_public_fb_prepare); never needed for correctness.
   int pfb_state = FB_UNTRIED;
   std::string pfb_reason;
   bool pfb_enabled = true;
-  int pfb_W = 0, pfb_W_used = 0, pfb_K = 0, pfb_K0 = 0, pfb_KS = 0;
+  int pfb_W = 0;                // requested window; 0 = not chosen yet
   std::vector<HBig> pfb_bases;  // g_0 .. g_PFB_SHORT (chosen at the first build unless set)
-  PfbConst* d_pfb = nullptr;
-  SgpHalf* d_sgp_pfb = nullptr;  // the split-pair sampler over the public tables (kernels_sgp.hpp)
-  std::vector<void*> pfb_mem;
-  std::vector<void*> pfb_tables;  // (TableArena)
+  PfbTables pfb;
   long long pfb_seen = 0;
-  float pfb_host_ms = 0.f, pfb_dev_ms = 0.f;
-  uint64_t pfb_table_bytes = 0;
   long long fb_seen = 0;        // device-RNG elements encrypted under this key before the tables exist
   int fb_call = 0;              // host-buffer call in progress: its one fixed-base decision (+1 / -1), else 0
   int pfb_call = 0;             // the same for the public fixed-base sampler
@@ -321,10 +349,8 @@ pai_ctx::~pai_ctx() {
   if (d_guard) (void)hipFree(d_guard);
   for (void* p : allocs) (void)hipFree(p);
   for (void* p : priv_allocs) (void)hipFree(p);
-  for (void* p : fb_mem) (void)hipFree(p);
-  for (void* p : pfb_mem) (void)hipFree(p);
-  for (void* p : fb_tables) TableArena::get().free(p);
-  for (void* p : pfb_tables) TableArena::get().free(p);
+  fb.release();
+  pfb.release();
   if (counted && g_contexts.load() == 0) TableArena::get().trim();   // the process's last context: pooled chunks go back
   if (d_scratch) (void)hipFree(d_scratch);
   if (d_work) (void)hipFree(d_work);
@@ -370,17 +396,32 @@ struct CtxLock {
   }
 };
 
+// v -> a device block of its own, owned by `owner` (whoever holds that list frees it)
 template <typename T>
-static int upload(pai_ctx* c, const std::vector<T>& v, T** out) {
+static int upload_to(std::vector<void*>& owner, const std::vector<T>& v, T** out) {
   const auto t0 = std::chrono::steady_clock::now();
   void* p = nullptr;
   HIPCHK(hipMalloc(&p, std::max<size_t>(v.size(), 1) * sizeof(T)));
-  (c->in_priv ? c->priv_allocs : c->allocs).push_back(p);
+  owner.push_back(p);
   if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   *out = (T*)p;
   ++g_upload_n;
   g_upload_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
   return 0;
+}
+template <typename T>
+static int upload(pai_ctx* c, const std::vector<T>& v, T** out) {
+  return upload_to(c->in_priv ? c->priv_allocs : c->allocs, v, out);
+}
+
+static void append(std::vector<uint32_t>& to, const std::vector<uint32_t>& v) { to.insert(to.end(), v.begin(), v.end()); }
+
+// v < P^2 as the pair [v mod P : limbs][v div P : limbs] of 28-bit limbs (the pair kernels' residues mod P^2)
+static std::vector<uint32_t> pair_split(const HBig& v, const HBig& P, int limbs) {
+  const HBig qt = div_big(v, P);
+  std::vector<uint32_t> out = sub(v, mul(qt, P)).limbs(limbs, LB);
+  append(out, qt.limbs(limbs, LB));
+  return out;
 }
 
 static int tpi_for_bits(size_t need_bits, int min_tpi) {
@@ -1054,19 +1095,6 @@ static int setup_pe4(pai_ctx* c, const HBig& n) {
   return 0;
 }
 
-template <typename T>
-static int upload_fb(pai_ctx* c, const std::vector<T>& v, T** out) {
-  const auto t0 = std::chrono::steady_clock::now();
-  void* p = nullptr;
-  HIPCHK(hipMalloc(&p, std::max<size_t>(v.size(), 1) * sizeof(T)));
-  c->fb_mem.push_back(p);
-  if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = (T*)p;
-  ++g_upload_n;
-  g_upload_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-  return 0;
-}
-
 // Split-pair sampler (kernels_sgp.hpp) over the pair-group tables of modulus P (rows T R, R = 2^(28 FBGP_S)): C =
 // 2^(-56 K) mod P^2 as (C mod P, C div P), the chunk weights w 2^(16 c) C_A mod P of c0 = (1, w |M|), and 2^20 P.
 // FLEXPAI_SGP=0 keeps the group-engine samplers (k_fbgp, k_pfb).
@@ -1090,21 +1118,18 @@ static bool sgp_fin_enabled() {
   return !e || atoi(e) != 0;
 }
 
-template <class Upload>
-static int sgp_make_half(const HBig& P, const HBig& w, int K, const void* table, Upload&& up, SgpHalf* out) {
+static int sgp_make_half(const HBig& P, const HBig& w, int K, const void* table, std::vector<void*>& mem, SgpHalf* out) {
   const HBig P2 = mul(P, P);
   const HBig C = inv_mod(mul_pow2_mod(HBig(1), (size_t)LB * (FBGP_S - SGP_S) * K, P2), P2);
   if (C.is_zero()) return fail(PAI_ERR_KEY, "split-pair sampler: 2 not invertible mod P^2");
   const HBig cb = div_big(C, P), ca = sub(C, mul(cb, P));
   std::vector<uint32_t> nmc;
-  for (int k = 0; k < 4; ++k) {
-    const std::vector<uint32_t> v = mod(mul(mul_pow2_mod(mod(w, P), (size_t)16 * k, P), ca), P).limbs(SGP_S, LB);
-    nmc.insert(nmc.end(), v.begin(), v.end());
-  }
+  for (int k = 0; k < 4; ++k) append(nmc, mod(mul(mul_pow2_mod(mod(w, P), (size_t)16 * k, P), ca), P).limbs(SGP_S, LB));
   uint32_t *dp, *dca, *dcb, *dnmc, *dpb;
   int rc;
-  if ((rc = up(P.limbs(SGP_S, LB), &dp)) || (rc = up(ca.limbs(SGP_S, LB), &dca)) || (rc = up(cb.limbs(SGP_S, LB), &dcb)) ||
-      (rc = up(nmc, &dnmc)) || (rc = up(mul(P, pow2(20)).limbs(SGP_S, LB), &dpb)))
+  if ((rc = upload_to(mem, P.limbs(SGP_S, LB), &dp)) || (rc = upload_to(mem, ca.limbs(SGP_S, LB), &dca)) ||
+      (rc = upload_to(mem, cb.limbs(SGP_S, LB), &dcb)) || (rc = upload_to(mem, nmc, &dnmc)) ||
+      (rc = upload_to(mem, mul(P, pow2(20)).limbs(SGP_S, LB), &dpb)))
     return rc;
   *out = SgpHalf{(const uint4*)table, dp, dca, dcb, dnmc, dpb, mont_prime(P, LB)};
   return 0;
@@ -1116,17 +1141,14 @@ static int sgp_make_half(const HBig& P, const HBig& w, int K, const void* table,
 // both never ends up on the factored rows at the Shoup rows' lower window. Any failure here leaves the Montgomery sampler
 // k_sgp in place over the complete factored tables (returns nonzero with the reason in pai_last_error; the caller frees
 // at[] and keeps the fixed-base path).
-template <class Ctx>
-static int sgs_build(Ctx* c, const HBig* primes, int K, int W, void* const* t, const SgpHalf* sv, uint4* const* at) {
+static int sgs_build(pai_ctx* c, const HBig* primes, int K, int W, void* const* t, const SgpHalf* sv, uint4* const* at) {
   SgsHalf sh[2];
   const size_t rows = (size_t)K << W;
   for (int h = 0; h < 2; ++h) {
     const HBig& P = primes[h];
     std::vector<uint32_t> nmr;
-    for (int k = 0; k < 4; ++k) {
-      const std::vector<uint32_t> v = mul_pow2_mod(mod(primes[1 - h], P), (size_t)16 * k + (size_t)LB * FBGP_S, P).limbs(SGP_S, LB);
-      nmr.insert(nmr.end(), v.begin(), v.end());
-    }
+    for (int k = 0; k < 4; ++k)
+      append(nmr, mul_pow2_mod(mod(primes[1 - h], P), (size_t)16 * k + (size_t)LB * FBGP_S, P).limbs(SGP_S, LB));
     const HBig mu = div_big(pow2((size_t)2 * LB * SGP_S), P);
     if (mu.bits() > (size_t)LB * (SGP_S + 1)) return fail(PAI_ERR_KEY, "Shoup rows: mu exceeds S + 1 limbs");
     // R^-K mod P^2 = c_A (1 + P beta): the rows' Montgomery factor R = 2^(28 FBGP_S), once per row product
@@ -1146,21 +1168,22 @@ static int sgs_build(Ctx* c, const HBig* primes, int K, int W, void* const* t, c
     const HBig beta = mod(add(mul(cB, cAi), delta), P);
     uint32_t *dn, *dmu, *dcy, *dbr;
     int rc;
-    if ((rc = upload_fb(c, nmr, &dn)) || (rc = upload_fb(c, mu.limbs(SGP_S + 2, LB), &dmu)) ||
-        (rc = upload_fb(c, y.words(FBGP_PW), &dcy)) ||
-        (rc = upload_fb(c, mul_pow2_mod(beta, (size_t)LB * FBGP_S, P).limbs(SGP_S, LB), &dbr)))
+    std::vector<void*>& mem = c->fb.mem;
+    if ((rc = upload_to(mem, nmr, &dn)) || (rc = upload_to(mem, mu.limbs(SGP_S + 2, LB), &dmu)) ||
+        (rc = upload_to(mem, y.words(FBGP_PW), &dcy)) ||
+        (rc = upload_to(mem, mul_pow2_mod(beta, (size_t)LB * FBGP_S, P).limbs(SGP_S, LB), &dbr)))
       return rc;
     sh[h] = SgsHalf{at[h], (const uint4*)t[h], sv[h].p, dn, sv[h].pbig, dmu, dcy, dbr, sv[h].mprime};
   }
   SgsHalf* d = nullptr;
   std::vector<SgsHalf> shv(sh, sh + 2);
   int rc;
-  if ((rc = upload_fb(c, shv, &d))) return rc;
+  if ((rc = upload_to(c->fb.mem, shv, &d))) return rc;
   if (sgs_launch_conv(d, rows, at[0], at[1], nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
     (void)hipGetLastError();
     return fail(PAI_ERR_HIP, "Shoup row conversion failed");
   }
-  c->d_sgs_fb = d;
+  c->fb.d_sgs = d;
   return 0;
 }
 
@@ -1314,28 +1337,9 @@ static long long fb_break_even(const pai_ctx* c, int W, int K, int row_bytes) {
 
 static bool fb_wanted(pai_ctx* c, long long n);
 static bool pfb_supported(const pai_ctx* c);
-static void pfb_release(pai_ctx* c);
-
-static void fb_release(pai_ctx* c) {
-  for (void* p : c->fb_mem) (void)hipFree(p);
-  c->fb_mem.clear();
-  for (void* p : c->fb_tables) TableArena::get().free(p);
-  c->fb_tables.clear();
-  c->d_fb_halves = nullptr;
-  c->d_fbp_halves = nullptr;
-  c->d_fbp_fin_cs = c->d_fbp_fin_p = nullptr;
-  c->fb_pair_s = 0;
-  c->fb_shoup = false;
-  c->d_fbs_cst = nullptr;
-  c->d_fbgp_halves = nullptr;
-  c->fb_gpair = false;
-  c->d_sgp_fb = nullptr;
-  c->d_sgs_fb = nullptr;
-  c->d_fb_red = nullptr;
-}
 
 static int fb_unavailable(pai_ctx* c, const std::string& why) {
-  fb_release(c);
+  c->fb.release();
   (void)hipGetLastError();   // clear a failed allocation / launch so later calls start clean
   c->fb_state = pai_ctx::FB_UNAVAILABLE;
   c->fb_reason = why;
@@ -1391,388 +1395,381 @@ static int pair_host_invert(const HBig& m, uint32_t* d_cval, int nv, int S) {
   return 0;
 }
 
+// Device scratch of one modulus's factored-row build (kernels_fbp.hpp, kernels_grp_pair.hpp, kernels_pfb.hpp), sized from
+// the digit positions K, the window W and the limbs S of the modulus; freed with the object.
+struct RowScratch {
+  uint32_t* lohi = nullptr;    // [K][2][FB_LO][2S] lo/hi half-digit entries
+  uint32_t* inv = nullptr;     // [K][2][FB_LO][S] inverses of their A parts
+  uint32_t* pre = nullptr;     // [2K][2^(W - W/2)][S] the batch inversion's prefix products
+  uint32_t* cval = nullptr;    // [2K][S] the chain products, then their inverses (pair_host_invert)
+  uint32_t* bases = nullptr;   // [K][2][2S] the public tables' digit bases (a key holder uploads its own)
+  RowScratch() = default;
+  RowScratch(const RowScratch&) = delete;
+  RowScratch& operator=(const RowScratch&) = delete;
+  ~RowScratch() { free(); }
+  bool alloc(int K, int W, int S, bool with_bases = false) {
+    const size_t e = (size_t)S * 4, k = (size_t)K;
+    return hipMalloc(&lohi, k * 2 * FB_LO * 2 * e) == hipSuccess && hipMalloc(&inv, k * 2 * FB_LO * e) == hipSuccess &&
+           hipMalloc(&pre, (2 * k << (W - W / 2)) * e) == hipSuccess && hipMalloc(&cval, 2 * k * e) == hipSuccess &&
+           (!with_bases || hipMalloc(&bases, k * 2 * 2 * e) == hipSuccess);
+  }
+  void free() {
+    for (uint32_t** p : {&lohi, &inv, &pre, &cval, &bases}) {
+      if (*p) (void)hipFree(*p);
+      *p = nullptr;
+    }
+  }
+};
+
+// The factored rows of nmod moduli (S limbs each, K digit positions): phase 1 (the lo/hi entries and the batch inversion's
+// forward pass), the host inversion of each modulus's 2K chain products, phase 2 (backward pass, fill). lab: the setup
+// trace's labels of phase 1, of the inversion (null: timed with phase 1) and of phase 2. The reason of a failure is in
+// pai_last_error.
+template <class Phase1, class Phase2>
+static int build_factored_rows(const char* const (&lab)[3], Phase1&& phase1, Phase2&& phase2, const HBig* mods,
+                               const RowScratch* sc, int nmod, int K, int S) {
+  {
+    std::optional<SetupTrace> tr(std::in_place, lab[0]);
+    if (phase1() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(PAI_ERR_HIP, "table construction failed");
+    if (lab[1]) tr.emplace(lab[1]);
+    for (int h = 0; h < nmod; ++h)
+      if (int rc = pair_host_invert(mods[h], sc[h].cval, 2 * K, S)) return rc;
+  }
+  SetupTrace tr(lab[2]);
+  if (phase2() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(PAI_ERR_HIP, "table construction failed");
+  return 0;
+}
+
+// What ensure_fb builds for this key within the memory budget: the sampler family, the window and the digit geometry.
+// why: the first check that refuses the key, in ensure_fb's order (null: the key is accepted). The window is chosen
+// whenever one fits, whatever the later checks say, so that fb_threshold prices the very build ensure_fb would start.
+struct FbPlan {
+  const char* why = nullptr;
+  int sb = 0;            // limbs of p_h^2 (crt_sb)
+  bool grp = false;      // 4096-bit keys: halves of 148 limbs, recombined by the group-engine Garner kernels
+  int ps = 0;            // 1024/2048-bit keys: pairs over the ps = 19 / 37 limbs of p_h (kernels_fbp.hpp)
+  bool shoup = false;    //   ... on Shoup rows (kernels_fbs.hpp); the product takes nothing else
+  bool gpair = false;    // 4096-bit keys: pair groups (kernels_grp_pair.hpp)
+  bool sgp = false;      //   ... with the split-pair sampler's constants (kernels_sgp.hpp); the product takes nothing else
+  bool sgs = false;      //   ... and Shoup rows beside the factored rows (kernels_sgs.hpp; fb_choose)
+  int S = 0;             // limbs of a pair's components: ps, or FBGP_S
+  int row_words = 0;     // 32-bit words of one resident row (without the 4096-bit Shoup rows)
+  int W = 0, K = 0, raw_bits = 0;
+  size_t rows() const { return (size_t)K << W; }   // per half
+};
+
+static FbPlan fb_plan(pai_ctx* c, bool allow_sgs = true) {
+  FbPlan pl;
+  auto refuse = [&pl](const char* why) {
+    pl.why = why;
+    return pl;
+  };
+  if (!c->crt_ok && !c->fbg_ok) return refuse("needs the private key and the CRT kernels");
+  const int TW = fb_row_words(c);
+  if (!TW) return refuse("key size not supported by the fixed-base kernels");
+  pl.sb = c->crt_sb;
+  pl.grp = pl.sb == GRP_TPI * L;
+  pl.ps = pl.grp ? 0 : fb_pair_possible(c);
+  pl.shoup = pl.ps && fb_shoup_possible(c);
+  pl.gpair = pl.grp && fb_gpair_possible(c);
+  pl.sgp = pl.gpair && sgp_enabled();
+  pl.S = pl.ps ? pl.ps : FBGP_S;
+  pl.row_words = fb_table_row_words(c);
+  if (!c->fb_W) c->fb_W = fb_default_window();
+  pl.W = fb_choose(c, fb_budget(c), &pl.sgs, allow_sgs);
+  pl.K = pl.W ? fb_digit_count(c, pl.W) : 0;
+  pl.raw_bits = (int)std::max(sub(c->fb_p, HBig(1)).bits(), sub(c->fb_q, HBig(1)).bits()) + 64;
+  const size_t sq_bits = std::max(mul(c->fb_p, c->fb_p).bits(), mul(c->fb_q, c->fb_q).bits());
+  if (!pl.grp && (sq_bits > (size_t)32 * TW || c->ct_words != 2 * TW))
+    return refuse("unbalanced primes: p^2 or q^2 exceeds the table row");
+  if (!pl.W) return refuse("tables do not fit the device memory budget");
+  if ((pl.raw_bits + 31) / 32 > FB_RAW_MAX - 2) return refuse("exponent too wide");
+  // the Garner kernels take w_q < q^2 as an operand mod p^2 (k_fbg_garner: w_p + 8 p^2 - w_q > 0; k_fbp_fin: A_q, B_q <
+  // 2p): keys with q >= 2p encrypt on the generic CRT path
+  if (cmp(c->fb_q, shl1(c->fb_p)) >= 0) return refuse("q >= 2p: fixed-base Garner bounds");
+  // the test build also keeps the samplers the product's replaced: Montgomery rows on pairs (k_fbp, $FLEXPAI_FBS=0) and
+  // pair groups without the split-pair constants (k_fbgp, $FLEXPAI_SGP=0)
+  if (!pl.grp && !(FLEXPAI_XCHECK ? pl.ps != 0 : pl.shoup)) return refuse("key outside the pair sampler's bounds");
+  if (pl.grp && !(FLEXPAI_XCHECK ? pl.gpair : pl.sgp))
+    return refuse(FLEXPAI_XCHECK ? "key outside the pair-group sampler's bounds" : "key outside the split-pair sampler's bounds");
+  return pl;
+}
+
+// A build in flight: what ensure_fb's steps hand to each other. The scratch goes with it, however the build ends.
+struct FbHalfConst {
+  uint32_t g = 0;                                    // generator of Z_p_h*
+  std::vector<uint32_t> bases;                       // [K][2][2S] pairs of B_k R and B_k^(2^LO) R mod p_h^2, R = 2^(28 S)
+  std::vector<uint32_t> p, one, nm, pbig;            // p_h; pair of R mod p_h^2; c0 folding: the other prime's chunk
+                                                     //   weights 2^(CB c) mod p_h and the offset 2^PB p_h
+  std::vector<uint32_t> nmr, kap, fcst;              // pairs: nm R; pair of kappa R (p half); Shoup rows: mu, R^2 mod p_h
+  std::vector<uint32_t> x, p2, pr2;                  // pair groups: (1 - R) mod p_h; p_h^2; p_h R' mod p_h^2 (148 limbs)
+  FbRed red;                                         // exponent reduction mod p_h - 1
+};
+struct FbBuild {
+  FbPlan pl;
+  HBig primes[2], sq[2], coef;                       // p, q; p^2, q^2; (q^2)^-1 mod p^2
+  FbHalfConst hc[2];
+  RowScratch sc[2];
+  void* t[2] = {nullptr, nullptr};                   // the tables (owned by FbTables::tables)
+  uint4* sgs_rows[2] = {nullptr, nullptr};           // the 4096-bit Shoup rows' reservation (likewise)
+  FbpHalf pv[2];
+  FbgpHalf gv[2];
+  SgpHalf sv[2];
+};
+
+// The 4096-bit Shoup rows' memory is taken before anything is built: without room for it the tables are built at the
+// factored rows' own (higher) window instead of at the one chosen for both
+static bool sgs_reserve(pai_ctx* c, FbBuild& b) {
+  for (uint4*& r : b.sgs_rows) {
+    if (!(r = (uint4*)TableArena::get().alloc(c->device, b.pl.rows() * SGS_ROW_Q * sizeof(uint4)))) return false;
+    c->fb.tables.push_back(r);
+  }
+  return true;
+}
+static void sgs_unreserve(pai_ctx* c, FbBuild& b) {
+  std::vector<void*>& tb = c->fb.tables;
+  for (uint4*& r : b.sgs_rows) {
+    if (r) tb.erase(std::find(tb.begin(), tb.end(), (void*)r)), TableArena::get().free(r);
+    r = nullptr;
+  }
+}
+
+// The per-half host work that needs no device -- the generator search, G = g^n mod p_h^2 (ONE powm) and the digit bases
+// B_k by squarings, in the form the resident sampler's build takes -- for both halves at once on two threads (a fresh
+// key's setup, HE_SA_FT re-keys per exchange)
+static void fb_host_bases(const pai_ctx* c, FbBuild& b) {
+  SetupTrace tr_hp("  host prep (generator, G, B_k; both halves)");
+  auto prep = [&](int h) {
+    FbHalfConst& o = b.hc[h];
+    const HBig &P = b.primes[h], &m2 = b.sq[h];
+    o.g = c->fb_g[h] ? c->fb_g[h] : fb_base(P);
+    if (!o.g) return;
+    HMont M2(m2);
+    const int S = b.pl.S, W = b.pl.W;
+    const size_t RS = (size_t)LB * S;
+    HBig y = M2.to(M2.pow(HBig(o.g), c->n));
+    for (int k = 0; k < b.pl.K; ++k) {
+      append(o.bases, pair_split(mul_pow2_mod(M2.from(y), RS, m2), P, S));
+      append(o.bases, pair_split(mul_pow2_mod(M2.from(M2.sqr_k(y, (size_t)(W / 2))), RS, m2), P, S));
+      y = M2.sqr_k(y, (size_t)W);
+    }
+  };
+  std::thread t1(prep, 1);
+  prep(0);
+  t1.join();
+}
+
+// One half's remaining constants; returns the reason if the key cannot take the sampler
+static const char* fb_half_consts(FbBuild& b, int h) {
+  SetupTrace tr_h("  host prep (one half)");
+  const FbPlan& pl = b.pl;
+  FbHalfConst& o = b.hc[h];
+  const HBig &P = b.primes[h], &m2 = b.sq[h];
+  const HBig other = mod(b.primes[1 - h], P);
+  const int S = pl.S;
+  const size_t RS = (size_t)LB * S;
+  o.p = P.limbs(S, LB);
+  o.one = pair_split(mul_pow2_mod(HBig(1), RS, m2), P, S);
+  // c0 = 1 + n M: |M| in NC chunks of CB bits; negative M through the offset 2^PB p_h
+  const int CB = pl.ps ? FBP_CB : 16, NC = pl.ps ? FBP_NC : 4, PB = pl.ps ? FBP_PB : 20;
+  for (int k = 0; k < NC; ++k) {
+    append(o.nm, mul_pow2_mod(other, (size_t)CB * k, P).limbs(S, LB));
+    if (pl.ps) append(o.nmr, mul_pow2_mod(other, (size_t)CB * k + RS, P).limbs(S, LB));   // k_fbs: gamma R joins the b sum
+  }
+  o.pbig = mul(P, pow2(PB)).limbs(S, LB);
+  if (pl.ps) {
+    // position 0's lo entries are multiplied by kappa R (FbpHalf::kapR): kappa = q^-2 mod p^2 for the p half, so that
+    // the sampler leaves w_p q^-2 for k_fbp_fin; 1 (the pair of R) for the q half
+    if (h == 0) o.kap = pair_split(mul_pow2_mod(b.coef, RS, m2), P, S);
+    if (pl.shoup) {   // k_fbs_fill: mu = floor(R^2 / p_h) (S + 2 limbs), R^2 mod p_h (S limbs)
+      const HBig R2 = pow2(2 * RS);
+      const HBig mu = div_big(R2, P);
+      if (mu.bits() > (size_t)LB * (S + 1)) return "Shoup rows: mu exceeds S + 1 limbs";
+      o.fcst = mu.limbs(S + 2, LB);
+      append(o.fcst, mod(R2, P).limbs(S, LB));
+    }
+  } else {
+    o.x = mod(sub(add(P, HBig(1)), mul_pow2_mod(HBig(1), RS, P)), P).limbs(S, LB);
+    o.p2 = m2.limbs(pl.sb, LB);
+    o.pr2 = mul_pow2_mod(P, (size_t)LB * pl.sb, m2).limbs(pl.sb, LB);
+  }
+  const HBig D = sub(P, HBig(1));
+  const std::vector<uint32_t> dw = D.words((D.bits() + 31) / 32), muw = div_big(pow2((size_t)pl.raw_bits), D).words(4);
+  std::memset(&o.red, 0, sizeof(o.red));
+  std::copy(dw.begin(), dw.end(), o.red.D);
+  std::copy(muw.begin(), muw.end(), o.red.mu);
+  o.red.dwords = (int)dw.size();
+  o.red.kbits = (int)D.bits();
+  return nullptr;
+}
+
+// The device side of both halves: the table, the build scratch and the constants of each, then what both share -- the
+// exponent reduction and, on the 4096-bit layout that reads them, the p^2-Garner constants
+static int fb_upload_halves(pai_ctx* c, FbBuild& b) {
+  const FbPlan& pl = b.pl;
+  FbTables& fb = c->fb;
+  int rc;
+  for (int h = 0; h < 2; ++h) {
+    const FbHalfConst& o = b.hc[h];
+    RowScratch& sc = b.sc[h];
+    if (!sc.alloc(pl.K, pl.W, pl.S)) return fail(PAI_ERR_HIP, "table allocation failed");
+    {
+      SetupTrace tr_m("  table allocation (one half)");
+      if (!(b.t[h] = TableArena::get().alloc(c->device, pl.rows() * (pl.row_words / 4) * sizeof(uint4))))
+        return fail(PAI_ERR_HIP, "table allocation failed");
+    }
+    fb.tables.push_back(b.t[h]);
+    uint32_t *p, *one, *bases, *nm, *pbig;
+    if ((rc = upload_to(fb.mem, o.p, &p)) || (rc = upload_to(fb.mem, o.one, &one)) || (rc = upload_to(fb.mem, o.bases, &bases)) ||
+        (rc = upload_to(fb.mem, o.nm, &nm)) || (rc = upload_to(fb.mem, o.pbig, &pbig)))
+      return rc;
+    const uint32_t mprime = mont_prime(b.primes[h], LB);
+    if (pl.ps) {
+      uint32_t *nmr, *kap = one;
+      if ((rc = upload_to(fb.mem, o.nmr, &nmr)) || (h == 0 && (rc = upload_to(fb.mem, o.kap, &kap)))) return rc;
+      b.pv[h] = FbpHalf{(const uint4*)b.t[h], p, one, bases, sc.lohi, nm, pbig, mprime, sc.inv, sc.pre, sc.cval, kap, nmr};
+    } else {
+      uint32_t *x, *p2, *pr2;
+      if ((rc = upload_to(fb.mem, o.x, &x)) || (rc = upload_to(fb.mem, o.p2, &p2)) || (rc = upload_to(fb.mem, o.pr2, &pr2)))
+        return rc;
+      b.gv[h] = FbgpHalf{(const uint32_t*)b.t[h], p, x, one, bases, sc.lohi, nm, pbig, p2, pr2, mprime,
+                         mont_prime(b.sq[h], LB), sc.inv, sc.pre, sc.cval};
+      if (pl.sgp && (rc = sgp_make_half(b.primes[h], b.primes[1 - h], pl.K, b.t[h], fb.mem, &b.sv[h]))) return rc;
+    }
+  }
+  if ((rc = upload_to(fb.mem, std::vector<FbRed>{b.hc[0].red, b.hc[1].red}, &fb.d_red))) return rc;
+  if (pl.grp) {   // k_fbg_garner: p^2, 8 p^2, (q^2)^-1 R mod p^2; k_fbg_fin: q^2 R mod n^2
+    const size_t RB = (size_t)LB * pl.sb, RE = (size_t)LB * c->S_e;
+    fb.d_m0 = b.gv[0].p2;
+    fb.mprime0 = b.gv[0].mprime2;
+    if ((rc = upload_to(fb.mem, mul(b.sq[0], HBig(8)).limbs(pl.sb, LB), &fb.d_m8)) ||
+        (rc = upload_to(fb.mem, mul_pow2_mod(b.coef, RB, b.sq[0]).limbs(pl.sb, LB), &fb.d_coefR)) ||
+        (rc = upload_to(fb.mem, mul_pow2_mod(b.sq[1], RE, c->N).limbs(c->S_e, LB), &fb.d_q2Rn)))
+      return rc;
+  }
+  return 0;
+}
+
+// k_fbp_fin's constants (kernels_fbp.hpp): (q^-1 R)^, (q^-2 R)^ as pairs over p, then q, q^2, p q^2, 2p, 3p
+static int fbp_fin_consts(const FbBuild& b, std::vector<uint32_t>& cs) {
+  const HBig &P = b.primes[0], &Q = b.primes[1], &p2 = b.sq[0];
+  const int ps = b.pl.ps;
+  const size_t RS = (size_t)LB * ps;
+  const HBig qinv = inv_mod(mod(Q, p2), p2);
+  if (qinv.is_zero()) return fail(PAI_ERR_KEY, "q not invertible mod p^2");
+  cs = pair_split(mul_pow2_mod(qinv, RS, p2), P, ps);
+  append(cs, pair_split(mul_pow2_mod(b.coef, RS, p2), P, ps));
+  append(cs, Q.limbs(ps, LB));
+  append(cs, b.sq[1].limbs(2 * ps, LB));
+  append(cs, mul(P, b.sq[1]).limbs(3 * ps, LB));
+  append(cs, mul(P, HBig(2)).limbs(ps, LB));
+  append(cs, mul(P, HBig(3)).limbs(ps, LB));
+  return 0;
+}
+
+// What the sampler and its Garner kernels read of both halves at once
+static int fb_upload_sampler(pai_ctx* c, FbBuild& b) {
+  const FbPlan& pl = b.pl;
+  FbTables& fb = c->fb;
+  int rc;
+  if (pl.ps) {
+    if ((rc = upload_to(fb.mem, std::vector<FbpHalf>(b.pv, b.pv + 2), &fb.d_fbp))) return rc;
+    if (pl.shoup) {
+      FbsConst fc[2];
+      for (int h = 0; h < 2; ++h) {
+        uint32_t* d;
+        if ((rc = upload_to(fb.mem, b.hc[h].fcst, &d))) return rc;
+        fc[h] = FbsConst{d, d + pl.ps + 2};
+      }
+      if ((rc = upload_to(fb.mem, std::vector<FbsConst>(fc, fc + 2), &fb.d_fbs_cst))) return rc;
+    }
+    std::vector<uint32_t> cs;
+    if ((rc = fbp_fin_consts(b, cs)) || (rc = upload_to(fb.mem, cs, &fb.d_fbp_fin_cs))) return rc;
+    fb.d_fbp_fin_p = b.pv[0].p;
+    fb.fbp_fin_mprime = b.pv[0].mprime;
+  } else {
+    if ((rc = upload_to(fb.mem, std::vector<FbgpHalf>(b.gv, b.gv + 2), &fb.d_fbgp))) return rc;
+    if (pl.sgp) {
+      if ((rc = upload_to(fb.mem, std::vector<SgpHalf>(b.sv, b.sv + 2), &fb.d_sgp))) return rc;
+      fb.d_sgp_q = b.sv[1].p;
+    }
+  }
+  trace_uploads("  fb uploads");
+  return 0;
+}
+
+// The factored rows of both tables (the chain products are inverted on the host between the two phases), then the build
+// scratch goes back
+static int fb_build_rows(pai_ctx* c, FbBuild& b) {
+  const FbPlan& pl = b.pl;
+  const FbTables& fb = c->fb;
+  const int K = pl.K, W = pl.W;
+  auto phase1 = [&] { return pl.ps ? fbp_build_phase1(pl.ps, fb.d_fbp, K, W, nullptr) : fbgp_build_phase1(fb.d_fbgp, K, W, nullptr); };
+  auto phase2 = [&] {
+    if (!pl.ps) return fbgp_build_phase2(fb.d_fbgp, (uint32_t*)b.t[0], (uint32_t*)b.t[1], K, W, nullptr);
+    if constexpr (FLEXPAI_XCHECK)   // the test build's Montgomery rows
+      if (!pl.shoup) return fbp_build_phase2(pl.ps, fb.d_fbp, (uint4*)b.t[0], (uint4*)b.t[1], K, W, nullptr);
+    return fbs_build_phase2(pl.ps, fb.d_fbp, fb.d_fbs_cst, (uint4*)b.t[0], (uint4*)b.t[1], K, W, nullptr,
+                            guard_args(c, (unsigned long long)pl.rows(), 0, 0, 0));
+  };
+  static const char* const lab[3] = {"  phase 1 (lohi, inv_fwd) + host invert", nullptr, "  phase 2 (inv_bwd, fill) + frees"};
+  int rc;
+  if ((rc = build_factored_rows(lab, phase1, phase2, b.primes, b.sc, 2, K, pl.S)) || (rc = guard_collect(c, nullptr))) return rc;
+  SetupTrace tr_f("  scratch frees");
+  for (RowScratch& s : b.sc) s.free();
+  return 0;
+}
+
 // Builds everything the fixed-base path needs for window c->fb_W (or the largest smaller window within
 // the memory budget). Returns 1 when the path is ready, 0 when it is unavailable (reason in fb_reason);
 // never fails the caller.
 static int ensure_fb(pai_ctx* c) {
   if (c->fb_state == pai_ctx::FB_READY) return 1;
   if (c->fb_state == pai_ctx::FB_UNAVAILABLE) return 0;
-  if (!c->crt_ok && !c->fbg_ok) return fb_unavailable(c, "needs the private key and the CRT kernels");
-  const int sb = c->crt_sb, TW = fb_row_words(c);
-  if (!TW) return fb_unavailable(c, "key size not supported by the fixed-base kernels");
-  const bool grp = sb == GRP_TPI * L;   // group-engine rows (limbs), recombined by k_crt_fin
-  const HBig sq[2] = {mul(c->fb_p, c->fb_p), mul(c->fb_q, c->fb_q)};
-  if (!grp && (sq[0].bits() > (size_t)32 * TW || sq[1].bits() > (size_t)32 * TW || c->ct_words != 2 * TW))
-    return fb_unavailable(c, "unbalanced primes: p^2 or q^2 exceeds the table row");
-  if (!c->fb_W) c->fb_W = fb_default_window();
-  const uint64_t budget = fb_budget(c);
-  bool sgs = false;
-  int W = fb_choose(c, budget, &sgs);
-  if (!W) return fb_unavailable(c, "tables do not fit the device memory budget");
-  // the 4096-bit Shoup rows' memory is taken first: without room for it the tables are built at the factored rows'
-  // own (higher) window instead of at the one chosen for both
-  uint4* sgs_rows[2] = {nullptr, nullptr};
-  if (sgs) {
-    const size_t rows = (size_t)fb_digit_count(c, W) << W;
-    for (int h = 0; h < 2 && sgs; ++h)
-      if (!(sgs_rows[h] = (uint4*)TableArena::get().alloc(c->device, rows * SGS_ROW_Q * sizeof(uint4)))) sgs = false;
-    if (!sgs) {
-      for (uint4*& r : sgs_rows)
-        if (r) TableArena::get().free(r), r = nullptr;
-      W = fb_choose(c, fb_budget(c), &sgs, false);
-      if (!W) return fb_unavailable(c, "tables do not fit the device memory budget");
-      if (setup_trace_on()) fprintf(stderr, "flexpai-trace Shoup rows: no room; factored rows at W = %d\n", W);
-    } else {
-      for (uint4* r : sgs_rows) c->fb_tables.push_back(r);
-    }
+  FbBuild b;
+  FbPlan& pl = b.pl;
+  pl = fb_plan(c);
+  if (pl.why) return fb_unavailable(c, pl.why);
+  if (pl.sgs && !sgs_reserve(c, b)) {
+    sgs_unreserve(c, b);
+    pl = fb_plan(c, false);
+    if (pl.why) return fb_unavailable(c, pl.why);
+    if (setup_trace_on()) fprintf(stderr, "flexpai-trace Shoup rows: no room; factored rows at W = %d\n", pl.W);
   }
   SetupTrace tr_all("ensure_fb");
   const auto t0 = std::chrono::steady_clock::now();
-  const size_t kb[2] = {sub(c->fb_p, HBig(1)).bits(), sub(c->fb_q, HBig(1)).bits()};
-  const int raw_bits = (int)std::max(kb[0], kb[1]) + 64;
-  if ((raw_bits + 31) / 32 > FB_RAW_MAX - 2) return fb_unavailable(c, "exponent too wide");
-  const int K = fb_digit_count(c, W);
-  const size_t RB = (size_t)LB * sb;
-  const HBig primes[2] = {c->fb_p, c->fb_q};
-  // both Garner kernels take w_q < q^2 as an operand mod p^2 (k_fb_fin: w_p + 8 p^2 - w_q > 0; k_fbp_fin:
-  // A_q, B_q < 2p): keys with q >= 2p encrypt on the generic CRT path
-  if (cmp(primes[1], shl1(primes[0])) >= 0) return fb_unavailable(c, "q >= 2p: fixed-base Garner bounds");
-  // pair products (kernels_fbp.hpp) over the S limbs of p_h (fb_pair_possible), on Shoup rows when
-  // fb_shoup_possible (kernels_fbs.hpp)
-  const int ps = grp ? 0 : fb_pair_possible(c);
-  const bool pair_ok = ps != 0;
-  const bool shoup = pair_ok && fb_shoup_possible(c);
-#if FLEXPAI_XCHECK
-  if (!grp && !pair_ok) return fb_unavailable(c, "key outside the pair sampler's bounds");
-#else
-  if (!grp && !shoup) return fb_unavailable(c, "key outside the pair sampler's bounds");
-#endif
-  // 4096-bit keys: pair products on lane groups of 4 x 19 limbs (kernels_grp_pair.hpp), R = 2^(28 76) >= 2^24 p_h
-  const bool gpair_ok = grp && fb_gpair_possible(c);
-#if FLEXPAI_XCHECK
-  if (grp && !gpair_ok) return fb_unavailable(c, "key outside the pair-group sampler's bounds");
-#else
-  if (grp && !(gpair_ok && sgp_enabled())) return fb_unavailable(c, "key outside the split-pair sampler's bounds");
-#endif
-  const int lohi_limbs = pair_ok ? std::max(sb, 2 * ps) : gpair_ok ? std::max(sb, 2 * FBGP_S) : sb;
-  FbgpHalf gv[2];
-  SgpHalf sv[2];
-  FbpHalf pv[2];
-  std::vector<uint32_t> fcst_host[2];   // Shoup rows: mu = floor(R^2 / p_h) (S + 2 limbs), R^2 mod p_h (S limbs)
-  FbHalf hv[2];
-  FbRed red[2];
-  std::memset(red, 0, sizeof(red));
-  int rc;
-  void* t[2] = {nullptr, nullptr};
-  void* lohi[2] = {nullptr, nullptr};
-  std::vector<void*> fb_scratch;   // further build scratch (freed with lohi)
-  uint32_t* gcval[2] = {nullptr, nullptr};
-  uint32_t* pcval[2] = {nullptr, nullptr};
-  // The per-half host work that needs no device -- the generator search, G = g^n mod p_h^2 (ONE powm) and the digit
-  // bases B_k by squarings in the form the resident sampler's build takes -- for both halves at once on two threads (a
-  // fresh key's setup, HE_SA_FT re-keys per exchange; round 6: the pair paths had computed G and the B_k twice)
-  struct HalfPrep {
-    uint32_t g = 0;
-    std::vector<uint32_t> bases_p;
-  };
-  HalfPrep hp[2];
-  {
-    SetupTrace tr_hp("  host prep (generator, G, B_k; both halves)");
-    auto split_into = [](const HBig& v, const HBig& P, int limbs, std::vector<uint32_t>& out) {
-      const HBig qt = div_big(v, P), rm = sub(v, mul(qt, P));
-      const std::vector<uint32_t> a = rm.limbs(limbs, LB), b = qt.limbs(limbs, LB);
-      out.insert(out.end(), a.begin(), a.end());
-      out.insert(out.end(), b.begin(), b.end());
-    };
-    auto prep = [&](int h) {
-      HalfPrep& o = hp[h];
-      o.g = c->fb_g[h] ? c->fb_g[h] : fb_base(primes[h]);
-      if (!o.g) return;
-      const HBig& m2 = sq[h];
-      HMont M2(m2);
-      const HBig G = M2.to(M2.pow(HBig(o.g), c->n));
-      // pair constants: (x mod p_h, x div p_h) of Montgomery-form values x = v R mod p_h^2: B_k R and B_k^(2^LO) R
-      const HBig& P = primes[h];
-      const int limbs = pair_ok ? ps : FBGP_S;
-      const size_t RS = (size_t)LB * limbs;
-      HBig y = G;
-      for (int k = 0; k < K; ++k) {
-        split_into(mul_pow2_mod(M2.from(y), RS, m2), P, limbs, o.bases_p);
-        split_into(mul_pow2_mod(M2.from(M2.sqr_k(y, (size_t)(W / 2))), RS, m2), P, limbs, o.bases_p);
-        y = M2.sqr_k(y, (size_t)W);
-      }
-    };
-    std::thread t1(prep, 1);
-    prep(0);
-    t1.join();
-  }
+  b.primes[0] = c->fb_p;
+  b.primes[1] = c->fb_q;
+  for (int h = 0; h < 2; ++h) b.sq[h] = mul(b.primes[h], b.primes[h]);
+  b.coef = inv_mod(b.sq[1], b.sq[0]);
+  if (b.coef.is_zero()) return fb_unavailable(c, "q^2 not invertible mod p^2");
+  fb_host_bases(c, b);
   for (int h = 0; h < 2; ++h) {
-    if (!(c->fb_g[h] = hp[h].g)) return fb_unavailable(c, "no base found");
-    SetupTrace tr_h("  host prep (one half)");
-    const HBig& m2 = sq[h];
-    const std::vector<uint32_t> bl(sb, 0u);   // FbHalf::bases: no sampler left reads them (a placeholder row)
-    // c0 folding: n 2^(CB c) mod p_h^2 (c < NC) and 2^PB p_h^2 (the group kernel uses 74's geometry:
-    // 16-bit chunks, PB = 20)
-    std::vector<uint32_t> nm;
-    const int CB = sb == 37 ? FbGeom<37>::CB : FbGeom<74>::CB, NC = sb == 37 ? FbGeom<37>::NC : FbGeom<74>::NC;
-    const int PB = sb == 37 ? FbGeom<37>::PB : FbGeom<74>::PB;
-    {
-      const HBig nmod = mod(c->n, m2);
-      for (int k = 0; k < NC; ++k) {
-        const std::vector<uint32_t> v = mul_pow2_mod(nmod, (size_t)CB * k, m2).limbs(sb, LB);
-        nm.insert(nm.end(), v.begin(), v.end());
-      }
-    }
-    uint32_t *dm, *dR2, *done, *dbases, *dlohi, *dnm, *dpbig;
-    if ((rc = upload_fb(c, m2.limbs(sb, LB), &dm)) ||
-        (rc = upload_fb(c, mul_pow2_mod(HBig(1), 2 * RB, m2).limbs(sb, LB), &dR2)) ||
-        (rc = upload_fb(c, mul_pow2_mod(HBig(1), RB, m2).limbs(sb, LB), &done)) || (rc = upload_fb(c, bl, &dbases)) ||
-        (rc = upload_fb(c, nm, &dnm)) || (rc = upload_fb(c, mul(m2, pow2(PB)).limbs(sb, LB), &dpbig)))
-      return fb_unavailable(c, pai_last_error());
-    // lo/hi half-digit tables: build scratch only, released once the table is filled
-    if (hipMalloc(&lohi[h], (size_t)K * 2 * FB_LO * lohi_limbs * 4) != hipSuccess) return fb_unavailable(c, "table allocation failed");
-    c->fb_mem.push_back(lohi[h]);
-    dlohi = (uint32_t*)lohi[h];
-    {
-      SetupTrace tr_m("  table allocation (one half)");
-      if (!(t[h] = TableArena::get().alloc(c->device, ((size_t)K << W) * (fb_table_row_words(c) / 4) * sizeof(uint4))))
-        return fb_unavailable(c, "table allocation failed");
-    }
-    c->fb_tables.push_back(t[h]);
-    hv[h] = FbHalf{(const uint4*)t[h], dm, dR2, done, dbases, dlohi, dnm, dpbig, mont_prime(m2, LB)};
-    if (pair_ok) {
-      // pair constants: (x mod p_h, x div p_h) of Montgomery-form values x = v R mod p_h^2, R = 2^(28 S)
-      const HBig& P = primes[h];
-      const size_t RS = (size_t)LB * ps;
-      auto split = [&](const HBig& v, std::vector<uint32_t>& out) {
-        const HBig qt = div_big(v, P), rm = sub(v, mul(qt, P));
-        const std::vector<uint32_t> a = rm.limbs(ps, LB), b = qt.limbs(ps, LB);
-        out.insert(out.end(), a.begin(), a.end());
-        out.insert(out.end(), b.begin(), b.end());
-      };
-      std::vector<uint32_t> one_p, nm_p;
-      const std::vector<uint32_t>& bases_p = hp[h].bases_p;   // B_k R, B_k^(2^LO) R (host prep above)
-      split(mul_pow2_mod(HBig(1), RS, m2), one_p);
-      const HBig other = primes[1 - h];
-      std::vector<uint32_t> nmr_p;   // the same times R (k_fbs: gamma R joins the b sum)
-      for (int k = 0; k < FBP_NC; ++k) {
-        const std::vector<uint32_t> v = mul_pow2_mod(mod(other, P), (size_t)FBP_CB * k, P).limbs(ps, LB);
-        nm_p.insert(nm_p.end(), v.begin(), v.end());
-        const std::vector<uint32_t> r = mul_pow2_mod(mod(other, P), (size_t)FBP_CB * k + RS, P).limbs(ps, LB);
-        nmr_p.insert(nmr_p.end(), r.begin(), r.end());
-      }
-      // position 0's lo entries are multiplied by kappa R (FbpHalf::kapR): kappa = q^-2 mod p^2 for the p half, so
-      // that the sampler leaves w_p q^-2 for k_fbp_fin; 1 for the q half
-      std::vector<uint32_t> kap_p;
-      if (h == 0) {
-        const HBig kap = inv_mod(sq[1], sq[0]);
-        if (kap.is_zero()) return fb_unavailable(c, "q^2 not invertible mod p^2");
-        split(mul_pow2_mod(kap, RS, m2), kap_p);
-      }
-      uint32_t *pp, *pone, *pbases, *pnm, *pnmr, *ppbig, *pkap = nullptr;
-      if ((rc = upload_fb(c, P.limbs(ps, LB), &pp)) || (rc = upload_fb(c, one_p, &pone)) ||
-          (rc = upload_fb(c, bases_p, &pbases)) || (rc = upload_fb(c, nm_p, &pnm)) || (rc = upload_fb(c, nmr_p, &pnmr)) ||
-          (rc = upload_fb(c, mul(P, pow2(FBP_PB)).limbs(ps, LB), &ppbig)) ||
-          (h == 0 && (rc = upload_fb(c, kap_p, &pkap))))
-        return fb_unavailable(c, pai_last_error());
-      if (h != 0) pkap = pone;
-      // factored rows (kernels_fbp.hpp): inverse tables of the lo/hi entries' A parts and the batch inversion's
-      // scratch -- released with lohi
-      void *vinv = nullptr, *vpre = nullptr, *vcv = nullptr;
-      const size_t em = (size_t)1 << (W - W / 2);
-      if (hipMalloc(&vinv, (size_t)K * 2 * FB_LO * ps * 4) != hipSuccess ||
-          (c->fb_mem.push_back(vinv), hipMalloc(&vpre, (size_t)2 * K * em * ps * 4) != hipSuccess) ||
-          (c->fb_mem.push_back(vpre), hipMalloc(&vcv, (size_t)2 * K * ps * 4) != hipSuccess))
-        return fb_unavailable(c, "table allocation failed");
-      c->fb_mem.push_back(vcv);
-      for (void* q : {vinv, vpre, vcv}) fb_scratch.push_back(q);
-      pcval[h] = (uint32_t*)vcv;
-      pv[h] = FbpHalf{(const uint4*)t[h], pp, pone, pbases, dlohi, pnm, ppbig, mont_prime(P, LB),
-                      (uint32_t*)vinv, (uint32_t*)vpre, (uint32_t*)vcv, pkap, pnmr};
-      if (shoup) {
-        const HBig R2 = pow2(2 * RS);
-        const HBig mu = div_big(R2, P);
-        if (mu.bits() > (size_t)LB * (ps + 1)) return fb_unavailable(c, "Shoup rows: mu exceeds S + 1 limbs");
-        fcst_host[h] = mu.limbs(ps + 2, LB);
-        const std::vector<uint32_t> r2 = mod(R2, P).limbs(ps, LB);
-        fcst_host[h].insert(fcst_host[h].end(), r2.begin(), r2.end());
-      }
-    }
-    if (gpair_ok) {
-      // pair-group constants: S = 76 limbs of p_h, R = 2^(28 S); pairs as [A: S][B: S]
-      const HBig& P = primes[h];
-      const size_t RS = (size_t)LB * FBGP_S;
-      auto split = [&](const HBig& v, std::vector<uint32_t>& out) {
-        const HBig qt = div_big(v, P), rm = sub(v, mul(qt, P));
-        const std::vector<uint32_t> a = rm.limbs(FBGP_S, LB), b = qt.limbs(FBGP_S, LB);
-        out.insert(out.end(), a.begin(), a.end());
-        out.insert(out.end(), b.begin(), b.end());
-      };
-      std::vector<uint32_t> one_p, nm_p;
-      const std::vector<uint32_t>& bases_p = hp[h].bases_p;
-      split(mul_pow2_mod(HBig(1), RS, m2), one_p);
-      for (int k = 0; k < 4; ++k) {
-        const std::vector<uint32_t> v = mul_pow2_mod(mod(primes[1 - h], P), (size_t)16 * k, P).limbs(FBGP_S, LB);
-        nm_p.insert(nm_p.end(), v.begin(), v.end());
-      }
-      const HBig r = mul_pow2_mod(HBig(1), RS, P);
-      const HBig X = mod(sub(add(P, HBig(1)), r), P);   // (1 - R) mod p_h
-      uint32_t *gp, *gx, *gone, *gbases, *gnm, *gpbig, *gp2, *gpr2;
-      if ((rc = upload_fb(c, P.limbs(FBGP_S, LB), &gp)) || (rc = upload_fb(c, X.limbs(FBGP_S, LB), &gx)) ||
-          (rc = upload_fb(c, one_p, &gone)) || (rc = upload_fb(c, bases_p, &gbases)) || (rc = upload_fb(c, nm_p, &gnm)) ||
-          (rc = upload_fb(c, mul(P, pow2(20)).limbs(FBGP_S, LB), &gpbig)) || (rc = upload_fb(c, m2.limbs(sb, LB), &gp2)) ||
-          (rc = upload_fb(c, mul_pow2_mod(P, RB, m2).limbs(sb, LB), &gpr2)))
-        return fb_unavailable(c, pai_last_error());
-      // factored rows (kernels_grp_pair.hpp): inverse tables of the lo/hi entries and the inversion's prefix
-      // products -- build scratch, released with lohi
-      void *vinv = nullptr, *vpre = nullptr, *vcv = nullptr;
-      const size_t em = (size_t)1 << (W - W / 2);
-      if (hipMalloc(&vinv, (size_t)K * 2 * FB_LO * FBGP_S * 4) != hipSuccess ||
-          (c->fb_mem.push_back(vinv), hipMalloc(&vpre, (size_t)2 * K * em * FBGP_S * 4) != hipSuccess) ||
-          (c->fb_mem.push_back(vpre), hipMalloc(&vcv, (size_t)2 * K * FBGP_S * 4) != hipSuccess))
-        return fb_unavailable(c, "table allocation failed");
-      c->fb_mem.push_back(vcv);
-      for (void* q : {vinv, vpre, vcv}) fb_scratch.push_back(q);
-      gcval[h] = (uint32_t*)vcv;
-      gv[h] = FbgpHalf{(const uint32_t*)t[h], gp, gx, gone, gbases, dlohi, gnm, gpbig, gp2, gpr2, mont_prime(P, LB),
-                       mont_prime(m2, LB), (uint32_t*)vinv, (uint32_t*)vpre, (uint32_t*)vcv};
-      if (sgp_enabled() &&
-          (rc = sgp_make_half(P, primes[1 - h], K, t[h],
-                              [&](const std::vector<uint32_t>& v, uint32_t** o) { return upload_fb(c, v, o); }, &sv[h])))
-        return fb_unavailable(c, pai_last_error());
-    }
-    if (h == 0) {
-      c->d_fb_m0 = dm;
-      c->fb_mprime0 = mont_prime(m2, LB);
-    }
-    // exponent reduction mod D_h = p_h - 1
-    const HBig D = sub(primes[h], HBig(1));
-    const HBig mu = div_big(pow2((size_t)raw_bits), D);
-    const std::vector<uint32_t> dw = D.words((D.bits() + 31) / 32), muw = mu.words(4);
-    std::copy(dw.begin(), dw.end(), red[h].D);
-    std::copy(muw.begin(), muw.end(), red[h].mu);
-    red[h].dwords = (int)dw.size();
-    red[h].kbits = (int)D.bits();
+    if (!(c->fb_g[h] = b.hc[h].g)) return fb_unavailable(c, "no base found");
+    if (const char* why = fb_half_consts(b, h)) return fb_unavailable(c, why);
   }
-  // Garner constants (mod p^2): 8 p^2, (q^2)^-1 R, q^2
-  const HBig coef = inv_mod(sq[1], sq[0]);
-  if (coef.is_zero()) return fb_unavailable(c, "q^2 not invertible mod p^2");
-  std::vector<FbHalf> v(hv, hv + 2);
-  std::vector<FbRed> vr(red, red + 2);
-  if ((rc = upload_fb(c, v, &c->d_fb_halves)) || (rc = upload_fb(c, vr, &c->d_fb_red)) ||
-      (rc = upload_fb(c, mul(sq[0], HBig(8)).limbs(sb, LB), &c->d_fb_m8)) ||
-      (rc = upload_fb(c, mul_pow2_mod(coef, RB, sq[0]).limbs(sb, LB), &c->d_fb_coefR)) ||
-      (rc = upload_fb(c, sq[1].limbs(sb, LB), &c->d_fb_q2)) ||
-      (grp && (rc = upload_fb(c, mul_pow2_mod(sq[1], (size_t)LB * c->S_e, c->N).limbs(c->S_e, LB), &c->d_fb_q2Rn))))
-    return fb_unavailable(c, pai_last_error());
-  const auto t1 = std::chrono::steady_clock::now();
-  if (pair_ok) {
-    std::vector<FbpHalf> pvv(pv, pv + 2);
-    if ((rc = upload_fb(c, pvv, &c->d_fbp_halves))) return fb_unavailable(c, pai_last_error());
-    if (shoup) {
-      FbsConst fc[2];
-      for (int h = 0; h < 2; ++h) {
-        uint32_t* d;
-        if ((rc = upload_fb(c, fcst_host[h], &d))) return fb_unavailable(c, pai_last_error());
-        fc[h] = FbsConst{d, d + ps + 2};
-      }
-      std::vector<FbsConst> fcv(fc, fc + 2);
-      if ((rc = upload_fb(c, fcv, &c->d_fbs_cst))) return fb_unavailable(c, pai_last_error());
-    }
-    // k_fbp_fin (kernels_fbp.hpp): (q^-1 R)^, (q^-2 R)^ as pairs over p, then q, q^2, p q^2, 2p, 3p
-    const HBig &P = primes[0], &Q = primes[1];
-    const size_t RS = (size_t)LB * ps;
-    std::vector<uint32_t> cs;
-    auto put = [&](const HBig& v, int limbs) {
-      const std::vector<uint32_t> l = v.limbs(limbs, LB);
-      cs.insert(cs.end(), l.begin(), l.end());
-    };
-    auto put_pair = [&](const HBig& v) {   // v mod p^2 -> (v mod p, v div p)
-      const HBig qt = div_big(v, P);
-      put(sub(v, mul(qt, P)), ps);
-      put(qt, ps);
-    };
-    const HBig qinv = inv_mod(mod(Q, sq[0]), sq[0]);
-    if (qinv.is_zero()) return fb_unavailable(c, "q not invertible mod p^2");
-    put_pair(mul_pow2_mod(qinv, RS, sq[0]));
-    put_pair(mul_pow2_mod(coef, RS, sq[0]));
-    put(Q, ps);
-    put(sq[1], 2 * ps);
-    put(mul(P, sq[1]), 3 * ps);
-    put(mul(P, HBig(2)), ps);
-    put(mul(P, HBig(3)), ps);
-    if ((rc = upload_fb(c, cs, &c->d_fbp_fin_cs))) return fb_unavailable(c, pai_last_error());
-    c->d_fbp_fin_p = const_cast<uint32_t*>(pv[0].p);
-    c->fbp_fin_mprime = pv[0].mprime;
-  }
-  if (gpair_ok) {
-    std::vector<FbgpHalf> gvv(gv, gv + 2);
-    if ((rc = upload_fb(c, gvv, &c->d_fbgp_halves))) return fb_unavailable(c, pai_last_error());
-    if (sgp_enabled()) {
-      std::vector<SgpHalf> svv(sv, sv + 2);
-      if ((rc = upload_fb(c, svv, &c->d_sgp_fb))) return fb_unavailable(c, pai_last_error());
-      c->d_sgp_q = sv[1].p;
-    }
-  }
-  trace_uploads("  fb uploads");
-  if (gpair_ok || pair_ok) {   // factored rows: the chain products are inverted on the host between the two phases
-    SetupTrace tr_1("  phase 1 (lohi, inv_fwd) + host invert");
-    const hipError_t e1 = gpair_ok ? fbgp_build_phase1(c->d_fbgp_halves, K, W, nullptr)
-                                   : fbp_build_phase1(ps, c->d_fbp_halves, K, W, nullptr);
-    if (e1 != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fb_unavailable(c, "table construction failed");
-    for (int h = 0; h < 2; ++h)
-      if (pair_host_invert(primes[h], gpair_ok ? gcval[h] : pcval[h], 2 * K, gpair_ok ? FBGP_S : ps))
-        return fb_unavailable(c, pai_last_error());
-  }
-  SetupTrace tr_2("  phase 2 (inv_bwd, fill) + frees");
-#if FLEXPAI_XCHECK
-  const hipError_t be = gpair_ok ? fbgp_build_phase2(c->d_fbgp_halves, (uint32_t*)t[0], (uint32_t*)t[1], K, W, nullptr)
-                        : shoup  ? fbs_build_phase2(ps, c->d_fbp_halves, c->d_fbs_cst, (uint4*)t[0], (uint4*)t[1], K, W, nullptr,
-                                                    guard_args(c, (unsigned long long)K << W, 0, 0, 0))
-                                 : fbp_build_phase2(ps, c->d_fbp_halves, (uint4*)t[0], (uint4*)t[1], K, W, nullptr);
-#else
-  const hipError_t be = gpair_ok ? fbgp_build_phase2(c->d_fbgp_halves, (uint32_t*)t[0], (uint32_t*)t[1], K, W, nullptr)
-                                 : fbs_build_phase2(ps, c->d_fbp_halves, c->d_fbs_cst, (uint4*)t[0], (uint4*)t[1], K, W, nullptr,
-                                                    guard_args(c, (unsigned long long)K << W, 0, 0, 0));
-#endif
-  if (be != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-    return fb_unavailable(c, "table construction failed");
-  if (guard_collect(c, nullptr)) return fb_unavailable(c, pai_last_error());
-  for (void* p : lohi) fb_scratch.push_back(p);
-  SetupTrace tr_f("  scratch frees");
-  for (void* p : fb_scratch) {
-    c->fb_mem.erase(std::find(c->fb_mem.begin(), c->fb_mem.end(), p));
-    (void)hipFree(p);
-  }
-  if (sgs && !(gpair_ok && sgp_enabled())) {   // (a test build's $FLEXPAI_SGP=0 context)
-    for (uint4*& r : sgs_rows) {
-      c->fb_tables.erase(std::find(c->fb_tables.begin(), c->fb_tables.end(), (void*)r));
-      TableArena::get().free(r);
-      r = nullptr;
-    }
-  }
-  if (gpair_ok && sgp_enabled() && sgs) {
+  if (fb_upload_halves(c, b)) return fb_unavailable(c, pai_last_error());
+  const auto t1 = std::chrono::steady_clock::now();   // fb_host_ms | fb_dev_ms
+  if (fb_upload_sampler(c, b) || fb_build_rows(c, b)) return fb_unavailable(c, pai_last_error());
+  if (pl.sgs) {
     SetupTrace tr_s("  Shoup rows (k_sgs_conv)");
-    if ((rc = sgs_build(c, primes, K, W, t, sv, sgs_rows))) {
+    if (sgs_build(c, b.primes, pl.K, pl.W, b.t, b.sv, b.sgs_rows)) {
       // the factored rows are complete: k_sgp runs on them (split_sampler bit 3 stays clear)
-      if (setup_trace_on()) fprintf(stderr, "flexpai-trace Shoup rows failed (%s): k_sgp at W = %d\n", pai_last_error(), W);
-      for (uint4*& r : sgs_rows) {
-        c->fb_tables.erase(std::find(c->fb_tables.begin(), c->fb_tables.end(), (void*)r));
-        TableArena::get().free(r);
-        r = nullptr;
-      }
+      if (setup_trace_on()) fprintf(stderr, "flexpai-trace Shoup rows failed (%s): k_sgp at W = %d\n", pai_last_error(), pl.W);
+      sgs_unreserve(c, b);
     }
   }
   const auto t2 = std::chrono::steady_clock::now();
-  c->fb_host_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
-  c->fb_dev_ms = std::chrono::duration<float, std::milli>(t2 - t1).count();
-  c->fb_table_bytes = fb_bytes(c, W, c->d_sgs_fb != nullptr);
-  c->fb_K = K;
-  c->fb_pair_s = pair_ok ? ps : 0;
-  c->fb_shoup = shoup;
-  c->fb_gpair = gpair_ok;
-  c->fb_W_used = W;
-  c->fb_raw_bits = raw_bits;
+  FbTables& fb = c->fb;
+  fb.host_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+  fb.dev_ms = std::chrono::duration<float, std::milli>(t2 - t1).count();
+  fb.table_bytes = fb_bytes(c, pl.W, fb.d_sgs != nullptr);
+  fb.K = pl.K;
+  fb.W_used = pl.W;
+  fb.raw_bits = pl.raw_bits;
+  fb.pair_s = pl.ps;
+  fb.shoup = pl.shoup;
+  fb.gpair = pl.gpair;
   c->fb_state = pai_ctx::FB_READY;
   return 1;
 }
@@ -1806,12 +1803,6 @@ static int setup_fbg(pai_ctx* c, const HBig& p, const HBig& q) {
     for (int h = 0; h < 2; ++h) {
       const HBig& ph = primes[h];
       const HBig m2 = mul(ph, ph);
-      auto split = [&](const HBig& v) {
-        const HBig qt = div_big(v, ph), rm = sub(v, mul(qt, ph));
-        std::vector<uint32_t> out = rm.limbs(D4_S, LB), b = qt.limbs(D4_S, LB);
-        out.insert(out.end(), b.begin(), b.end());
-        return out;
-      };
       auto one_minus = [&](const HBig& r) {   // (1 - r) mod p_h for 0 < r < p_h
         return mod(sub(add(ph, HBig(1)), r), ph);
       };
@@ -1824,7 +1815,7 @@ static int setup_fbg(pai_ctx* c, const HBig& p, const HBig& q) {
       if ((rc = upload(c, ph.limbs(D4_S, LB), &dp)) ||
           (rc = upload(c, one_minus(mul_pow2_mod(HBig(1), RS, ph)).limbs(D4_S, LB), &dx1)) ||
           (rc = upload(c, one_minus(mul_pow2_mod(HBig(1), RS * kp, ph)).limbs(D4_S, LB), &dxk)) ||
-          (rc = upload(c, split(mul_pow2_mod(HBig(1), RS * (kp + 1), m2)), &dck)) ||
+          (rc = upload(c, pair_split(mul_pow2_mod(HBig(1), RS * (kp + 1), m2), ph, D4_S), &dck)) ||
           (rc = upload(c, mul_pow2_mod(hh, RS, ph).limbs(D4_S, LB), &dhr)) || (rc = upload(c, pd, &dprog)) ||
           (rc = upload(c, kf, &dkf)))
         return rc;
@@ -2025,12 +2016,6 @@ static int setup_crt(pai_ctx* c, const HBig& p, const HBig& q) {
   if (pair && (size_t)LB * sa >= pb + 12) {
     SetupTrace tr_p("    pair consts");
     const int S2 = 2 * sa;
-    auto split = [&](const HBig& v, const HBig& P) {   // canonical pair of v < P^2
-      const HBig qt = div_big(v, P), rm = sub(v, mul(qt, P));
-      std::vector<uint32_t> out = rm.limbs(sa, LB), b = qt.limbs(sa, LB);
-      out.insert(out.end(), b.begin(), b.end());
-      return out;
-    };
     const int kp = (int)((32 * (size_t)c->ct_words + RA - 1) / RA);
     std::vector<uint32_t> one(S2, 0);
     one[0] = 1;
@@ -2052,11 +2037,11 @@ static int setup_crt(pai_ctx* c, const HBig& p, const HBig& q) {
       const uint32_t mp1 = mont_prime(ph, LB);
       uint32_t *dph, *dck, *dhR, *dpm1, *done, *dprog, *dr2, *dcoef, *dpe, *dkf = nullptr;
       if ((rc = upload(c, ph.limbs(sa, LB), &dph)) ||
-          (rc = upload(c, split(mul_pow2_mod(HBig(1), RA * (kp + 1), m2), ph), &dck)) ||
+          (rc = upload(c, pair_split(mul_pow2_mod(HBig(1), RA * (kp + 1), m2), ph, sa), &dck)) ||
           (rc = upload(c, mul_pow2_mod(sub(ph, oi), RA, ph).limbs(sa, LB), &dhR)) ||
           (rc = upload(c, sub(ph, HBig(1)).limbs(sa, LB), &dpm1)) || (rc = upload(c, one, &done)) ||
-          (rc = upload(c, pd, &dprog)) || (rc = upload(c, split(mul_pow2_mod(HBig(1), 2 * RA, m2), ph), &dr2)) ||
-          (rc = upload(c, split(coef, ph), &dcoef)) || (rc = upload(c, pe, &dpe)) ||
+          (rc = upload(c, pd, &dprog)) || (rc = upload(c, pair_split(mul_pow2_mod(HBig(1), 2 * RA, m2), ph, sa), &dr2)) ||
+          (rc = upload(c, pair_split(coef, ph, sa), &dcoef)) || (rc = upload(c, pe, &dpe)) ||
           (!kf.empty() && (rc = upload(c, kf, &dkf))))
         return rc;
       dp[h] = DecPairHalf{dph, dck, dhR, dpm1, mp1, 0u};
@@ -2207,7 +2192,7 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       if (value == c->pfb_W) return 0;
       c->pfb_W = value;
       HIPCHK(hipSetDevice(c->device));
-      pfb_release(c);
+      c->pfb.release();
       c->pfb_state = pai_ctx::FB_UNTRIED;
       return 0;
     case PAI_OPT_FB_WINDOW:
@@ -2215,7 +2200,7 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       if (value == c->fb_W) return 0;
       c->fb_W = value;
       HIPCHK(hipSetDevice(c->device));
-      fb_release(c);                       // rebuilt lazily for the new window
+      c->fb.release();                       // rebuilt lazily for the new window
       c->fb_state = pai_ctx::FB_UNTRIED;
       return 0;
   }
@@ -2239,21 +2224,21 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_FIXED_BASE:
       *value = ((c->crt_ok || c->fbg_ok) && c->fb_enabled && c->fb_state != pai_ctx::FB_UNAVAILABLE) ? 1 : 0;
       return 0;
-    case PAI_OPT_FB_WINDOW: *value = c->fb_W_used ? c->fb_W_used : c->fb_W ? c->fb_W : fb_default_window(); return 0;
+    case PAI_OPT_FB_WINDOW: *value = c->fb.W_used ? c->fb.W_used : c->fb_W ? c->fb_W : fb_default_window(); return 0;
     case PAI_OPT_FB_READY: *value = c->fb_state == pai_ctx::FB_READY ? 1 : 0; return 0;
     case PAI_OPT_PUBLIC_FB:
       *value = (pfb_supported(c) && c->pfb_enabled && c->pfb_state != pai_ctx::FB_UNAVAILABLE) ? 1 : 0;
       return 0;
     case PAI_OPT_PFB_READY: *value = c->pfb_state == pai_ctx::FB_READY ? 1 : 0; return 0;
-    case PAI_OPT_PFB_WINDOW: *value = c->pfb_W_used ? c->pfb_W_used : c->pfb_W ? c->pfb_W : pfb_default_window(); return 0;
+    case PAI_OPT_PFB_WINDOW: *value = c->pfb.W_used ? c->pfb.W_used : c->pfb_W ? c->pfb_W : pfb_default_window(); return 0;
     case PAI_OPT_FB_PAIR:
-      *value = c->fb_state == pai_ctx::FB_READY ? (c->fb_gpair ? FBGP_S : c->fb_pair_s) : 0;
+      *value = c->fb_state == pai_ctx::FB_READY ? (c->fb.gpair ? FBGP_S : c->fb.pair_s) : 0;
       return 0;
     case PAI_OPT_SPLIT_SAMPLER:
-      *value = (c->fb_state == pai_ctx::FB_READY && c->d_sgp_fb ? 1 : 0) |
-               (c->pfb_state == pai_ctx::FB_READY && c->d_sgp_pfb ? 2 : 0) |
-               (c->fb_state == pai_ctx::FB_READY && c->fb_shoup ? 4 : 0) |
-               (c->fb_state == pai_ctx::FB_READY && c->d_sgs_fb ? 8 : 0);
+      *value = (c->fb_state == pai_ctx::FB_READY && c->fb.d_sgp ? 1 : 0) |
+               (c->pfb_state == pai_ctx::FB_READY && c->pfb.d_sgp ? 2 : 0) |
+               (c->fb_state == pai_ctx::FB_READY && c->fb.shoup ? 4 : 0) |
+               (c->fb_state == pai_ctx::FB_READY && c->fb.d_sgs ? 8 : 0);
       return 0;
     case PAI_OPT_PAIR:
       *value = ((c->dec_pair_ok || c->dec4_ok) && c->dec_lane_enabled ? 1 : 0) | (c->crt_pair_ok ? 2 : 0) |
@@ -2292,8 +2277,8 @@ int pai_ctx_fixed_base_info(pai_ctx* c, uint32_t* g_p, uint32_t* g_q, int* digit
   if (!ensure_fb((pai_ctx*)c)) return fail(PAI_ERR_KEY, "fixed-base obfuscation not available: " + c->fb_reason);
   if (g_p) *g_p = c->fb_g[0];
   if (g_q) *g_q = c->fb_g[1];
-  if (digits) *digits = c->fb_K;
-  if (window) *window = c->fb_W_used;
+  if (digits) *digits = c->fb.K;
+  if (window) *window = c->fb.W_used;
   return 0;
 }
 
@@ -2310,13 +2295,9 @@ int pai_ctx_fixed_base_prepare(pai_ctx* c) {
 // The window ensure_fb would choose and its break-even element count (0 when the tables are resident or
 // the path is unavailable: nothing left to decide).
 static long long fb_threshold(pai_ctx* c) {
-  if (c->fb_state != pai_ctx::FB_UNTRIED || (!c->crt_ok && !c->fbg_ok)) return 0;
-  const int TW = fb_row_words(c);
-  if (!TW) return 0;
-  if (!c->fb_W) c->fb_W = fb_default_window();
-  bool sgs = false;
-  const int w = fb_choose(c, fb_budget(c), &sgs);
-  return w ? fb_break_even(c, w, fb_digit_count(c, w), 4 * fb_table_row_words(c) + (sgs ? 16 * SGS_ROW_Q : 0)) : 0;
+  if (c->fb_state != pai_ctx::FB_UNTRIED) return 0;
+  const FbPlan pl = fb_plan(c);
+  return pl.W ? fb_break_even(c, pl.W, pl.K, 4 * pl.row_words + (pl.sgs ? 16 * SGS_ROW_Q : 0)) : 0;
 }
 
 static bool fb_wanted(pai_ctx* c, long long n) {
@@ -2338,9 +2319,9 @@ int pai_ctx_fixed_base_setup(const pai_ctx* c, float* host_ms, float* device_ms,
   if (!c) return fail(PAI_ERR_ARG, "null ctx");
   CtxLock lk(c);
   if (c->fb_state != pai_ctx::FB_READY) return fail(PAI_ERR_KEY, "fixed-base tables are not resident");
-  if (host_ms) *host_ms = c->fb_host_ms;
-  if (device_ms) *device_ms = c->fb_dev_ms;
-  if (table_bytes) *table_bytes = c->fb_table_bytes;
+  if (host_ms) *host_ms = c->fb.host_ms;
+  if (device_ms) *device_ms = c->fb.dev_ms;
+  if (table_bytes) *table_bytes = c->fb.table_bytes;
   return 0;
 }
 
@@ -2461,27 +2442,27 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
   const bool grp = SB == GRP_TPI * L;
   const long long N = e.n;
   const long long chunk = std::min(N, CRT_CHUNK);
-  int occF = 1, occG = 1;
+  const int K = c->fb.K, W = c->fb.W_used;
+  int occF = 1;
 #if FLEXPAI_XCHECK
-  if (grp && !c->fb_gpair) return fail(PAI_ERR_KEY, "fixed-base encrypt: no pair tables");
-  if (grp && !c->d_sgp_fb) fbgp_occupancy(&occF);
-  if (!grp && !c->fb_pair_s) return fail(PAI_ERR_KEY, "fixed-base encrypt: no pair tables");
+  if (grp && !c->fb.gpair) return fail(PAI_ERR_KEY, "fixed-base encrypt: no pair tables");
+  if (grp && !c->fb.d_sgp) fbgp_occupancy(&occF);
+  if (!grp && !c->fb.pair_s) return fail(PAI_ERR_KEY, "fixed-base encrypt: no pair tables");
 #else
-  if (grp && !(c->fb_gpair && c->d_sgp_fb)) return fail(PAI_ERR_KEY, "fixed-base encrypt: no split-pair tables");
-  if (!grp && !c->fb_shoup) return fail(PAI_ERR_KEY, "fixed-base encrypt: no Shoup tables");
+  if (grp && !(c->fb.gpair && c->fb.d_sgp)) return fail(PAI_ERR_KEY, "fixed-base encrypt: no split-pair tables");
+  if (!grp && !c->fb.shoup) return fail(PAI_ERR_KEY, "fixed-base encrypt: no Shoup tables");
 #endif
 #if FLEXPAI_XCHECK
-  if (c->fb_pair_s && !c->fb_shoup && fbp_occupancy(c->fb_pair_s, &occF)) return fail(PAI_ERR_KEY, "fixed-base encrypt: unsupported size");
+  if (c->fb.pair_s && !c->fb.shoup && fbp_occupancy(c->fb.pair_s, &occF)) return fail(PAI_ERR_KEY, "fixed-base encrypt: unsupported size");
 #endif
-  if (c->fb_shoup && fbs_occupancy(c->fb_pair_s, &occF)) return fail(PAI_ERR_KEY, "fixed-base encrypt: unsupported size");
+  if (c->fb.shoup && fbs_occupancy(c->fb.pair_s, &occF)) return fail(PAI_ERR_KEY, "fixed-base encrypt: unsupported size");
   // elements per block: one per lane, one per lane pair (k_fbs), or one per lane group (grp)
-  const int EPB = grp ? BLOCK / GRP_TPI : c->fb_shoup ? LANE_BLOCK / 2 : LANE_BLOCK;
+  const int EPB = grp ? BLOCK / GRP_TPI : c->fb.shoup ? LANE_BLOCK / 2 : LANE_BLOCK;
   const long long lane_blocks = (chunk + EPB - 1) / EPB;
   const int gxF = (int)std::max<long long>(1, std::min<long long>(lane_blocks, (long long)occF * c->cus / 2));
-  const int gxG = (int)std::max<long long>(1, std::min<long long>(lane_blocks, (long long)occG * c->cus));
-  const size_t dbytes = (size_t)2 * c->fb_K * 4, wbytes = (size_t)2 * std::max(SB, 2 * c->fb_pair_s) * 4;   // per element
+  const size_t dbytes = (size_t)2 * K * 4, wbytes = (size_t)2 * std::max(SB, 2 * c->fb.pair_s) * 4;   // per element
   int rc;
-  const size_t sbytes = c->d_sgs_fb ? (size_t)2 * (16 * sizeof(uint4) + 2 * 4) : 0;   // k_sgs's b sums
+  const size_t sbytes = c->fb.d_sgs ? (size_t)2 * (16 * sizeof(uint4) + 2 * 4) : 0;   // k_sgs's b sums
   if ((rc = ensure_work(c, dbytes * chunk + wbytes * (size_t)fbp_npad(chunk) + sbytes * chunk))) return rc;   // pairs: 64-element tiles
   uint32_t* digits = (uint32_t*)c->d_work;
   uint32_t* w = (uint32_t*)((char*)c->d_work + dbytes * chunk);
@@ -2498,50 +2479,41 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
     pd.n = n;
     std::memcpy(pd.rng_key, sl.rnd.rng_key, sizeof(pd.rng_key));
     pd.index_base = sl.rnd.index_base;
-    pd.K = c->fb_K;
-    pd.W = c->fb_W_used;
-    pd.raw_bits = c->fb_raw_bits;
-    pd.red = c->d_fb_red;
+    pd.K = K;
+    pd.W = W;
+    pd.raw_bits = c->fb.raw_bits;
+    pd.red = c->fb.d_red;
     pd.digits = digits;
-    const unsigned long long dig_words = (unsigned long long)2 * c->fb_K * chunk, w_words = wbytes * (size_t)fbp_npad(chunk) / 4;
+    const unsigned long long dig_words = (unsigned long long)2 * K * chunk, w_words = wbytes * (size_t)fbp_npad(chunk) / 4;
     pd.g = guard_args(c, 0, dig_words, 0, 0);
     const int gD = (int)std::min<long long>((long long)8 * c->cus, (n + FB_DIG_BLOCK - 1) / FB_DIG_BLOCK);
     stage_mark(c, 0, st);
     HIPCHK(fb_launch_digits(pd, gD, st));
     stage_mark(c, 1, st);
-    FbParams pf{};
-    pf.halves = c->d_fb_halves;
-    pf.n = n;
-    pf.K = c->fb_K;
-    pf.W = c->fb_W_used;
-    pf.digits = digits;
-    pf.out = w;
-    pf.src = sl.src;
-    pf.dst = sl.dst;
     const int gF = (int)std::min<long long>(gxF, (n + EPB - 1) / EPB);
-    if (c->fb_pair_s) {
-      FbpParams pp{c->d_fbp_halves, n, pf.K, pf.W, digits, w, sl.src, sl.dst};
-      pp.g = guard_args(c, (unsigned long long)pf.K << pf.W, dig_words, w_words, 0);
+    const FbgpParams pg{c->fb.d_fbgp, n, K, W, digits, w, sl.src, sl.dst};   // the test build's k_fbgp, and k_fbgp_w
+    if (c->fb.pair_s) {
+      FbpParams pp{c->fb.d_fbp, n, K, W, digits, w, sl.src, sl.dst};
+      pp.g = guard_args(c, (unsigned long long)K << W, dig_words, w_words, 0);
 #if FLEXPAI_XCHECK
-      if (!c->fb_shoup) HIPCHK(fbp_launch(c->fb_pair_s, pp, gF, st));
+      if (!c->fb.shoup) HIPCHK(fbp_launch(c->fb.pair_s, pp, gF, st));
 #endif
-      if (c->fb_shoup) HIPCHK(fbs_launch(c->fb_pair_s, pp, gF, st));
-    } else if (grp && c->fb_gpair) {
-      const FbgpParams pg{c->d_fbgp_halves, n, pf.K, pf.W, digits, w, sl.src, sl.dst};
-      if (c->d_sgs_fb) {   // split pairs on Shoup rows (kernels_sgs.hpp), then the b sums applied
+      if (c->fb.shoup) HIPCHK(fbs_launch(c->fb.pair_s, pp, gF, st));
+    } else if (grp && c->fb.gpair) {
+      if (c->fb.d_sgs) {   // split pairs on Shoup rows (kernels_sgs.hpp), then the b sums applied
         int occS = 1;
         sgs_occupancy(&occS);
-        SgsParams sp{c->d_sgs_fb, n, pf.K, pf.W, digits, w, sgs_bsum, sgs_bcc};
-        sp.g = guard_args(c, (unsigned long long)pf.K << pf.W, dig_words, w_words, 0);
+        SgsParams sp{c->fb.d_sgs, n, K, W, digits, w, sgs_bsum, sgs_bcc};
+        sp.g = guard_args(c, (unsigned long long)K << W, dig_words, w_words, 0);
         const long long nb = (n + SGP_PAIRS - 1) / SGP_PAIRS;
         HIPCHK(sgs_launch(sp, (int)std::max<long long>(1, std::min<long long>(nb, (long long)occS * c->cus / 2)), 2, st));
-        const SgsFinParams sf{c->d_sgs_fb, n, w, sgs_bsum, sgs_bcc, sl.src, sl.dst.exp, sl.dst.status, dbg_stage};
+        const SgsFinParams sf{c->fb.d_sgs, n, w, sgs_bsum, sgs_bcc, sl.src, sl.dst.exp, sl.dst.status, dbg_stage};
         if (dbg_stage != 1) HIPCHK(sgs_launch_bfin(sf, 2, c->cus, st));
-      } else if (c->d_sgp_fb) {   // split pairs (kernels_sgp.hpp): SGP_PAIRS elements per block, grid (gx, 2)
+      } else if (c->fb.d_sgp) {   // split pairs (kernels_sgp.hpp): SGP_PAIRS elements per block, grid (gx, 2)
         int occS = 1;
         sgp_occupancy(&occS);
-        SgpParams sp{c->d_sgp_fb, n, pf.K, pf.W, digits, w, sl.src, sl.dst};
-        sp.g = guard_args(c, (unsigned long long)pf.K << pf.W, dig_words, w_words, 0);
+        SgpParams sp{c->fb.d_sgp, n, K, W, digits, w, sl.src, sl.dst};
+        sp.g = guard_args(c, (unsigned long long)K << W, dig_words, w_words, 0);
         const long long nb = (n + SGP_PAIRS - 1) / SGP_PAIRS;
         HIPCHK(sgp_launch(sp, (int)std::max<long long>(1, std::min<long long>(nb, (long long)occS * c->cus / 2)), 2, st));
       } else {
@@ -2557,44 +2529,42 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
     if (grp) {   // w_h = c0 G_h^(a_h) mod p_h^2 -> Garner: h mod p^2 (S = 148), c = w_q + q^2 h mod n^2 (S = 296)
       int occH = 1, occC = 1;
       grp_fin_occupancy(&occH, &occC);
-      if (c->fb_gpair && c->d_sgp_fb) {   // the pairs -> w_h = A + p_h B mod p_h^2 (timed with the fin stage)
+      if (c->fb.gpair && c->fb.d_sgp) {   // the pairs -> w_h = A + p_h B mod p_h^2 (timed with the fin stage)
         SgpParams sw{};
-        sw.halves = c->d_sgp_fb;
+        sw.halves = c->fb.d_sgp;
         sw.n = n;
         sw.out = w;
         HIPCHK(sgp_launch_w(sw, 2, c->cus, st));
-      } else if (c->fb_gpair) {
-        const FbgpParams pg{c->d_fbgp_halves, n, pf.K, pf.W, digits, w, sl.src, sl.dst};
+      } else if (c->fb.gpair) {
         const long long gb4 = (n + BLOCK / 4 - 1) / (BLOCK / 4);
         HIPCHK(fbgp_launch_w(pg, (int)std::max<long long>(1, std::min<long long>(gb4, (long long)occH * c->cus / 2)), st));
       }
       const long long gb4 = (n + BLOCK / GRP_TPI - 1) / (BLOCK / GRP_TPI), gb8 = (n + BLOCK / 8 - 1) / (BLOCK / 8);
-      FbgGarnerParams gh{w, n, c->d_fb_m0, c->d_fb_m8, c->d_fb_coefR, c->fb_mprime0};
+      FbgGarnerParams gh{w, n, c->fb.d_m0, c->fb.d_m8, c->fb.d_coefR, c->fb.mprime0};
       HIPCHK(grp_launch_garner(gh, (int)std::max<long long>(1, std::min<long long>(gb4, (long long)occH * c->cus)), st));
       // c = w_q + q^2 h on lanes (kernels_sgp.hpp k_sgp_fin): its intermediates' top 2S rows go to the digit buffer
       // (2K rows, dead by now; K >= S at every window the ladder has)
-      if (c->d_sgp_q && c->ct_words == SGPF_CT_WORDS && pf.K >= SGP_S && sgp_fin_enabled()) {
-        const SgpFinParams sf{w, digits, n, c->d_sgp_q, sl.dst.ct, c->ct_words};
+      if (c->fb.d_sgp_q && c->ct_words == SGPF_CT_WORDS && K >= SGP_S && sgp_fin_enabled()) {
+        const SgpFinParams sf{w, digits, n, c->fb.d_sgp_q, sl.dst.ct, c->ct_words};
         HIPCHK(sgp_launch_fin(sf, c->cus, st));
       } else {
-        FbgFinParams gf{w, SB, n, c->d_N, c->d_fb_q2Rn, c->mprime_N, sl.dst.ct, c->ct_words};
+        FbgFinParams gf{w, SB, n, c->d_N, c->fb.d_q2Rn, c->mprime_N, sl.dst.ct, c->ct_words};
         HIPCHK(grp_launch_fin(gf, (int)std::max<long long>(1, std::min<long long>(gb8, (long long)occC * c->cus)), st));
       }
       stage_mark(c, 3, st);
       continue;
     }
-    if (c->fb_pair_s) {   // Garner on pairs (kernels_fbp.hpp)
+    if (c->fb.pair_s) {   // Garner on pairs (kernels_fbp.hpp)
       int occP = 1;
-      fbp_fin_occupancy(c->fb_pair_s, &occP);
-      FbpFinParams pp{w, n, c->d_fbp_fin_p, c->d_fbp_fin_cs, c->fbp_fin_mprime, sl.dst.ct,
+      fbp_fin_occupancy(c->fb.pair_s, &occP);
+      FbpFinParams pp{w, n, c->fb.d_fbp_fin_p, c->fb.d_fbp_fin_cs, c->fb.fbp_fin_mprime, sl.dst.ct,
                       c->ct_words};
       pp.g = guard_args(c, 0, 0, (unsigned long long)n * c->ct_words, w_words);
       const long long nb = (n + LANE_BLOCK - 1) / LANE_BLOCK;
-      HIPCHK(fbp_launch_fin(c->fb_pair_s, pp, (int)std::max<long long>(1, std::min<long long>(nb, (long long)occP * c->cus)), st));
+      HIPCHK(fbp_launch_fin(c->fb.pair_s, pp, (int)std::max<long long>(1, std::min<long long>(nb, (long long)occP * c->cus)), st));
       stage_mark(c, 3, st);
       continue;
     }
-    (void)gxG;
   }
   return 0;
 }
@@ -2626,30 +2596,11 @@ static int pfb_choose_window(pai_ctx* c) {
   return 0;
 }
 
-static void pfb_release(pai_ctx* c) {
-  for (void* q : c->pfb_mem) (void)hipFree(q);
-  c->pfb_mem.clear();
-  for (void* q : c->pfb_tables) TableArena::get().free(q);
-  c->pfb_tables.clear();
-  c->d_pfb = nullptr;
-  c->d_sgp_pfb = nullptr;
-}
-
 static int pfb_unavailable(pai_ctx* c, const std::string& why) {
-  pfb_release(c);
+  c->pfb.release();
   (void)hipGetLastError();
   c->pfb_state = pai_ctx::FB_UNAVAILABLE;
   c->pfb_reason = why;
-  return 0;
-}
-
-template <typename T>
-static int upload_pfb(pai_ctx* c, const std::vector<T>& v, T** out) {
-  void* q = nullptr;
-  HIPCHK(hipMalloc(&q, std::max<size_t>(v.size(), 1) * sizeof(T)));
-  c->pfb_mem.push_back(q);
-  if (!v.empty()) HIPCHK(hipMemcpy(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = (T*)q;
   return 0;
 }
 
@@ -2695,79 +2646,50 @@ static bool random_below(const HBig& n, HBig* out) {
   return false;
 }
 
-static int ensure_pfb(pai_ctx* c) {
-  if (c->pfb_state == pai_ctx::FB_READY) return 1;
-  if (c->pfb_state == pai_ctx::FB_UNAVAILABLE) return 0;
-  if (!pfb_supported(c)) return pfb_unavailable(c, "the public fixed-base kernels need a 1537..2048-bit n");
-  const int W = pfb_choose_window(c);
-  if (!W) return pfb_unavailable(c, "tables do not fit the device memory budget");
-  SetupTrace tr_all("ensure_pfb");
-  const auto t0 = std::chrono::steady_clock::now();
-  int K0, KS;
-  pfb_digit_counts(c, W, &K0, &KS);
-  const int K = K0 + PFB_SHORT * KS;
-  const HBig& n = c->n;
-  std::optional<SetupTrace> tr_h(std::in_place, "  pfb host prep (bases, constants)");
-  if (c->pfb_bases.empty()) {
-    HBig g;
-    do {
-      if (!random_below(n, &g)) return pfb_unavailable(c, "no randomness for the bases");
-    } while (jacobi(g, n) != -1);   // g_0: Jacobi symbol -1, so the publicly visible symbol of c mod n is uniform
-    c->pfb_bases.push_back(g);
-    for (int j = 0; j < PFB_SHORT; ++j) {
-      if (!random_below(n, &g)) return pfb_unavailable(c, "no randomness for the bases");
-      c->pfb_bases.push_back(g);
-    }
+// g_0 with Jacobi symbol -1 (so that the publicly visible symbol of c mod n is uniform) and PFB_SHORT further bases,
+// unless the caller set them (pai_ctx_public_fb_set_bases)
+static bool pfb_draw_bases(pai_ctx* c) {
+  if (!c->pfb_bases.empty()) return true;
+  std::vector<HBig> bs;
+  HBig g;
+  do {
+    if (!random_below(c->n, &g)) return false;
+  } while (jacobi(g, c->n) != -1);
+  bs.push_back(g);
+  for (int j = 0; j < PFB_SHORT; ++j) {
+    if (!random_below(c->n, &g)) return false;
+    bs.push_back(g);
   }
-  const HBig& n2 = c->N;
+  c->pfb_bases = bs;
+  return true;
+}
+
+// The public tables' constants, scratch and table on the device (the modulus is n: one "half" of the pair-group builder)
+static int pfb_upload(pai_ctx* c, int W, int K0, int KS, RowScratch& sc, uint4** table) {
+  SetupTrace tr_m("  pfb uploads + hipMalloc");
+  const HBig &n = c->n, &n2 = c->N;
   const size_t RS = (size_t)LB * PFB_S;
-  auto split = [&](const HBig& v) {   // v < n^2 -> [v mod n: S limbs][v div n: S limbs]
-    const HBig qt = div_big(v, n), rm = sub(v, mul(qt, n));
-    std::vector<uint32_t> out = rm.limbs(PFB_S, LB), b = qt.limbs(PFB_S, LB);
-    out.insert(out.end(), b.begin(), b.end());
-    return out;
-  };
+  const int K = K0 + PFB_SHORT * KS;
+  PfbTables& pfb = c->pfb;
   const HBig oneR = mul_pow2_mod(HBig(1), RS, n2);
-  const HBig R2 = mul_pow2_mod(oneR, RS, n2);
   const HBig X = mod(sub(add(n, HBig(1)), mul_pow2_mod(HBig(1), RS, n)), n);   // (1 - R) mod n
   std::vector<uint32_t> gl;
-  for (const HBig& g : c->pfb_bases) {
-    const std::vector<uint32_t> v = g.limbs(PFB_S, LB);
-    gl.insert(gl.end(), v.begin(), v.end());
-  }
-  tr_h.reset();
-  pfb_release(c);
-  std::optional<SetupTrace> tr_m(std::in_place, "  pfb uploads + hipMalloc");
-  uint32_t *dn, *dx, *done, *dr2, *dgl, *dnw, *dbases, *dlohi;
-  uint4* dtab;
+  for (const HBig& g : c->pfb_bases) append(gl, g.limbs(PFB_S, LB));
+  uint32_t *dn, *dx, *done, *dr2, *dgl, *dnw;
   int rc;
-  if ((rc = upload_pfb(c, n.limbs(PFB_S, LB), &dn)) || (rc = upload_pfb(c, X.limbs(PFB_S, LB), &dx)) ||
-      (rc = upload_pfb(c, split(oneR), &done)) || (rc = upload_pfb(c, split(R2), &dr2)) ||
-      (rc = upload_pfb(c, gl, &dgl)) || (rc = upload_pfb(c, n.words(PFB_PW), &dnw)))
-    return pfb_unavailable(c, pai_last_error());
-  void *vb = nullptr, *vl = nullptr, *vt = nullptr, *vinv = nullptr, *vpre = nullptr;
-  void* vcv = nullptr;
-  if (hipMalloc(&vcv, (size_t)2 * K * PFB_S * 4) != hipSuccess) return pfb_unavailable(c, "table allocation failed");
-  c->pfb_mem.push_back(vcv);
-  if (hipMalloc(&vinv, (size_t)K * 2 * FB_LO * PFB_S * 4) != hipSuccess) return pfb_unavailable(c, "table allocation failed");
-  c->pfb_mem.push_back(vinv);
-  if (hipMalloc(&vpre, (size_t)2 * K * ((size_t)1 << (W - W / 2)) * PFB_S * 4) != hipSuccess)
-    return pfb_unavailable(c, "table allocation failed");
-  c->pfb_mem.push_back(vpre);
-  if (hipMalloc(&vb, (size_t)K * 2 * 2 * PFB_S * 4) != hipSuccess) return pfb_unavailable(c, "table allocation failed");
-  c->pfb_mem.push_back(vb);
-  if (hipMalloc(&vl, (size_t)K * 2 * FB_LO * 2 * PFB_S * 4) != hipSuccess) return pfb_unavailable(c, "table allocation failed");
-  c->pfb_mem.push_back(vl);
-  if (!(vt = TableArena::get().alloc(c->device, ((size_t)K << W) * PFB_ROW4 * sizeof(uint4))))
-    return pfb_unavailable(c, "table allocation failed");
-  c->pfb_tables.push_back(vt);
-  dbases = (uint32_t*)vb;
-  dlohi = (uint32_t*)vl;
-  dtab = (uint4*)vt;
+  if ((rc = upload_to(pfb.mem, n.limbs(PFB_S, LB), &dn)) || (rc = upload_to(pfb.mem, X.limbs(PFB_S, LB), &dx)) ||
+      (rc = upload_to(pfb.mem, pair_split(oneR, n, PFB_S), &done)) ||
+      (rc = upload_to(pfb.mem, pair_split(mul_pow2_mod(oneR, RS, n2), n, PFB_S), &dr2)) ||
+      (rc = upload_to(pfb.mem, gl, &dgl)) || (rc = upload_to(pfb.mem, n.words(PFB_PW), &dnw)))
+    return rc;
+  if (!sc.alloc(K, W, PFB_S, true) ||
+      !(*table = (uint4*)TableArena::get().alloc(c->device, ((size_t)K << W) * PFB_ROW4 * sizeof(uint4))))
+    return fail(PAI_ERR_HIP, "table allocation failed");
+  pfb.tables.push_back(*table);
   PfbConst pc{};
-  pc.g = FbgpHalf{(const uint32_t*)dtab, dn, dx, done, dbases, dlohi, nullptr, nullptr, nullptr, nullptr,
-                  mont_prime(n, LB), 0u, (uint32_t*)vinv, (uint32_t*)vpre, (uint32_t*)vcv};
-  pc.table = dtab;
+  pc.g = FbgpHalf{(const uint32_t*)*table, dn, dx, done, sc.bases, sc.lohi, nullptr, nullptr, nullptr, nullptr,
+                  mont_prime(n, LB), 0u, sc.inv, sc.pre, sc.cval};
+  pc.table = *table;
   pc.gl = dgl;
   pc.r2 = dr2;
   pc.nw = dnw;
@@ -2777,49 +2699,47 @@ static int ensure_pfb(pai_ctx* c) {
   pc.W = W;
   pc.K0 = K0;
   pc.KS = KS;
-  std::vector<PfbConst> pv{pc};
-  PfbConst* dpc = nullptr;
-  if ((rc = upload_pfb(c, pv, &dpc))) return pfb_unavailable(c, pai_last_error());
-  SgpHalf* dsgp = nullptr;
+  if ((rc = upload_to(pfb.mem, std::vector<PfbConst>{pc}, &pfb.d_pfb))) return rc;
   if (sgp_enabled()) {
     SgpHalf sh{};
-    if ((rc = sgp_make_half(n, HBig(1), K, dtab,
-                            [&](const std::vector<uint32_t>& v, uint32_t** o) { return upload_pfb(c, v, o); }, &sh)))
-      return pfb_unavailable(c, pai_last_error());
-    std::vector<SgpHalf> shv{sh};
-    if ((rc = upload_pfb(c, shv, &dsgp))) return pfb_unavailable(c, pai_last_error());
+    if ((rc = sgp_make_half(n, HBig(1), K, *table, pfb.mem, &sh)) ||
+        (rc = upload_to(pfb.mem, std::vector<SgpHalf>{sh}, &pfb.d_sgp)))
+      return rc;
   }
-  tr_m.reset();
-  const auto t1 = std::chrono::steady_clock::now();
+  return 0;
+}
+
+static int ensure_pfb(pai_ctx* c) {
+  if (c->pfb_state == pai_ctx::FB_READY) return 1;
+  if (c->pfb_state == pai_ctx::FB_UNAVAILABLE) return 0;
+  if (!pfb_supported(c)) return pfb_unavailable(c, "the public fixed-base kernels need a 1537..2048-bit n");
+  const int W = pfb_choose_window(c);
+  if (!W) return pfb_unavailable(c, "tables do not fit the device memory budget");
+  SetupTrace tr_all("ensure_pfb");
+  int K0, KS;
+  pfb_digit_counts(c, W, &K0, &KS);
+  const int K = K0 + PFB_SHORT * KS;
   {
-    SetupTrace tr_1("  pfb phase 1 (chains, lohi, inv_fwd)");
-    if (pfb_build_phase1(dpc, pc.nbases, K, W, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-      return pfb_unavailable(c, "table construction failed");
+    SetupTrace tr_h("  pfb host prep (bases, constants)");
+    if (!pfb_draw_bases(c)) return pfb_unavailable(c, "no randomness for the bases");
   }
+  PfbTables& pfb = c->pfb;
+  pfb.release();
+  RowScratch sc;
+  uint4* table = nullptr;
+  if (pfb_upload(c, W, K0, KS, sc, &table)) return pfb_unavailable(c, pai_last_error());
+  static const char* const lab[3] = {"  pfb phase 1 (chains, lohi, inv_fwd)", "  pfb host invert", "  pfb phase 2 (inv_bwd, fill)"};
+  if (build_factored_rows(
+          lab, [&] { return pfb_build_phase1(pfb.d_pfb, (int)c->pfb_bases.size(), K, W, nullptr); },
+          [&] { return pfb_build_phase2(pfb.d_pfb, K, W, table, nullptr); }, &c->n, &sc, 1, K, PFB_S))
+    return pfb_unavailable(c, pai_last_error());
   {
-    SetupTrace tr_i("  pfb host invert");
-    if (pair_host_invert(n, (uint32_t*)vcv, 2 * K, PFB_S)) return pfb_unavailable(c, pai_last_error());
+    SetupTrace tr_f("  pfb scratch frees");
+    sc.free();
   }
-  {
-    SetupTrace tr_2("  pfb phase 2 (inv_bwd, fill)");
-    if (pfb_build_phase2(dpc, K, W, dtab, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-      return pfb_unavailable(c, "table construction failed");
-  }
-  SetupTrace tr_f("  pfb scratch frees");
-  for (void* q : {vb, vl, vinv, vpre, vcv}) {   // build scratch
-    c->pfb_mem.erase(std::find(c->pfb_mem.begin(), c->pfb_mem.end(), q));
-    (void)hipFree(q);
-  }
-  const auto t2 = std::chrono::steady_clock::now();
-  c->d_pfb = dpc;
-  c->d_sgp_pfb = dsgp;
-  c->pfb_host_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
-  c->pfb_dev_ms = std::chrono::duration<float, std::milli>(t2 - t1).count();
-  c->pfb_table_bytes = pfb_bytes(c, W);
-  c->pfb_K = K;
-  c->pfb_K0 = K0;
-  c->pfb_KS = KS;
-  c->pfb_W_used = W;
+  pfb.K = K;
+  pfb.K0 = K0;
+  pfb.W_used = W;
   c->pfb_state = pai_ctx::FB_READY;
   return 1;
 }
@@ -2860,9 +2780,9 @@ static int launch_pfb(pai_ctx* c, const EncParams& e, hipStream_t st) {
   constexpr int GPB = BLOCK / PFB_TPI;
   const int gx = (int)std::max<long long>(1, std::min<long long>((chunk + GPB - 1) / GPB, (long long)occ * c->cus));
 #else
-  if (!c->d_sgp_pfb) return fail(PAI_ERR_KEY, "public fixed-base encrypt: no split-pair tables");
+  if (!c->pfb.d_sgp) return fail(PAI_ERR_KEY, "public fixed-base encrypt: no split-pair tables");
 #endif
-  const size_t dbytes = (size_t)c->pfb_K * 4, xbytes = (size_t)2 * PFB_SP * 4;
+  const size_t dbytes = (size_t)c->pfb.K * 4, xbytes = (size_t)2 * PFB_SP * 4;
   int rc;
   if ((rc = ensure_work(c, (dbytes + xbytes) * chunk))) return rc;
   uint32_t* digits = (uint32_t*)c->d_work;
@@ -2874,19 +2794,19 @@ static int launch_pfb(pai_ctx* c, const EncParams& e, hipStream_t st) {
     pd.n = n;
     std::memcpy(pd.rng_key, sl.rnd.rng_key, sizeof(pd.rng_key));
     pd.index_base = sl.rnd.index_base;
-    pd.K = c->pfb_K;
-    pd.W = c->pfb_W_used;
+    pd.K = c->pfb.K;
+    pd.W = c->pfb.W_used;
     pd.digits = digits;
     const int gD = (int)std::max<long long>(1, std::min<long long>((long long)8 * c->cus, (n + PFB_DIG_BLOCK - 1) / PFB_DIG_BLOCK));
     stage_mark(c, 0, st);
     HIPCHK(pfb_launch_digits(pd, gD, st));
     stage_mark(c, 1, st);
-    const PfbParams pp{c->d_pfb, n, digits, sl.src, sl.dst, xw};
-    if (c->d_sgp_pfb) {   // split pairs (kernels_sgp.hpp)
+    const PfbParams pp{c->pfb.d_pfb, n, digits, sl.src, sl.dst, xw};
+    if (c->pfb.d_sgp) {   // split pairs (kernels_sgp.hpp)
       int occS = 1;
       sgp_occupancy(&occS);
-      SgpParams sp{c->d_sgp_pfb, n, c->pfb_K, c->pfb_W_used, digits, xw, sl.src, sl.dst};
-      sp.g = guard_args(c, (unsigned long long)c->pfb_K << c->pfb_W_used, (unsigned long long)c->pfb_K * chunk,
+      SgpParams sp{c->pfb.d_sgp, n, c->pfb.K, c->pfb.W_used, digits, xw, sl.src, sl.dst};
+      sp.g = guard_args(c, (unsigned long long)c->pfb.K << c->pfb.W_used, (unsigned long long)c->pfb.K * chunk,
                         (unsigned long long)2 * PFB_SP * chunk, 0);
       const long long nb = (n + SGP_PAIRS - 1) / SGP_PAIRS;
       HIPCHK(sgp_launch(sp, (int)std::max<long long>(1, std::min<long long>(nb, (long long)occS * c->cus)), 1, st));
@@ -2934,7 +2854,7 @@ int pai_ctx_public_fb_set_bases(pai_ctx* c, const uint8_t* bases_le, size_t base
     bs.push_back(g);
   }
   HIPCHK(hipSetDevice(c->device));
-  pfb_release(c);
+  c->pfb.release();
   c->pfb_bases = bs;
   c->pfb_state = pai_ctx::FB_UNTRIED;
   return 0;
@@ -2953,9 +2873,9 @@ int pai_ctx_public_fb_info(pai_ctx* c, uint8_t* bases_le, size_t base_bytes, int
     }
   }
   if (nbases) *nbases = (int)c->pfb_bases.size();
-  if (digits) *digits = c->pfb_K;
-  if (window) *window = c->pfb_W_used;
-  if (e0_digits) *e0_digits = c->pfb_K0;
+  if (digits) *digits = c->pfb.K;
+  if (window) *window = c->pfb.W_used;
+  if (e0_digits) *e0_digits = c->pfb.K0;
   return 0;
 }
 
@@ -4674,19 +4594,19 @@ int pai_debug_encrypt_route(const pai_route_facts* facts, int obf_mode, long lon
   return 0;
 }
 
-// Copies the per-half sampler outputs (c0 G_h^a_h mod h^2) of the last fixed-base chunk: limbs [2][SB][n] (k_fb,
-// k_fbg), or canonical pairs [2][2S][n] with *sb = 2S for the pair tables (k_fbs/k_fbp; the p half times q^-2).
+// Copies the per-half sampler outputs (c0 G_h^a_h mod h^2) of the last fixed-base chunk: limbs [2][SB][n] (4096-bit
+// keys), or canonical pairs [2][2S][n] with *sb = 2S for the pair tables (k_fbs/k_fbp; the p half times q^-2).
 extern "C" int pai_debug_fb_w(pai_ctx* c, uint32_t* out, size_t max_words, long long* n, int* sb) {
   if (!c) return fail(PAI_ERR_ARG, "null ctx");
   CtxLock lk(c);
   if (!c->fb_last_w) return fail(PAI_ERR_ARG, "no fixed-base output");
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipDeviceSynchronize());
-  const int rows = c->fb_pair_s ? 2 * c->fb_pair_s : c->crt_sb;
+  const int rows = c->fb.pair_s ? 2 * c->fb.pair_s : c->crt_sb;
   const long long ne = c->fb_last_n;
   const size_t words = (size_t)2 * rows * ne;
   if (words > max_words) return fail(PAI_ERR_ARG, "buffer too small");
-  if (c->fb_pair_s) {   // 64-element tiles (kernels_fbp.hpp fbp_pair_index) -> [2][2S][n]
+  if (c->fb.pair_s) {   // 64-element tiles (kernels_fbp.hpp fbp_pair_index) -> [2][2S][n]
     const long long np = fbp_npad(ne);
     std::vector<uint32_t> t((size_t)2 * rows * np);
     HIPCHK(hipMemcpy(t.data(), c->fb_last_w, t.size() * 4, hipMemcpyDeviceToHost));

@@ -15,9 +15,8 @@
 // then cut into K = ceil(bits(p_h - 1) / W) W-bit digits. G^a = prod_k T_k[d_k] with T_k[d] =
 // G^(d 2^(W k)) precomputed once per key and resident in HBM; the samplers that multiply the rows are
 // kernels_fbs.hpp (1024/2048-bit keys, Shoup rows) and kernels_sgp.hpp / kernels_sgs.hpp (4096-bit keys).
-// This header holds what they share: the digit kernel, the row DMA, the table structs and the Garner
-// output helpers. (The round-1 sampler k_fb, its Garner k_fb_fin and table builders were retired in
-// round 6; the test build keeps k_fbp, kernels_fbp.hpp, as the cross-check of k_fbs.)
+// This header holds what they share: the digit kernel, the row DMA and the Garner output helpers.
+// (The test build keeps k_fbp, kernels_fbp.hpp, as the cross-check of k_fbs.)
 #pragma once
 #include "kernels_crt.hpp"
 #include "guard.hpp"
@@ -30,18 +29,17 @@ constexpr int FB_DIG_BLOCK = 128;            // threads per block of k_fb_digits
 constexpr int FB_LO = 4096;
                                              // entries of the per-position small tables (k_fbp_lohi): W <= 24
 
-// Compile-time geometry per lane size SB (limbs of p_h^2): TW = 32-bit words per table row (the
-// canonical values are < p_h^2 < 2^(32 TW)); c0 = 1 + n M is folded in as NC chunks of CB bits of |M|,
-// and negative M through the offset 2^PB p_h^2 (> the chunk sum, < 2^(28 SB - 4)).
+// Compile-time geometry per lane size SB (limbs of p_h^2): TW = 32-bit words of a value < p_h^2 (a half of the
+// ciphertext's 2 TW words)
 template <int SB>
 struct FbGeom;
 template <>
 struct FbGeom<37> {
-  static constexpr int TW = 32, CB = 4, NC = 16, PB = 10;
+  static constexpr int TW = 32;
 };
 template <>
 struct FbGeom<74> {
-  static constexpr int TW = 64, CB = 16, NC = 4, PB = 20;
+  static constexpr int TW = 64;
 };
 
 struct FbRed {             // Barrett reduction of the raw exponent modulo D_h = p_h - 1 (HAC 14.42, b = 2)
@@ -49,28 +47,6 @@ struct FbRed {             // Barrett reduction of the raw exponent modulo D_h =
   uint32_t mu[4];          // floor(2^raw_bits / D_h) (< 2^(raw_bits - kbits + 1) <= 2^66)
   int dwords, kbits;       // words and bits of D_h
   int pad[2];
-};
-
-struct FbHalf {
-  const uint4* table;      // [K][2^W][TW/4] quads: 32-bit words of T_k[d] = G^(d 2^(W k)) R mod p_h^2
-  const uint32_t* m;       // p_h^2, SB limbs
-  const uint32_t* R2;      // R^2 mod p_h^2 (table construction)
-  const uint32_t* oneR;    // R mod p_h^2 (table construction)
-  const uint32_t* bases;   // [K][SB] B_k = G^(2^(W k)) mod p_h^2, plain (table construction)
-  uint32_t* lohi;          // [K][2][FB_LO][SB] scratch of the table construction
-  const uint32_t* nm;      // [NC][SB] n 2^(CB c) mod p_h^2 (c0 folding)
-  const uint32_t* pbig;    // [SB] 2^PB p_h^2
-  uint32_t mprime;
-};
-
-struct FbParams {
-  const FbHalf* halves;    // [2]
-  long long n;             // elements
-  int K, W;                // digit positions, digit bits
-  const uint32_t* digits;  // [2][K][n] (k_fb_digits)
-  uint32_t* out;           // w [2][SB][n]: c0 G_h^a_h mod p_h^2 (< 2 p_h^2)
-  EncPlain src;
-  EncOut dst;              // exp and status, written by half 0 (ct: the finish kernels')
 };
 
 struct FbDigitParams {
@@ -86,7 +62,7 @@ struct FbDigitParams {
 // ---------------------------------------------------------------- exponent digits
 // Each lane stages its raw stream in its own LDS row (odd stride: conflict-free), reduces it modulo
 // D_h in place and extracts the digits. A kernel of its own: the ChaCha key schedule's registers would
-// otherwise push the modulus out of the SGPRs of k_fb.
+// otherwise push the modulus out of the samplers' SGPRs.
 // ROW (odd, >= raw words + 3): LDS words per lane, sized to the key (21 / 37 / 69 at nb = 1024 / 2048 / 4096) so
 // that the LDS of a block does not cap the occupancy (the 83-word rows of every key size allowed 1.5 waves per SIMD).
 // the per-key constants of the digit extraction, read once per kernel

@@ -208,6 +208,42 @@ def test_fixed_base_memory_cap_falls_back(golden, monkeypatch):
     assert np.array_equal(val, x.astype(np.float64))
 
 
+def test_fixed_base_rebuilds_after_memory_cap(golden, monkeypatch):
+    """A refused build leaves nothing behind: once the cap is lifted and the window changed, the same context builds
+    its tables (1024 bits: the smallest key on k_fbs, S = 19) and samples bit-exactly against the oracle; a build at
+    another window in between changes no ciphertext bit."""
+    N = _native()
+    key = _key(golden, 1024)
+    monkeypatch.setenv("FLEXPAI_FB_MAX_BYTES", "1000000")
+    monkeypatch.setenv("FLEXPAI_QUIET", "1")
+    ctx = N.Context(key.n, 0, key.p, key.q)
+    try:
+        with pytest.raises(RuntimeError):
+            ctx.prepare_fixed_base()
+        assert not ctx.fb_ready
+        monkeypatch.delenv("FLEXPAI_FB_MAX_BYTES")
+        assert ctx.fb_window != 8                          # so that the new window returns the path to "not tried"
+        ctx.set_fb_window(8)
+        ctx.prepare_fixed_base()
+        assert ctx.fb_ready and ctx.split_sampler & 4
+        params = ctx.fixed_base_info()
+        assert params[3] == 8 and ctx.fixed_base_setup()[2] == 2 * params[2] * (1 << 8) * 224
+        x = (np.random.default_rng(1024).standard_normal(64) * 100).astype(np.float32)
+        rk = bytes(range(11, 43))
+        ct, ex, _ = ctx.encrypt(x, obf_mode=N.PAI_OBF_RNG, rng_key=rk, index_base=2 ** 33 + 9)
+        got = N.words_to_ints(ct)
+        for i in range(x.size):
+            assert (got[i], int(ex[i])) == O.fb_encrypt_value(x[i], key, rk, 2 ** 33 + 9 + i, params), f"element {i}"
+        ctx.set_fb_window(12)
+        assert ctx.fixed_base_info()[3] == 12              # tables at another window in between
+        ctx.set_fb_window(8)
+        assert ctx.fixed_base_info() == params
+        ct2, ex2, _ = ctx.encrypt(x, obf_mode=N.PAI_OBF_RNG, rng_key=rk, index_base=2 ** 33 + 9)
+        assert np.array_equal(ct, ct2) and np.array_equal(ex, ex2)
+    finally:
+        ctx.close()
+
+
 def test_fixed_base_garner_unreduced_half_regression(ctxs):
     """Regression: k_fb's per-half outputs are < 2 h^2, and Garner must reduce w_q mod q^2 BEFORE it forms
     h = (w_p - w_q) (q^2)^-1 mod p^2. With the 1024-bit key (R / p^2 = 2^12) w_q lands in [q^2, 2 q^2) for

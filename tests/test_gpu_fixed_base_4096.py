@@ -133,6 +133,42 @@ def test_fixed_base_4096_memory_cap_falls_back(golden, monkeypatch):
     assert np.array_equal(val, x.astype(np.float64))
 
 
+def test_fixed_base_4096_rebuilds_after_memory_cap(golden, monkeypatch):
+    """A refused build leaves nothing behind: once the cap is lifted and the window changed, the same context builds
+    its tables, samples on split pairs bit-exactly against the oracle, and a build at another window in between changes
+    no ciphertext bit."""
+    N = _native()
+    key = _key(golden)
+    monkeypatch.setenv("FLEXPAI_FB_MAX_BYTES", "1000000")
+    monkeypatch.setenv("FLEXPAI_QUIET", "1")
+    ctx = N.Context(key.n, 0, key.p, key.q)
+    try:
+        with pytest.raises(RuntimeError):
+            ctx.prepare_fixed_base()
+        assert not ctx.fb_ready
+        monkeypatch.delenv("FLEXPAI_FB_MAX_BYTES")
+        assert ctx.fb_window != 8
+        ctx.set_fb_window(8)
+        ctx.prepare_fixed_base()
+        assert ctx.fb_ready and ctx.split_sampler & 1
+        params = ctx.fixed_base_info()
+        assert params[3] == 8
+        x = (np.random.default_rng(4096).standard_normal(16) * 1e3).astype(np.float32)
+        rk = bytes(range(5, 37))
+        ct, ex, _ = ctx.encrypt(x, obf_mode=N.PAI_OBF_RNG, rng_key=rk, index_base=2 ** 33 + 3)
+        got = N.words_to_ints(ct)
+        for i in range(x.size):
+            assert (got[i], int(ex[i])) == O.fb_encrypt_value(x[i], key, rk, 2 ** 33 + 3 + i, params), f"element {i}"
+        ctx.set_fb_window(12)
+        assert ctx.fixed_base_info()[3] == 12              # tables at another window in between
+        ctx.set_fb_window(8)
+        assert ctx.fixed_base_info() == params and ctx.split_sampler & 1
+        ct2, ex2, _ = ctx.encrypt(x, obf_mode=N.PAI_OBF_RNG, rng_key=rk, index_base=2 ** 33 + 3)
+        assert np.array_equal(ct, ct2) and np.array_equal(ex, ex2)
+    finally:
+        ctx.close()
+
+
 def test_split_sampler_matches_group_engine(ctx4096, golden, monkeypatch, xlib):
     """k_sgp (kernels_sgp.hpp, split pairs: the default) and k_fbgp (pair groups, FLEXPAI_SGP=0 in the test build)
     read the same tables and give the same ciphertexts, ragged size, non-zero index base."""

@@ -131,6 +131,40 @@ def test_public_fresh_key_small_call_uses_pe(golden, monkeypatch):
         assert got[i] == O.encrypt_value(x[i], key, O.device_r(rk, 9 + i, rbytes) % key.n)[0]
 
 
+def test_public_fixed_base_rebuilds_after_memory_cap(golden, monkeypatch):
+    """A refused build leaves nothing behind: once the cap is lifted and the window changed, the same context builds
+    its tables and samples exactly what a fresh context with the same bases does."""
+    N = _native()
+    n = int(golden["keys"]["2048"]["n"], 16)
+    monkeypatch.setenv("FLEXPAI_FB_MAX_BYTES", "1000000")
+    monkeypatch.setenv("FLEXPAI_QUIET", "1")
+    ctx, fresh = N.Context(n, 0), None
+    try:
+        with pytest.raises(RuntimeError):
+            ctx.prepare_public_fixed_base()
+        assert not ctx.pfb_ready
+        monkeypatch.delenv("FLEXPAI_FB_MAX_BYTES")
+        ctx.set_pfb_window(12)
+        ctx.prepare_public_fixed_base()
+        assert ctx.pfb_ready
+        bases, K, W, K0 = ctx.public_fixed_base_info()
+        assert W == 12 and (K0, (K - K0) // O.PFB_SHORT) == O.pfb_layout(2048, 12)
+        fresh = N.Context(n, 0)
+        fresh.set_public_bases(bases)
+        fresh.set_pfb_window(12)
+        fresh.prepare_public_fixed_base()
+        assert fresh.public_fixed_base_info() == (bases, K, W, K0)
+        x = (np.random.default_rng(2048).standard_normal(64) * 100).astype(np.float32)
+        rk = bytes(range(21, 53))
+        a = ctx.encrypt(x, obf_mode=N.PAI_OBF_RNG, rng_key=rk, index_base=2 ** 33 + 7)
+        b = fresh.encrypt(x, obf_mode=N.PAI_OBF_RNG, rng_key=rk, index_base=2 ** 33 + 7)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    finally:
+        ctx.close()
+        if fresh is not None:
+            fresh.close()
+
+
 def test_public_full_size_roundtrip(drawn):
     N = _native()
     ctx, dec, key = drawn
