@@ -29,15 +29,15 @@ hipError_t fbs_launch(int s, const FbpParams& p, int gx, hipStream_t st) {
 }
 
 hipError_t fbs_build_phase2(int s, const FbpHalf* d_halves, const FbsConst* cst, uint4* t0, uint4* t1, int K, int W,
-                            hipStream_t st, const GuardArgs& g) {
-  const int per = ((1 << W) + LANE_BLOCK - 1) / LANE_BLOCK;
+                            int nw, hipStream_t st, const GuardArgs& g) {
+  const int blocks = nw * fbs_fill_blocks(W + 1) + (K - nw) * fbs_fill_blocks(W);   // k_fbs_fill: FbsFillPos
   const dim3 ig((2 * K + 63) / 64, 2);
   if (s == 19) {
-    hipLaunchKernelGGL(k_fbp_inv_bwd<19>, ig, dim3(64), 0, st, d_halves, K, W);
-    hipLaunchKernelGGL(k_fbs_fill<19>, dim3(K * per, 2), dim3(LANE_BLOCK), 0, st, d_halves, cst, K, W, t0, t1, g);
+    hipLaunchKernelGGL(k_fbp_inv_bwd<19>, ig, dim3(64), 0, st, d_halves, K, W, nw);
+    hipLaunchKernelGGL(k_fbs_fill<19>, dim3(blocks, 2), dim3(LANE_BLOCK), 0, st, d_halves, cst, W, nw, t0, t1, g);
   } else if (s == 37) {
-    hipLaunchKernelGGL(k_fbp_inv_bwd<37>, ig, dim3(64), 0, st, d_halves, K, W);
-    hipLaunchKernelGGL(k_fbs_fill<37>, dim3(K * per, 2), dim3(LANE_BLOCK), 0, st, d_halves, cst, K, W, t0, t1, g);
+    hipLaunchKernelGGL(k_fbp_inv_bwd<37>, ig, dim3(64), 0, st, d_halves, K, W, nw);
+    hipLaunchKernelGGL(k_fbs_fill<37>, dim3(blocks, 2), dim3(LANE_BLOCK), 0, st, d_halves, cst, W, nw, t0, t1, g);
   } else {
     return hipErrorInvalidValue;
   }

@@ -11,8 +11,9 @@ int fbs_occupancy(int s, int* occ);
 // k_fbs<s> over grid (gx, 2): LANE_BLOCK / 2 elements per block and sweep
 hipError_t fbs_launch(int s, const FbpParams& p, int gx, hipStream_t st);
 // phase 2 of the table construction for Shoup rows (after the host wrote the chain inverses): the inverse tables
-// (k_fbp_inv_bwd), then the rows (k_fbs_fill); cst: device array of the two halves' FbsConst; g: the address guard (guard.hpp)
+// (k_fbp_inv_bwd), then the rows (k_fbs_fill); cst: device array of the two halves' FbsConst; g: the address guard (guard.hpp).
+// K digit positions, the first nw of W + 1 bits, the others of W (fb_cut.hpp)
 hipError_t fbs_build_phase2(int s, const FbpHalf* d_halves, const FbsConst* cst, uint4* t0, uint4* t1, int K, int W,
-                            hipStream_t st, const GuardArgs& g);
+                            int nw, hipStream_t st, const GuardArgs& g);
 
 }  // namespace fpai

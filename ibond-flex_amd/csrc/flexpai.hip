@@ -92,6 +92,7 @@ static void free_device(std::vector<void*>& mem, std::vector<void*>& tables) {
 struct FbTables {
   int K = 0;                    // digit positions
   int W_used = 0;               // window of the resident tables (may be below pai_ctx::fb_W under a memory cap)
+  int nw = 0;                   // Shoup rows: positions 0 .. nw-1 are one bit wider than the window (fb_cut.hpp)
   int raw_bits = 0;
   FbRed* d_red = nullptr;       // [2] k_fb_digits: the exponent reduction mod p_h - 1
   // 1024/2048-bit keys: pair tables over the S limbs of p_h
@@ -1268,10 +1269,12 @@ static int fb_table_row_words(const pai_ctx* c) {
   return fb_row_words(c);
 }
 
-static int fb_digit_count(const pai_ctx* c, int W) {
-  const size_t kb = std::max(sub(c->fb_p, HBig(1)).bits(), sub(c->fb_q, HBig(1)).bits());
-  return (int)((kb + W - 1) / W);
+// bits of the exponents a_h < p_h - 1
+static int fb_exponent_bits(const pai_ctx* c) {
+  return (int)std::max(sub(c->fb_p, HBig(1)).bits(), sub(c->fb_q, HBig(1)).bits());
 }
+
+static int fb_digit_count(const pai_ctx* c, int W) { return fb_cut_uniform(fb_exponent_bits(c), W).K; }
 
 static uint64_t fb_bytes(const pai_ctx* c, int W, bool sgs = false) {
   return 2ull * (uint64_t)fb_digit_count(c, W) * (1ull << W) * ((uint64_t)fb_table_row_words(c) + (sgs ? 4ull * SGS_ROW_Q : 0ull)) *
@@ -1281,12 +1284,8 @@ static uint64_t fb_bytes(const pai_ctx* c, int W, bool sgs = false) {
 // The window of the tables (<= c->fb_W, within budget) and whether Shoup rows join them (sgs_mode, above)
 static int fb_choose(const pai_ctx* c, uint64_t budget, bool* sgs, bool allow_sgs = true) {
   static const int ladder[] = {24, 23, 22, 21, 20, 16, 12, 8};
-  int wm = 0, ws = 0;
-  for (int w : ladder)
-    if (w <= c->fb_W && fb_bytes(c, w) <= budget) {
-      wm = w;
-      break;
-    }
+  const int wm = fb_ladder_window(fb_exponent_bits(c), c->fb_W, 4ull * fb_table_row_words(c), budget);
+  int ws = 0;
   const int mode = allow_sgs ? sgs_mode() : 0;
   if (mode != 0 && fb_gpair_possible(c) && sgp_enabled())
     for (int w : ladder)
@@ -1328,9 +1327,9 @@ static uint64_t fb_budget(const pai_ctx* c) {
 // only once the device-RNG elements of this context (this call included) reach the break-even count --
 // a re-keying caller (HE_SA_FT, he_sa_ft/train.py:39-40) encrypting a few hundred elements per key never
 // pays the build. $FLEXPAI_FB_MIN_ELEMS overrides the count; pai_ctx_fixed_base_prepare builds at once.
-static long long fb_break_even(const pai_ctx* c, int W, int K, int row_bytes) {
+static long long fb_break_even(const pai_ctx* c, uint64_t rows, int row_bytes) {   // rows: per half
   if (const char* e = getenv("FLEXPAI_FB_MIN_ELEMS")) return atoll(e);
-  const double build_s = 0.05 + 2.0 * K * (double)(1ull << W) * 2.1e-9 * (row_bytes / 256.0);
+  const double build_s = 0.05 + 2.0 * (double)rows * 2.1e-9 * (row_bytes / 256.0);
   const double save_s = c->nb > 2048 ? 27e-6 : c->nb > 1024 ? 0.59e-6 : 0.08e-6;
   return (long long)(build_s / save_s) + 1;
 }
@@ -1455,7 +1454,8 @@ struct FbPlan {
   int S = 0;             // limbs of a pair's components: ps, or FBGP_S
   int row_words = 0;     // 32-bit words of one resident row (without the 4096-bit Shoup rows)
   int W = 0, K = 0, raw_bits = 0;
-  size_t rows() const { return (size_t)K << W; }   // per half
+  int nw = 0;            // Shoup rows: the first nw of the K digits hold W + 1 bits (fb_cut.hpp); 0: the uniform cut
+  size_t rows() const { return (size_t)fb_cut_row(K, W, nw); }   // per half
 };
 
 static FbPlan fb_plan(pai_ctx* c, bool allow_sgs = true) {
@@ -1476,9 +1476,17 @@ static FbPlan fb_plan(pai_ctx* c, bool allow_sgs = true) {
   pl.S = pl.ps ? pl.ps : FBGP_S;
   pl.row_words = fb_table_row_words(c);
   if (!c->fb_W) c->fb_W = fb_default_window();
-  pl.W = fb_choose(c, fb_budget(c), &pl.sgs, allow_sgs);
+  const uint64_t budget = fb_budget(c);
+  pl.W = fb_choose(c, budget, &pl.sgs, allow_sgs);
   pl.K = pl.W ? fb_digit_count(c, pl.W) : 0;
-  pl.raw_bits = (int)std::max(sub(c->fb_p, HBig(1)).bits(), sub(c->fb_q, HBig(1)).bits()) + 64;
+  // Shoup rows: an uneven cut within the same budget where it saves a whole row product (fb_cut.hpp). K stays >= S.
+  // The 4096-bit samplers and the test build's Montgomery rows keep the uniform cut.
+  if (pl.shoup && pl.W) {
+    const FbCut cut = fb_cut_plan(fb_exponent_bits(c), pl.W, c->fb_W, 4ull * pl.row_words, budget, pl.ps);
+    pl.W = cut.W, pl.K = cut.K, pl.nw = cut.nw;
+    if (pl.K < pl.ps) return refuse("fewer digit positions than limbs");
+  }
+  pl.raw_bits = fb_exponent_bits(c) + 64;
   const size_t sq_bits = std::max(mul(c->fb_p, c->fb_p).bits(), mul(c->fb_q, c->fb_q).bits());
   if (!pl.grp && (sq_bits > (size_t)32 * TW || c->ct_words != 2 * TW))
     return refuse("unbalanced primes: p^2 or q^2 exceeds the table row");
@@ -1545,13 +1553,14 @@ static void fb_host_bases(const pai_ctx* c, FbBuild& b) {
     o.g = c->fb_g[h] ? c->fb_g[h] : fb_base(P);
     if (!o.g) return;
     HMont M2(m2);
-    const int S = b.pl.S, W = b.pl.W;
+    const int S = b.pl.S;
     const size_t RS = (size_t)LB * S;
     HBig y = M2.to(M2.pow(HBig(o.g), c->n));
-    for (int k = 0; k < b.pl.K; ++k) {
+    for (int k = 0; k < b.pl.K; ++k) {   // B_k = G^(2^off_k), off_k the bit offset of digit k
+      const int w = fb_cut_width(k, b.pl.W, b.pl.nw);
       append(o.bases, pair_split(mul_pow2_mod(M2.from(y), RS, m2), P, S));
-      append(o.bases, pair_split(mul_pow2_mod(M2.from(M2.sqr_k(y, (size_t)(W / 2))), RS, m2), P, S));
-      y = M2.sqr_k(y, (size_t)W);
+      append(o.bases, pair_split(mul_pow2_mod(M2.from(M2.sqr_k(y, (size_t)(w / 2))), RS, m2), P, S));
+      y = M2.sqr_k(y, (size_t)w);
     }
   };
   std::thread t1(prep, 1);
@@ -1612,7 +1621,7 @@ static int fb_upload_halves(pai_ctx* c, FbBuild& b) {
   for (int h = 0; h < 2; ++h) {
     const FbHalfConst& o = b.hc[h];
     RowScratch& sc = b.sc[h];
-    if (!sc.alloc(pl.K, pl.W, pl.S)) return fail(PAI_ERR_HIP, "table allocation failed");
+    if (!sc.alloc(pl.K, fb_cut_width(0, pl.W, pl.nw), pl.S)) return fail(PAI_ERR_HIP, "table allocation failed");   // the widest digit's
     {
       SetupTrace tr_m("  table allocation (one half)");
       if (!(b.t[h] = TableArena::get().alloc(c->device, pl.rows() * (pl.row_words / 4) * sizeof(uint4))))
@@ -1704,12 +1713,12 @@ static int fb_build_rows(pai_ctx* c, FbBuild& b) {
   const FbPlan& pl = b.pl;
   const FbTables& fb = c->fb;
   const int K = pl.K, W = pl.W;
-  auto phase1 = [&] { return pl.ps ? fbp_build_phase1(pl.ps, fb.d_fbp, K, W, nullptr) : fbgp_build_phase1(fb.d_fbgp, K, W, nullptr); };
+  auto phase1 = [&] { return pl.ps ? fbp_build_phase1(pl.ps, fb.d_fbp, K, W, pl.nw, nullptr) : fbgp_build_phase1(fb.d_fbgp, K, W, nullptr); };
   auto phase2 = [&] {
     if (!pl.ps) return fbgp_build_phase2(fb.d_fbgp, (uint32_t*)b.t[0], (uint32_t*)b.t[1], K, W, nullptr);
     if constexpr (FLEXPAI_XCHECK)   // the test build's Montgomery rows
       if (!pl.shoup) return fbp_build_phase2(pl.ps, fb.d_fbp, (uint4*)b.t[0], (uint4*)b.t[1], K, W, nullptr);
-    return fbs_build_phase2(pl.ps, fb.d_fbp, fb.d_fbs_cst, (uint4*)b.t[0], (uint4*)b.t[1], K, W, nullptr,
+    return fbs_build_phase2(pl.ps, fb.d_fbp, fb.d_fbs_cst, (uint4*)b.t[0], (uint4*)b.t[1], K, W, pl.nw, nullptr,
                             guard_args(c, (unsigned long long)pl.rows(), 0, 0, 0));
   };
   static const char* const lab[3] = {"  phase 1 (lohi, inv_fwd) + host invert", nullptr, "  phase 2 (inv_bwd, fill) + frees"};
@@ -1763,9 +1772,10 @@ static int ensure_fb(pai_ctx* c) {
   FbTables& fb = c->fb;
   fb.host_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
   fb.dev_ms = std::chrono::duration<float, std::milli>(t2 - t1).count();
-  fb.table_bytes = fb_bytes(c, pl.W, fb.d_sgs != nullptr);
+  fb.table_bytes = 2ull * pl.rows() * (4ull * pl.row_words + (fb.d_sgs ? 16ull * SGS_ROW_Q : 0ull));
   fb.K = pl.K;
   fb.W_used = pl.W;
+  fb.nw = pl.nw;
   fb.raw_bits = pl.raw_bits;
   fb.pair_s = pl.ps;
   fb.shoup = pl.shoup;
@@ -2297,7 +2307,7 @@ int pai_ctx_fixed_base_prepare(pai_ctx* c) {
 static long long fb_threshold(pai_ctx* c) {
   if (c->fb_state != pai_ctx::FB_UNTRIED) return 0;
   const FbPlan pl = fb_plan(c);
-  return pl.W ? fb_break_even(c, pl.W, pl.K, 4 * pl.row_words + (pl.sgs ? 16 * SGS_ROW_Q : 0)) : 0;
+  return pl.W ? fb_break_even(c, pl.rows(), 4 * pl.row_words + (pl.sgs ? 16 * SGS_ROW_Q : 0)) : 0;
 }
 
 static bool fb_wanted(pai_ctx* c, long long n) {
@@ -2481,6 +2491,7 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
     pd.index_base = sl.rnd.index_base;
     pd.K = K;
     pd.W = W;
+    pd.nw = c->fb.nw;
     pd.raw_bits = c->fb.raw_bits;
     pd.red = c->fb.d_red;
     pd.digits = digits;
@@ -2494,7 +2505,8 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
     const FbgpParams pg{c->fb.d_fbgp, n, K, W, digits, w, sl.src, sl.dst};   // the test build's k_fbgp, and k_fbgp_w
     if (c->fb.pair_s) {
       FbpParams pp{c->fb.d_fbp, n, K, W, digits, w, sl.src, sl.dst};
-      pp.g = guard_args(c, (unsigned long long)K << W, dig_words, w_words, 0);
+      pp.nw = c->fb.nw;
+      pp.g = guard_args(c, fb_cut_row(K, W, pp.nw), dig_words, w_words, 0);
 #if FLEXPAI_XCHECK
       if (!c->fb.shoup) HIPCHK(fbp_launch(c->fb.pair_s, pp, gF, st));
 #endif

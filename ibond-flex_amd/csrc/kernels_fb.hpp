@@ -12,14 +12,17 @@
 //
 // a_h = raw_h mod (p_h - 1): raw_h is the first raw_bits = max bits(p_h - 1) + 64 bits of a ChaCha20
 // stream (statistical distance 2^-64 from uniform), reduced on the device by Barrett (k_fb_digits),
-// then cut into K = ceil(bits(p_h - 1) / W) W-bit digits. G^a = prod_k T_k[d_k] with T_k[d] =
-// G^(d 2^(W k)) precomputed once per key and resident in HBM; the samplers that multiply the rows are
-// kernels_fbs.hpp (1024/2048-bit keys, Shoup rows) and kernels_sgp.hpp / kernels_sgs.hpp (4096-bit keys).
+// then cut into K = ceil(bits(p_h - 1) / W) W-bit digits -- or, on the Shoup rows of 1024/2048-bit keys, into fewer
+// digits whose first nw are one bit wider where the memory allows it (fb_cut.hpp). G^a = prod_k T_k[d_k] with T_k[d] =
+// G^(d 2^off_k), off_k the digit's bit offset (W k for the uniform cut), precomputed once per key and resident in HBM;
+// the samplers that multiply the rows are kernels_fbs.hpp (1024/2048-bit keys, Shoup rows) and kernels_sgp.hpp /
+// kernels_sgs.hpp (4096-bit keys).
 // This header holds what they share: the digit kernel, the row DMA and the Garner output helpers.
 // (The test build keeps k_fbp, kernels_fbp.hpp, as the cross-check of k_fbs.)
 #pragma once
 #include "kernels_crt.hpp"
 #include "guard.hpp"
+#include "fb_cut.hpp"
 
 namespace fpai {
 
@@ -55,8 +58,9 @@ struct FbDigitParams {
   unsigned long long index_base;
   int K, W, raw_bits;
   const FbRed* red;        // [2]
-  uint32_t* digits;        // [2][K][n]
+  uint32_t* digits;        // [2][K][n]: digit k plus fb_cut_shift(k, W, nw), the samplers' row index less k 2^W
   GuardArgs g;             // test build: digits = 2 K n
+  int nw;                  // digits 0 .. nw-1 hold W + 1 bits (fb_cut.hpp; 0: the uniform cut)
 };
 
 // ---------------------------------------------------------------- exponent digits
@@ -69,7 +73,7 @@ struct FbDigitParams {
 struct FbDigitKey {
   const FbRed* R;
   int rb, rw, nblk, dw, kb;
-  uint32_t mask, mu0, mu1, mu2;
+  uint32_t mu0, mu1, mu2;
 };
 __device__ __forceinline__ FbDigitKey fb_digit_key(const FbDigitParams& p, int half) {
   FbDigitKey k;
@@ -79,7 +83,6 @@ __device__ __forceinline__ FbDigitKey fb_digit_key(const FbDigitParams& p, int h
   k.nblk = (k.rw + 15) / 16;
   k.dw = k.R->dwords;
   k.kb = k.R->kbits;
-  k.mask = (1u << p.W) - 1u;
   k.mu0 = k.R->mu[0];
   k.mu1 = k.R->mu[1];
   k.mu2 = k.R->mu[2];
@@ -92,7 +95,6 @@ template <int ROW>
 __device__ __forceinline__ void fb_digits_elem(const FbDigitParams& p, const FbDigitKey& dk, int half, long long i, uint32_t* a) {
   const FbRed* R = dk.R;
   const int rb = dk.rb, rw = dk.rw, nblk = dk.nblk, dw = dk.dw, kb = dk.kb;
-  const uint32_t mask = dk.mask;
   {
     const unsigned long long g = p.index_base + (unsigned long long)i;
     for (int b = 0; b < nblk; ++b) {
@@ -175,9 +177,11 @@ __device__ __forceinline__ void fb_digits_elem(const FbDigitParams& p, const FbD
       }
     }
     for (int k = 0; k < p.K; ++k) {
-      const int bit = k * p.W, wi = bit >> 5, sh = bit & 31;
+      const int bit = fb_cut_bit(k, p.W, p.nw), wi = bit >> 5, sh = bit & 31;
       const uint64_t v = (((uint64_t)a[wi + 1] << 32) | a[wi]) >> sh;
-      p.digits[FPAI_GUARD_IDX(p.g, GS_DIG_OUT, ((size_t)half * p.K + k) * p.n + i, p.g.digits, i)] = (uint32_t)(v & mask);
+      // stored as the samplers look it up: the row of T_k[d] less k 2^W, i.e. d itself for the uniform cut
+      p.digits[FPAI_GUARD_IDX(p.g, GS_DIG_OUT, ((size_t)half * p.K + k) * p.n + i, p.g.digits, i)] =
+          fb_cut_shift(k, p.W, p.nw) + ((uint32_t)v & ((1u << fb_cut_width(k, p.W, p.nw)) - 1u));
     }
   }
 }

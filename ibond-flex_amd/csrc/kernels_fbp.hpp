@@ -64,11 +64,12 @@ struct FbpParams {
   const FbpHalf* halves;   // [2]
   long long n;
   int K, W;
-  const uint32_t* digits;  // [2][K][n]
+  const uint32_t* digits;  // [2][K][n]: row of T_k[d_k] less k 2^W (k_fb_digits)
   uint32_t* out;           // canonical pairs (A limbs, then B) for k_fbp_fin in 64-element tiles (fbp_pair_index)
   EncPlain src;
   EncOut dst;              // exp and status, written by half 0 (ct: the finish kernels')
-  GuardArgs g;             // test build (guard.hpp): rows = K 2^W, digits = 2 K n, out = the pair tiles' words
+  GuardArgs g;             // test build (guard.hpp): rows = the table's, digits = 2 K n, out = the pair tiles' words
+  int nw = 0;              // k_fbs's test build: digits 0 .. nw-1 hold W + 1 bits (fb_cut.hpp), for the digit check alone
 };
 
 // LDS words at a byte offset from this lane's row base (offsets past the 16-bit immediate take a second base)
@@ -810,11 +811,12 @@ __global__ __launch_bounds__(LANE_BLOCK, 2) void k_fbp_fin(FbpFinParams p) {
 // square-and-multiply from R (the pair of one; position 0's lo entries times kappa R, FbpHalf::kapR, so that
 // T_0[d] = kappa B_0^d); k_fbp_inv_*: the inverses of their A parts mod p_h; k_fbp_fill:
 // T_k[d] R = lo[d & (2^LO - 1)] hi[d >> LO] R^-1, one pair product per entry, factored (header) and stored as words.
+// Position k's digit holds w = W + (k < nw) bits (fb_cut.hpp; nw = 0 but for the Shoup rows): LO = w / 2, HI = w - LO.
 template <int S>
-__global__ __launch_bounds__(LANE_BLOCK) void k_fbp_lohi(const FbpHalf* halves, int K, int W) {
+__global__ __launch_bounds__(LANE_BLOCK) void k_fbp_lohi(const FbpHalf* halves, int K, int W, int nw) {
   const int k = blockIdx.x, half = blockIdx.y;
   const FbpHalf* H = halves + half;
-  const int LO = W / 2, HI = W - LO;
+  const int w = fb_cut_width(k, W, nw), LO = w / 2, HI = w - LO;
   uint32_t m[S], A[S], B[S];
 #pragma unroll
   for (int i = 0; i < S; ++i) m[i] = H->p[i];
@@ -869,11 +871,12 @@ struct FbpInvChain {
   uint32_t* pre;        // prefix product j at pre + S j
   uint32_t* inv;        // inverse j at inv + S j
   uint32_t* cval;
-  __device__ FbpInvChain(const FbpHalf* H, int K, int W) {
+  __device__ FbpInvChain(const FbpHalf* H, int K, int W, int nw) {
     const int c0 = blockIdx.x * blockDim.x + threadIdx.x;
     valid = c0 < 2 * K;
     const int c = valid ? c0 : 0, k = c >> 1, sp = c & 1;
-    const int LO = W / 2, HI = W - LO, EM = 1 << (HI > LO ? HI : LO);
+    const int w = fb_cut_width(k, W, nw), LO = w / 2, HI = w - LO;
+    const int wm = fb_cut_width(0, W, nw), EM = 1 << (wm - wm / 2);   // the widest position's chains set the stride
     E = 1 << (sp ? HI : LO);
     lh = H->lohi + ((size_t)k * 2 + sp) * FB_LO * 2 * S;
     pre = H->pre + (size_t)c * EM * S;
@@ -883,9 +886,9 @@ struct FbpInvChain {
 };
 
 template <int S>
-__global__ __launch_bounds__(64) void k_fbp_inv_fwd(const FbpHalf* halves, int K, int W) {
+__global__ __launch_bounds__(64) void k_fbp_inv_fwd(const FbpHalf* halves, int K, int W, int nw) {
   const FbpHalf* H = halves + blockIdx.y;
-  const FbpInvChain<S> ch(H, K, W);
+  const FbpInvChain<S> ch(H, K, W, nw);
   if (!ch.valid) return;
   uint32_t m[S], acc[S], x[S];
 #pragma unroll
@@ -907,9 +910,9 @@ __global__ __launch_bounds__(64) void k_fbp_inv_fwd(const FbpHalf* halves, int K
 }
 
 template <int S>
-__global__ __launch_bounds__(64) void k_fbp_inv_bwd(const FbpHalf* halves, int K, int W) {
+__global__ __launch_bounds__(64) void k_fbp_inv_bwd(const FbpHalf* halves, int K, int W, int nw) {
   const FbpHalf* H = halves + blockIdx.y;
-  const FbpInvChain<S> ch(H, K, W);
+  const FbpInvChain<S> ch(H, K, W, nw);
   if (!ch.valid) return;
   uint32_t m[S], I[S], x[S], t[S];
 #pragma unroll

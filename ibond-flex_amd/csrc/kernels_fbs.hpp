@@ -245,7 +245,9 @@ __device__ __forceinline__ void fbs_row_fetch(const uint4* row, uint32_t lb, int
 __device__ __forceinline__ uint32_t fbs_guard_digit(const FbpParams& p, int h, int k, long long ee, unsigned int s_off,
                                                     unsigned int s_val) {
   const uint32_t d = p.digits[FPAI_GUARD_IDX(p.g, s_off, ((size_t)h * p.K + k) * p.n + ee, p.g.digits, ee)];
-  return (uint32_t)FPAI_GUARD_IDX(p.g, s_val, d, 1ull << p.W, ee);
+  // (the digit comes with its position's row shift, fb_cut_shift: checked without it, returned with it)
+  const uint32_t sh = fb_cut_shift(k, p.W, p.nw);
+  return sh + (uint32_t)FPAI_GUARD_IDX(p.g, s_val, d - sh, 1ull << fb_cut_width(k, p.W, p.nw), ee);
 }
 #define FBS_DIGIT(k) fbs_guard_digit(p, half, (k), ee, GS_FBS_DIGIT, GS_FBS_DVAL)
 #define FBS_ROW(k, d) FPAI_GUARD_IDX(p.g, GS_FBS_ROW, ((size_t)(k) << W) + (d), p.g.rows, ee)
@@ -268,7 +270,7 @@ __global__ __launch_bounds__(LANE_BLOCK, 2) void k_fbs(FbpParams p) {
   for (int j = 0; j < S; ++j) m[j] = H->p[j];
   const uint32_t mprime = H->mprime;
   const uint4* table = H->table;
-  const int K = p.K, W = p.W;
+  const int K = p.K, W = p.W;   // (an uneven cut's row shifts come inside the digits: k_fb_digits, fb_cut_shift)
   const int lane = threadIdx.x & 63;
   const int tig = threadIdx.x & 1;
   const bool odd = tig != 0;
@@ -463,25 +465,39 @@ __device__ __forceinline__ void fbs_apt_all(uint32_t (&tl)[S + 1], const uint32_
   (fbs_apt_step<S, Ts>(acc, tl, ap, A, m, std::make_integer_sequence<int, S + 1>{}), ...);
 }
 
-// One row per thread. UNI: every thread of the block shares the hi entry (2^(W/2) >= LANE_BLOCK, i.e. W >= 16), whose
+// blocks of k_fbs_fill per digit position of w bits: one row per thread
+__host__ __device__ constexpr int fbs_fill_blocks(int w) { return ((1 << w) + LANE_BLOCK - 1) / LANE_BLOCK; }
+// blockIdx.x -> the position k, its width w and the block's first digit d0; the blocks of the nw positions of W + 1 bits
+// come first (fb_cut.hpp; nw = 0: k = blockIdx.x / blocks(W), as ever)
+struct FbsFillPos {
+  int k, w, d0;
+  __device__ FbsFillPos(int W, int nw) {
+    const int wide_blocks = nw * fbs_fill_blocks(W + 1), bx = blockIdx.x;
+    const bool wide = bx < wide_blocks;
+    const int r = wide ? bx : bx - wide_blocks, per = fbs_fill_blocks(wide ? W + 1 : W);
+    k = (wide ? 0 : nw) + r / per;
+    w = wide ? W + 1 : W;
+    d0 = (r % per) * LANE_BLOCK;
+  }
+};
+
+// One row per thread. UNI: every thread of the block shares the hi entry (2^(w/2) >= LANE_BLOCK, i.e. w >= 16), whose
 // pair and inverse, with mu and R^2, the block stages once in LDS (sh); otherwise they come from global memory (round 5:
 // a global load per digit of the hi entry, each waited, had made the fill latency-bound at 4.0 ns per row -- 34 ms of a
 // fresh key's 95 ms at W = 16, 1.57 s of the W = 22 build).
 template <int S, bool UNI>
-__device__ __forceinline__ void fbs_fill_body(const FbpHalf* halves, const FbsConst* cst, int W, uint4* table0, uint4* table1,
-                                              const GuardArgs& g, const uint32_t* sh) {
+__device__ __forceinline__ void fbs_fill_body(const FbpHalf* halves, const FbsConst* cst, const FbsFillPos& pos, size_t row0,
+                                              uint4* table0, uint4* table1, const GuardArgs& g, const uint32_t* sh) {
   using G = FbsGeom<S>;
   constexpr int TQ = fbs_row_quads<S>();
-  const int ent = 1 << W;
-  const int per = (ent + LANE_BLOCK - 1) / LANE_BLOCK;
-  const int k = blockIdx.x / per;
-  const int d = (blockIdx.x % per) * LANE_BLOCK + threadIdx.x;
-  if (d >= ent) return;
+  const int k = pos.k;
+  const int d = pos.d0 + threadIdx.x;
+  if (d >= (1 << pos.w)) return;
   const int half = blockIdx.y;
   const FbpHalf* H = halves + half;
   const FbsConst* C = cst + half;
   uint4* table = half ? table1 : table0;
-  const int LO = W / 2;
+  const int LO = pos.w / 2;
   const int dl = (int)FPAI_GUARD_IDX(g, GS_FILL_LOHI, (unsigned)(d & ((1 << LO) - 1)), FB_LO, d),
             dh = (int)FPAI_GUARD_IDX(g, GS_FILL_LOHI, (unsigned)(d >> LO), FB_LO, d);
   const uint32_t* lo = H->lohi + (((size_t)k * 2 + 0) * FB_LO + dl) * 2 * S;
@@ -523,7 +539,7 @@ __device__ __forceinline__ void fbs_fill_body(const FbpHalf* halves, const FbsCo
       inc = v >> lane::LB;
     }
   }
-  uint4* dst = table + FPAI_GUARD_IDX(g, GS_FILL_ROW, (size_t)k * ent + d, g.rows, d) * TQ;
+  uint4* dst = table + FPAI_GUARD_IDX(g, GS_FILL_ROW, row0 + d, g.rows, d) * TQ;
   fbs_store_limbs<S>(dst, A, std::make_integer_sequence<int, G::QA>{});
   fbs_store_limbs<S>(dst + G::QA, ap, std::make_integer_sequence<int, G::QAP>{});   // a' < R: limb S is zero
   // b = B_T A_T^-1, b R: after a and a' are stored (their registers free again)
@@ -548,14 +564,15 @@ __device__ __forceinline__ void fbs_fill_body(const FbpHalf* halves, const FbsCo
 }
 
 template <int S>
-__global__ __launch_bounds__(LANE_BLOCK, 2) void k_fbs_fill(const FbpHalf* halves, const FbsConst* cst, int K, int W, uint4* table0,
+__global__ __launch_bounds__(LANE_BLOCK, 2) void k_fbs_fill(const FbpHalf* halves, const FbsConst* cst, int W, int nw, uint4* table0,
                                                          uint4* table1, GuardArgs g) {
   __shared__ uint32_t sh[5 * S + 2];   // hi pair [2S], its inverse [S], mu [S + 2], R^2 mod p [S]
-  (void)K;
-  const int LO = W / 2;
-  if ((1 << LO) >= LANE_BLOCK) {   // block-uniform (W is a kernel argument)
-    const int per = (1 << W) / LANE_BLOCK, k = blockIdx.x / per;
-    const int dh = (int)FPAI_GUARD_IDX(g, GS_FILL_LOHI, (unsigned)(((blockIdx.x % per) * LANE_BLOCK) >> LO), FB_LO, k);
+  const FbsFillPos pos(W, nw);
+  const size_t row0 = fb_cut_row(pos.k, W, nw);   // the position's first row
+  const int LO = pos.w / 2;
+  if ((1 << LO) >= LANE_BLOCK) {   // block-uniform (the position follows from blockIdx.x)
+    const int k = pos.k;
+    const int dh = (int)FPAI_GUARD_IDX(g, GS_FILL_LOHI, (unsigned)(pos.d0 >> LO), FB_LO, k);
     const FbpHalf* H = halves + blockIdx.y;
     const FbsConst* C = cst + blockIdx.y;
     const uint32_t* hi = H->lohi + (((size_t)k * 2 + 1) * FB_LO + dh) * 2 * S;
@@ -563,9 +580,9 @@ __global__ __launch_bounds__(LANE_BLOCK, 2) void k_fbs_fill(const FbpHalf* halve
     for (int i = threadIdx.x; i < 5 * S + 2; i += LANE_BLOCK)
       sh[i] = i < 2 * S ? hi[i] : i < 3 * S ? ih[i - 2 * S] : i < 4 * S + 2 ? C->mu[i - 3 * S] : C->r2[i - 4 * S - 2];
     __syncthreads();
-    fbs_fill_body<S, true>(halves, cst, W, table0, table1, g, sh);
+    fbs_fill_body<S, true>(halves, cst, pos, row0, table0, table1, g, sh);
   } else {
-    fbs_fill_body<S, false>(halves, cst, W, table0, table1, g, nullptr);
+    fbs_fill_body<S, false>(halves, cst, pos, row0, table0, table1, g, nullptr);
   }
 }
 

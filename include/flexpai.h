@@ -120,6 +120,15 @@ typedef struct pai_comm pai_comm;
                                     back: the window of the resident tables, which is the largest one <= the
                                     requested window whose 2 K 2^W rows fit $FLEXPAI_FB_MAX_BYTES (default:
                                     free device memory less max(4 GiB, 1/12 of the device)).
+                                    1024/2048-bit keys (Shoup rows): when that window is below the requested one,
+                                    the exponent is cut unevenly if that saves a whole digit within the same
+                                    budget -- the smallest digit count that fits, no digit wider than the request,
+                                    the first few one bit wider than the rest (csrc/fb_cut.hpp; nb = 2048 on an
+                                    idle MI355X, 23 requested: 12 digits of 23 bits + 34 of 22, 46 digits in 2 x
+                                    109 GB instead of 47 in 2 x 88.3 GB). The window read back is then the
+                                    narrower width (22), pai_ctx_fixed_base_info's digits the true count (46),
+                                    pai_ctx_fixed_base_setup's bytes the true size. Ciphertexts do not depend on
+                                    the cut. 4096-bit keys and the public tables keep the uniform cut.
                                     $FLEXPAI_FB_WINDOW=auto: a process holding ONE private key asks for 24 and
                                     gets the largest window whose tables fit $FLEXPAI_FB_AUTO_FRAC (default
                                     0.75) of the free memory (W = 22 at nb = 2048, 21 at nb = 4096 on an idle
