@@ -54,6 +54,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_mul.hpp"
 #include "engine_mm.hpp"
 #include "engine_obf.hpp"
+#include "engine_pack.hpp"
 #include "engine_crtw.hpp"
 #include "engine_pe1.hpp"
 #include "engine_pe4.hpp"
@@ -257,6 +258,12 @@ struct pai_ctx {
   void* d_obf = nullptr;
   size_t obf_bytes = 0;
   int obf_chunk = 262144;
+  // packed plaintexts (kernels_pack.hpp): the zero plaintexts, exponents and statuses of the encryption that yields r^n
+  // (pai_encrypt_packed_dev); the exponents, values, statuses and raw plaintexts of the decrypt chain ahead of k_unpack
+  // (pai_decrypt_packed_dev); and k_unpack's constants, the words of n, max_int and n - max_int
+  void* d_pack = nullptr;
+  size_t pack_bytes = 0;
+  uint32_t* d_pack_consts = nullptr;
   // fused matrix product (kernels_mm.hpp): PAI_OPT_MATMUL_FUSED / PAI_OPT_MATMUL_PATH
   bool mm_fused = true;
   int mm_path = 0;              // last pai_matmul[_dev] call: 0 none yet, 1 term path, 2 fused
@@ -366,6 +373,7 @@ pai_ctx::~pai_ctx() {
   }
   if (d_plain) (void)hipFree(d_plain);
   if (d_obf) (void)hipFree(d_obf);
+  if (d_pack) (void)hipFree(d_pack);
   if (d_seg) (void)hipFree(d_seg);
   if (d_addplan) (void)hipFree(d_addplan);
 }
@@ -3611,6 +3619,125 @@ int pai_decrypt_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size
   return fail(PAI_ERR_KEY, "unsupported group size");
 }
 
+// ------------------------------------------------------------------ packed plaintexts (kernels_pack.hpp)
+static int pack_layout(const pai_ctx* c, const pai_pack_layout* l, PackLayout* out) {
+  if (!l) return fail(PAI_ERR_ARG, "packed layout: null");
+  if (l->slot_bits < 16 || l->slot_bits > 64 || l->slot_bits % 8)
+    return fail(PAI_ERR_ARG, "packed layout: slot_bits must be a multiple of 8 in [16, 64]");
+  if (l->value_bits < 2 || l->value_bits > l->slot_bits)
+    return fail(PAI_ERR_ARG, "packed layout: value_bits must be in [2, slot_bits]");
+  if (l->slots < 1 || l->slots > (c->nb - 2) / l->slot_bits)
+    return fail(PAI_ERR_ARG, "packed layout: slots must be in [1, (key_bits - 2) / slot_bits]");
+  *out = PackLayout{l->slot_bits, l->value_bits, l->exponent, l->slots};
+  return 0;
+}
+
+int pai_pack_max_slots(const pai_ctx* c, int slot_bits, int* slots) {
+  if (!c || !slots) return fail(PAI_ERR_ARG, "pai_pack_max_slots: null argument");
+  if (slot_bits < 16 || slot_bits > 64 || slot_bits % 8)
+    return fail(PAI_ERR_ARG, "pai_pack_max_slots: slot_bits must be a multiple of 8 in [16, 64]");
+  *slots = (c->nb - 2) / slot_bits;
+  return 0;
+}
+
+// E0 = the encryption of ceil(N / slots) int64 zeros goes straight into d_ct by pai_encrypt_dev's own route (skipped for
+// PAI_OBF_NONE), then one k_pack_mul forms c0 of every ciphertext and multiplies in place.
+int pai_encrypt_packed_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, const pai_pack_layout* layout, int obf_mode,
+                           const uint32_t* d_r_words, size_t r_stride_words, size_t r_words, const uint8_t* rng_key32,
+                           uint64_t index_base, uint32_t* d_ct, int32_t* d_status, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  PackLayout lay;
+  int rc = pack_layout(c, layout, &lay);
+  if (rc) return rc;
+  if (N == 0) return 0;
+  if (dtype < 0 || dtype > 2 || !d_x || !d_ct) return fail(PAI_ERR_ARG, "pai_encrypt_packed_dev: bad arguments");
+  if (obf_mode == PAI_OBF_GIVEN && (!d_r_words || r_words == 0 || r_words > (size_t)c->ct_words))
+    return fail(PAI_ERR_ARG, "pai_encrypt_packed_dev: r must be given with 0 < r_words <= ct_words");
+  if (obf_mode == PAI_OBF_RNG && !rng_key32) return fail(PAI_ERR_ARG, "pai_encrypt_packed_dev: rng key required");
+  if (obf_mode < 0 || obf_mode > 2) return fail(PAI_ERR_ARG, "pai_encrypt_packed_dev: bad obf_mode");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t C = (N + lay.k - 1) / lay.k;
+  if (obf_mode != PAI_OBF_NONE) {
+    const size_t x_bytes = align16(C * 8), e_bytes = align16(C * 4);
+    if ((rc = ensure_buf(&c->d_pack, &c->pack_bytes, x_bytes + 2 * e_bytes))) return rc;
+    int64_t* zeros = (int64_t*)c->d_pack;
+    int32_t* ex = (int32_t*)((char*)zeros + x_bytes);
+    int32_t* status = (int32_t*)((char*)ex + e_bytes);
+    HIPCHK(hipMemsetAsync(zeros, 0, C * 8, st));
+    if ((rc = encrypt_dev(c, PAI_I64, zeros, C, PAI_EXP_AUTO, 0, obf_mode, d_r_words, r_stride_words, r_words, rng_key32,
+                          index_base, d_ct, ex, status, st)))
+      return rc;
+  }
+  int occ = 1;
+  if (pack_occupancy(c->tpi_e, &occ)) return fail(PAI_ERR_KEY, "unsupported group size");
+  const int gpb = BLOCK / c->tpi_e;
+  PackMulParams p{};
+  p.x = d_x;
+  p.dtype = dtype;
+  p.nvals = (long long)N;
+  p.lay = lay;
+  p.obf = obf_mode;
+  p.ct = d_ct;
+  p.status = d_status;
+  p.n = (long long)C;
+  p.N = c->d_N;
+  p.R2 = c->d_R2;
+  p.nl = c->d_nl;
+  p.mprime = c->mprime_N;
+  p.ct_words = c->ct_words;
+  p.n_limbs = (c->nb + LB - 1) / LB;
+  p.m_limbs = (lay.k * lay.sb - 1 + LB - 1) / LB;   // |M| < 2^(k sb - 1)
+  const int grid = (int)std::max<long long>(1, std::min<long long>((p.n + gpb - 1) / gpb, (long long)occ * c->cus));
+  HIPCHK(pack_launch(c->tpi_e, p, grid, st));
+  return 0;
+}
+
+// The decrypt chain pai_decrypt_dev picks for these ciphertexts, with the raw plaintexts requested, then k_unpack.
+int pai_decrypt_packed_dev(pai_ctx* c, const uint32_t* d_ct, const pai_pack_layout* layout, size_t N, double* d_val,
+                           int64_t* d_mant, int32_t* d_status, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  PackLayout lay;
+  int rc = pack_layout(c, layout, &lay);
+  if (rc) return rc;
+  if (!c->has_priv) return fail(PAI_ERR_NOPRIV, "pai_decrypt_packed: context has no private key");
+  if (N == 0) return 0;
+  if (!d_ct || !d_val || !d_status) return fail(PAI_ERR_ARG, "pai_decrypt_packed_dev: bad arguments");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t C = (N + lay.k - 1) / lay.k, PW = c->pt_words;
+  if (!c->d_pack_consts) {
+    const HBig maxint = sub(div_small(c->n, 3), HBig(1));   // keypair.py:29
+    std::vector<uint32_t> cs = c->n.words(PW);
+    append(cs, maxint.words(PW));
+    append(cs, sub(c->n, maxint).words(PW));
+    if ((rc = upload_to(c->allocs, cs, &c->d_pack_consts))) return rc;
+  }
+  const size_t e_bytes = align16(C * 4), v_bytes = align16(C * 8), raw_bytes = align16(C * PW * 4);
+  if ((rc = ensure_buf(&c->d_pack, &c->pack_bytes, 2 * e_bytes + v_bytes + raw_bytes))) return rc;
+  double* val = (double*)c->d_pack;
+  uint32_t* raw = (uint32_t*)((char*)val + v_bytes);
+  int32_t* ex = (int32_t*)((char*)raw + raw_bytes);
+  int32_t* status = (int32_t*)((char*)ex + e_bytes);
+  HIPCHK(hipMemsetAsync(ex, 0, C * 4, st));
+  if ((rc = pai_decrypt_dev(c, d_ct, ex, C, val, nullptr, status, raw, stream))) return rc;
+  UnpackParams u{};
+  u.raw = raw;
+  u.n = (long long)C;
+  u.nvals = (long long)N;
+  u.lay = lay;
+  u.val = d_val;
+  u.mant = d_mant;
+  u.status = d_status;
+  u.consts = c->d_pack_consts;
+  u.pt_words = (int)PW;
+  const int grid = (int)std::max<long long>(1, std::min<long long>((u.n + UNPACK_CPB - 1) / UNPACK_CPB, 8ll * c->cus));
+  HIPCHK(unpack_launch(u, grid, st));
+  return 0;
+}
+
 // ------------------------------------------------------------------ host-buffer entry points
 struct DevScope {
   std::vector<void*> ptrs;
@@ -4591,6 +4718,117 @@ int pai_decrypt(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, do
   if (mant_out) HIPCHK(hipMemcpyAsync(mant_out, dmant, N * 8, hipMemcpyDeviceToHost, sc));
   HIPCHK(hipMemcpyAsync(status_out, dst, N * 4, hipMemcpyDeviceToHost, sc));
   if (raw_out) HIPCHK(hipMemcpyAsync(raw_out, draw, N * P * 4, hipMemcpyDeviceToHost, sc));
+  HIPCHK(hipStreamSynchronize(sc));
+  return 0;
+}
+
+// Packed plaintexts on host buffers: the values go up once, the ciphertexts are cut into chunks like pai_encrypt's (a
+// chunk of n ciphertexts takes the n slots values behind it) and drain through the pinned slots; one sampler decision
+// for the call, counted in ciphertexts (ObfCall).
+int pai_encrypt_packed(pai_ctx* c, int dtype, const void* x, size_t N, const pai_pack_layout* layout, int obf_mode,
+                       const uint8_t* r_le, size_t r_stride_bytes, size_t r_bytes, const uint8_t* rng_key32,
+                       uint64_t index_base, uint32_t* ct_out, int32_t* status_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  PackLayout lay;
+  int rc = pack_layout(c, layout, &lay);
+  if (rc) return rc;
+  if (N == 0) return 0;
+  if (dtype < 0 || dtype > 2 || !x || !ct_out) return fail(PAI_ERR_ARG, "pai_encrypt_packed: bad arguments");
+  if (obf_mode < 0 || obf_mode > 2) return fail(PAI_ERR_ARG, "pai_encrypt_packed: bad obf_mode");
+  if (obf_mode == PAI_OBF_GIVEN && (!r_le || r_bytes == 0 || r_bytes > (size_t)c->ct_words * 4))
+    return fail(PAI_ERR_ARG, "pai_encrypt_packed: r must be given with 0 < r_bytes <= 4 ct_words");
+  if (obf_mode == PAI_OBF_RNG && !rng_key32) return fail(PAI_ERR_ARG, "pai_encrypt_packed: rng key required");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t esz = dtype == PAI_F32 ? 4 : 8, W = c->ct_words, K = lay.k, C = (N + K - 1) / K;
+  const size_t r_words = obf_mode == PAI_OBF_GIVEN ? (r_bytes + 3) / 4 : 0;
+  const size_t r_cnt = obf_mode == PAI_OBF_GIVEN ? (r_stride_bytes ? C : 1) : 0;
+  size_t CH;
+  int nch;
+  if ((rc = host_pipe(c, C, carve_bytes({N * esz, C * W * 4, N * 4, r_cnt * r_words * 4}), W * 4, &CH, &nch))) return rc;
+  Carve cv{(char*)c->d_hostio};
+  void* dx = cv.take<uint8_t>(N * esz);
+  uint32_t* dct = cv.take<uint32_t>(C * W);
+  int32_t* dst = cv.take<int32_t>(N);
+  uint32_t* dr = cv.take<uint32_t>(r_cnt * r_words);
+  hipStream_t sc = c->s_comp, sy = c->s_copy;
+  HIPCHK(hipMemcpyAsync(dx, x, N * esz, hipMemcpyHostToDevice, sc));
+  if (r_cnt) {
+    std::vector<uint32_t> hr(r_cnt * r_words, 0);
+    for (size_t i = 0; i < r_cnt; ++i) std::memcpy(&hr[i * r_words], r_le + i * r_stride_bytes, r_bytes);
+    HIPCHK(hipMemcpyAsync(dr, hr.data(), hr.size() * 4, hipMemcpyHostToDevice, sc));
+    HIPCHK(hipStreamSynchronize(sc));   // hr is released at the end of this scope
+  }
+  const size_t r_stride_words = r_stride_bytes ? r_words : 0;
+  ObfCall oc(c, obf_mode, (long long)C);
+  for (int i = 0; i < nch; ++i) {
+    const size_t off = (size_t)i * CH, n = std::min(CH, C - off), v0 = off * K, nv = std::min(n * K, N - v0);
+    rc = pai_encrypt_packed_dev(c, dtype, (const char*)dx + v0 * esz, nv, layout, obf_mode,
+                                r_cnt ? dr + off * r_stride_words : nullptr, r_stride_words, r_words, rng_key32,
+                                index_base + off, dct + off * W, dst + v0, sc);
+    if (rc) {
+      (void)hipStreamSynchronize(sc);
+      return rc;
+    }
+    HIPCHK(hipEventRecord(c->hev[i], sc));
+  }
+  auto d2h = [&](int i) -> int {
+    const size_t off = (size_t)i * CH, n = std::min(CH, C - off);
+    HIPCHK(hipStreamWaitEvent(sy, c->hev[i], 0));
+    HIPCHK(hipMemcpyAsync(c->h_pin[i & 1], dct + off * W, n * W * 4, hipMemcpyDeviceToHost, sy));
+    HIPCHK(hipEventRecord(c->pev[i], sy));
+    return 0;
+  };
+  if ((rc = d2h(0))) return rc;
+  for (int i = 0; i < nch; ++i) {
+    if (i + 1 < nch && (rc = d2h(i + 1))) return rc;   // its slot's previous chunk (i - 1) is consumed
+    const size_t off = (size_t)i * CH, n = std::min(CH, C - off);
+    HIPCHK(hipEventSynchronize(c->pev[i]));
+    par_copy(ct_out + off * W, c->h_pin[i & 1], n * W * 4);
+  }
+  if (status_out) HIPCHK(hipMemcpyAsync(status_out, dst, N * 4, hipMemcpyDeviceToHost, sc));
+  HIPCHK(hipStreamSynchronize(sc));
+  HIPCHK(hipStreamSynchronize(sy));
+  return 0;
+}
+
+int pai_decrypt_packed(pai_ctx* c, const uint32_t* ct, const pai_pack_layout* layout, size_t N, double* val_out,
+                       int64_t* mant_out, int32_t* status_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  PackLayout lay;
+  int rc = pack_layout(c, layout, &lay);
+  if (rc) return rc;
+  if (!c->has_priv) return fail(PAI_ERR_NOPRIV, "pai_decrypt_packed: context has no private key");
+  if (N == 0) return 0;
+  if (!ct || !val_out || !status_out) return fail(PAI_ERR_ARG, "pai_decrypt_packed: null buffer");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t W = c->ct_words, K = lay.k, C = (N + K - 1) / K;
+  size_t CH;
+  int nch;
+  if ((rc = host_pipe(c, C, carve_bytes({C * W * 4, N * 8, N * 8, N * 4}), W * 4, &CH, &nch))) return rc;
+  Carve cv{(char*)c->d_hostio};
+  uint32_t* dct = cv.take<uint32_t>(C * W);
+  double* dval = cv.take<double>(N);
+  int64_t* dmant = cv.take<int64_t>(N);
+  int32_t* dst = cv.take<int32_t>(N);
+  hipStream_t sc = c->s_comp, sy = c->s_copy;
+  HostCall hc(c);
+  for (int i = 0; i < nch; ++i) {
+    const size_t off = (size_t)i * CH, n = std::min(CH, C - off), v0 = off * K, nv = std::min(n * K, N - v0);
+    if (i >= 2) HIPCHK(hipEventSynchronize(c->hev[i - 2]));   // the slot's previous upload is done
+    par_copy(c->h_pin[i & 1], ct + off * W, n * W * 4);
+    HIPCHK(hipMemcpyAsync(dct + off * W, c->h_pin[i & 1], n * W * 4, hipMemcpyHostToDevice, sy));
+    HIPCHK(hipEventRecord(c->hev[i], sy));
+    HIPCHK(hipStreamWaitEvent(sc, c->hev[i], 0));
+    if ((rc = pai_decrypt_packed_dev(c, dct + off * W, layout, nv, dval + v0, dmant + v0, dst + v0, sc))) {
+      (void)hipStreamSynchronize(sc);
+      return rc;
+    }
+  }
+  HIPCHK(hipMemcpyAsync(val_out, dval, N * 8, hipMemcpyDeviceToHost, sc));
+  if (mant_out) HIPCHK(hipMemcpyAsync(mant_out, dmant, N * 8, hipMemcpyDeviceToHost, sc));
+  HIPCHK(hipMemcpyAsync(status_out, dst, N * 4, hipMemcpyDeviceToHost, sc));
   HIPCHK(hipStreamSynchronize(sc));
   return 0;
 }

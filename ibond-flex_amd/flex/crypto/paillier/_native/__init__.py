@@ -45,7 +45,9 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_segment_add", "pai_segment_add_dev", "pai_comm_unique_id", "pai_comm_create", "pai_comm_destroy",
             "pai_allgather_dev", "pai_allgather_shards_dev", "pai_release_table_cache", "pai_debug_encrypt_route",
             "pai_next_prime", "pai_prime_last_times", "pai_prime_test", "pai_debug_prime_sieve",
-            "pai_obfuscate", "pai_obfuscate_dev")
+            "pai_obfuscate", "pai_obfuscate_dev",
+            "pai_pack_max_slots", "pai_encrypt_packed", "pai_encrypt_packed_dev", "pai_decrypt_packed",
+            "pai_decrypt_packed_dev")
 PAI_COMM_ID_BYTES = 128
 
 _lib = None
@@ -99,6 +101,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_decrypt_dev.argtypes = [P, P, P, S, P, P, P, P, P]
         lib.pai_obfuscate.argtypes = [P, P, S, I, P, S, S, P, U64, P]
         lib.pai_obfuscate_dev.argtypes = [P, P, S, I, P, S, S, P, U64, P, P]
+        lib.pai_pack_max_slots.argtypes = [P, I, P]
+        lib.pai_encrypt_packed.argtypes = [P, I, P, S, P, I, P, S, S, P, U64, P, P]
+        lib.pai_encrypt_packed_dev.argtypes = [P, I, P, S, P, I, P, S, S, P, U64, P, P, P]
+        lib.pai_decrypt_packed.argtypes = [P, P, P, S, P, P, P]
+        lib.pai_decrypt_packed_dev.argtypes = [P, P, P, S, P, P, P, P]
         lib.pai_mul.argtypes = [P, P, P, S, I, P, S, P, P, P]
         lib.pai_mul_dev.argtypes = [P, P, P, S, I, P, S, P, P, P, P]
         lib.pai_add_plain.argtypes = [P, P, P, S, I, P, S, P, P, P]
@@ -599,6 +606,53 @@ class Context:
                                          r_stride, r_bytes, key, index_base, _ptr(out)))
         return out
 
+    # ----------------------------------------------------------------- packed plaintexts (include/flexpai.h)
+    def pack_max_slots(self, slot_bits: int) -> int:
+        """floor((key_bits - 2) / slot_bits), the most slots a layout of this key may have."""
+        k = ctypes.c_int()
+        self._chk(self.lib.pai_pack_max_slots(self._h, int(slot_bits), ctypes.byref(k)))
+        return k.value
+
+    def encrypt_packed(self, x: np.ndarray, layout, obf_mode: int = PAI_OBF_RNG, r: Optional[Sequence[int]] = None,
+                       rng_key: Optional[bytes] = None, index_base: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """pai_encrypt_packed: x (float32 / float64 / int64) into ceil(N / slots) ciphertexts under `layout`
+        (slot_bits, value_bits, exponent, slots). r and index_base count ciphertexts. Returns (words [C, ct_words],
+        statuses [N])."""
+        x = np.ascontiguousarray(x)
+        dt = scalar_dtype(x)
+        N = x.size
+        lay = pack_layout(layout)
+        C = -(-N // lay.slots) if lay.slots > 0 else 0
+        ct = np.empty((C, self.ct_words), dtype=np.uint32)
+        st = np.empty(N, dtype=np.int32)
+        r_buf, r_stride, r_bytes = None, 0, 0
+        if obf_mode == PAI_OBF_GIVEN:
+            r_bytes = self.ct_words * 4
+            r_buf = np.frombuffer(b"".join(int_to_le(v, r_bytes) for v in r), dtype=np.uint8).copy()
+            r_stride = r_bytes
+        key = rng_key if rng_key is not None else os.urandom(32)
+        self.calls["pai_encrypt_packed"] += 1
+        self._chk(self.lib.pai_encrypt_packed(self._h, dt, _ptr(x), N, ctypes.byref(lay), obf_mode,
+                                              _ptr(r_buf) if r_buf is not None else None, r_stride, r_bytes, key,
+                                              index_base, _ptr(ct), _ptr(st)))
+        return ct, st
+
+    def decrypt_packed(self, ct: np.ndarray, layout, N: int):
+        """pai_decrypt_packed: the first N values of the packed ciphertexts ct [ceil(N / slots), ct_words]. Returns
+        (val float64 [N], mant int64 [N], statuses [N])."""
+        ct = np.ascontiguousarray(ct, dtype=np.uint32)
+        lay = pack_layout(layout)
+        N = int(N)
+        C = -(-N // lay.slots) if lay.slots > 0 else 0
+        if lay.slots > 0 and (ct.ndim != 2 or ct.shape != (C, self.ct_words)):
+            raise ValueError(f"ciphertext buffer shape {ct.shape} does not match ({C}, {self.ct_words})")
+        val = np.empty(N, dtype=np.float64)
+        mant = np.empty(N, dtype=np.int64)
+        st = np.empty(N, dtype=np.int32)
+        self.calls["pai_decrypt_packed"] += 1
+        self._chk(self.lib.pai_decrypt_packed(self._h, _ptr(ct), ctypes.byref(lay), N, _ptr(val), _ptr(mant), _ptr(st)))
+        return val, mant, st
+
     def add(self, cts: Sequence[np.ndarray], exps: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
         k = len(cts)
         cts = [np.ascontiguousarray(c, dtype=np.uint32) for c in cts]
@@ -695,6 +749,23 @@ class Context:
         self._chk(self.lib.pai_decrypt(self._h, _ptr(ct), _ptr(exp), N, _ptr(val), _ptr(mant), _ptr(st),
                                     _ptr(raw) if raw is not None else None))
         return val, mant, st, raw
+
+
+class PackLayoutC(ctypes.Structure):
+    """pai_pack_layout (include/flexpai.h)."""
+    _fields_ = [("slot_bits", ctypes.c_int32), ("value_bits", ctypes.c_int32), ("exponent", ctypes.c_int32),
+                ("slots", ctypes.c_int32)]
+
+
+def pack_layout(layout) -> PackLayoutC:
+    """A pai_pack_layout from (slot_bits, value_bits, exponent, slots) or from an object with those attributes."""
+    if isinstance(layout, PackLayoutC):
+        return layout
+    if isinstance(layout, (tuple, list)):
+        sb, vb, e, k = layout
+    else:
+        sb, vb, e, k = layout.slot_bits, layout.value_bits, layout.exponent, layout.slots
+    return PackLayoutC(int(sb), int(vb), int(e), int(k))
 
 
 def scalar_dtype(x: np.ndarray) -> int:

@@ -90,9 +90,31 @@ class PaillierDecryptor(object):
                 values.append(FixedPointNumber(raw[i], int(exps[i]), self.pub_key.n, self.pub_key.max_int).decode())
         return np.array(values).reshape(s)
 
+    def _decrypt_packed(self, buf) -> np.ndarray:
+        """A PackedCiphertextBuffer (packed_buffer.py) in ONE pai_decrypt_packed call: float64 values of buf.shape,
+        int64 when the layout's exponent is 0."""
+        from . import _native, _runtime
+        from .packed_buffer import host_decrypt_packed
+        if buf.public_key != self.pub_key:
+            raise ValueError("encrypted_number was encrypted against a different key!")
+        e = buf.layout.exponent
+        if buf.count == 0:
+            return np.zeros(buf.shape, dtype=np.int64 if e == 0 else np.float64)
+        if _runtime.gpu_available():
+            val, mant, st = _runtime.context(self.pub_key, self.priv_key).decrypt_packed(buf.words, buf.layout, buf.count)
+            if np.any(st == _native.EL_OVERFLOW):
+                raise OverflowError('Overflow detected in decode number')
+        else:
+            mant = np.array(host_decrypt_packed(buf, self.priv_key), dtype=np.int64)
+            val = np.ldexp(mant.astype(np.float64), -4 * e)
+        return (mant if e == 0 else val).reshape(buf.shape)
+
     def decrypt(self, encrypted_number):
-        """decryptor.py:114-127 (plus CiphertextBuffer, cipher_buffer.py)"""
+        """decryptor.py:114-127 (plus CiphertextBuffer, cipher_buffer.py, and PackedCiphertextBuffer)"""
         from .cipher_buffer import CiphertextBuffer
+        from .packed_buffer import PackedCiphertextBuffer
+        if isinstance(encrypted_number, PackedCiphertextBuffer):
+            return self._decrypt_packed(encrypted_number)
         if isinstance(encrypted_number, CiphertextBuffer):
             if encrypted_number.public_key != self.pub_key:
                 raise ValueError("encrypted_number was encrypted against a different key!")

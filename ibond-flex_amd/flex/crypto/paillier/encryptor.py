@@ -127,6 +127,27 @@ class PaillierEncryptor(object):
                 ex[i] = e.exponent
         return CiphertextBuffer(self.pub_key, ct, ex, 1, s)
 
+    def encrypt_packed(self, values: np.ndarray, layout):
+        """Encrypt an array into a PackedCiphertextBuffer (packed_buffer.py): layout.slots values per ciphertext, in
+        ONE pai_encrypt_packed call. ValueError names the first value outside the layout's range."""
+        from . import _native, _runtime
+        from .packed_buffer import PackedCiphertextBuffer, host_encrypt_packed
+        values = np.asarray(values)
+        x, _ = _device_input(values.reshape(-1))
+        if x is None:
+            raise TypeError(f"encrypt_packed: unsupported input dtype {values.dtype}")
+        if layout.key_bits != self.pub_key.n.bit_length():
+            raise ValueError("layout does not belong to a key of this size")
+        if _runtime.gpu_available():
+            ct, st = _runtime.context(self.pub_key).encrypt_packed(x, layout, _native.PAI_OBF_RNG)
+        else:
+            ct, st = host_encrypt_packed(x, layout, self.pub_key)
+        bad = np.flatnonzero(st)
+        if bad.size:
+            raise ValueError(f"encrypt_packed: value at index {int(bad[0])} is outside the layout's range "
+                             f"(|v * 16^{layout.exponent}| <= 2^{layout.value_bits - 1} - 1)")
+        return PackedCiphertextBuffer(self.pub_key, ct, layout, x.size, values.shape, obfuscated=True)
+
     def encrypt(self, value, precision: int = None, random_value: int = None):
         """encryptor.py:99-114"""
         if isinstance(value, np.ndarray):

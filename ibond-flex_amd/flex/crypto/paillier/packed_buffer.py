@@ -1,0 +1,380 @@
+"""Packed plaintexts: many signed fixed-point values per Paillier ciphertext (include/flexpai.h, "Packed plaintexts").
+
+A float32 weight uses about 30 of the ~2046 plaintext bits of a 2048-bit key. A PackedLayout cuts the plaintext into
+`slots` fields of `slot_bits` bits, each holding one signed fixed-point value t = rint(v * 16^exponent) with
+|t| <= 2^(value_bits - 1) - 1; the plaintext is the signed integer M = sum_j t_j 2^(slot_bits j), encrypted like any
+other (m = M mod n), so a packed ciphertext is an ordinary ciphertext of the reference: adding two adds every slot,
+multiplying by an integer scales every slot. Encrypt, add, obfuscate, decrypt and the wire all shrink by `slots`.
+
+    lay = PackedLayout.for_sum(pub_key, max_abs=4.0, exponent=5, terms=3)   # every party agrees on this
+    buf = encryptor.encrypt_packed(weights, lay)                            # ONE pai_encrypt_packed call
+    total = add_packed([PackedCiphertextBuffer.from_wire(w) for w in received])   # ONE k-way pai_add call
+    send(total.to_wire(be_secure=True))                                     # ONE pai_obfuscate call
+    sums = decryptor.decrypt(PackedCiphertextBuffer.from_wire(reply))       # ONE pai_decrypt_packed call
+
+Opt-in, and both peers must be flexpai (like CiphertextBuffer and FLEXPAI_PICKLE_BULK). A slot that overflows into its
+neighbour cannot be seen in the plaintext, so every buffer carries `bound`, an exact Python int with |t| <= bound for
+every slot: sums add the bounds, products scale them, and a result whose bound would pass 2^(slot_bits - 1) - 1 raises
+OverflowError before any GPU call. Only integer scalars are supported (a float scalar would change the exponent of a
+whole ciphertext, which the layout fixes).
+
+Without a GPU the same operations run on Python integers (small arrays only, as in the rest of the package).
+"""
+from __future__ import annotations
+
+import math
+import secrets
+from fractions import Fraction
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import _bigint
+
+_MAGIC = b"FPPK1\0"
+EL_ENC_RANGE = 5
+
+
+class PackedLayout(object):
+    """(slot_bits, value_bits, exponent, slots) for keys of pub_key's size: slot_bits a multiple of 8 in [16, 64],
+    2 <= value_bits <= slot_bits, 1 <= slots <= (key_bits - 2) // slot_bits (the default)."""
+    __slots__ = ("slot_bits", "value_bits", "exponent", "slots", "key_bits")
+
+    def __init__(self, pub_key, slot_bits: int, value_bits: int, exponent: int, slots: Optional[int] = None):
+        nb = pub_key.n.bit_length()
+        slot_bits, value_bits, exponent = int(slot_bits), int(value_bits), int(exponent)
+        if slot_bits % 8 or not 16 <= slot_bits <= 64:
+            raise ValueError("slot_bits must be a multiple of 8 in [16, 64]")
+        if not 2 <= value_bits <= slot_bits:
+            raise ValueError("value_bits must be in [2, slot_bits]")
+        most = (nb - 2) // slot_bits
+        slots = most if slots is None else int(slots)
+        if not 1 <= slots <= most:
+            raise ValueError(f"slots must be in [1, {most}] for a {nb}-bit key and {slot_bits}-bit slots")
+        self.slot_bits, self.value_bits, self.exponent, self.slots, self.key_bits = slot_bits, value_bits, exponent, slots, nb
+
+    @classmethod
+    def for_sum(cls, pub_key, max_abs, exponent: int, terms: int = 1) -> "PackedLayout":
+        """The layout for sums of `terms` values of magnitude at most max_abs at this exponent: the smallest value_bits
+        that hold max_abs * 16^exponent and the smallest slot_bits (a multiple of 8) with ceil(log2 terms) bits above."""
+        if terms < 1:
+            raise ValueError("terms must be at least 1")
+        top = math.ceil(abs(Fraction(max_abs)) * Fraction(16) ** int(exponent))
+        value_bits = max(2, int(top).bit_length() + 1)
+        head = (int(terms) - 1).bit_length()
+        slot_bits = max(16, -(-(value_bits + head) // 8) * 8)
+        if slot_bits > 64:
+            raise ValueError("max_abs * 16^exponent * terms does not fit a 64-bit slot")
+        return cls(pub_key, slot_bits, value_bits, exponent)
+
+    @property
+    def value_max(self) -> int:
+        return (1 << (self.value_bits - 1)) - 1
+
+    @property
+    def slot_max(self) -> int:
+        return (1 << (self.slot_bits - 1)) - 1
+
+    def as_tuple(self):
+        return self.slot_bits, self.value_bits, self.exponent, self.slots
+
+    def __eq__(self, other):
+        return isinstance(other, PackedLayout) and self.as_tuple() == other.as_tuple()
+
+    def __hash__(self):
+        return hash(self.as_tuple())
+
+    def __repr__(self):
+        return "PackedLayout(slot_bits=%d, value_bits=%d, exponent=%d, slots=%d)" % self.as_tuple()
+
+
+# ---------------------------------------------------------------- the contract on Python integers (no GPU)
+def pack_int(ts: Sequence[int], slot_bits: int) -> int:
+    """M = sum_j t_j 2^(slot_bits j): signed, slot 0 least significant."""
+    M = 0
+    for j, t in enumerate(ts):
+        M += int(t) << (slot_bits * j)
+    return M
+
+
+def unpack_int(m: int, n: int, slot_bits: int, slots: int):
+    """The signed digits of the raw plaintext m in [0, n), or None where decoding overflows."""
+    max_int = n // 3 - 1
+    if m <= max_int:
+        M = m
+    elif m >= n - max_int:
+        M = m - n
+    else:
+        return None
+    B, out = 1 << slot_bits, []
+    for _ in range(slots):
+        t = ((M + B // 2) % B) - B // 2
+        out.append(t)
+        M = (M - t) // B
+    return out if M == 0 else None
+
+
+def encode_values(x: np.ndarray, layout: PackedLayout):
+    """(t as Python ints, statuses) of a float32 / float64 / int64 array at the layout's exponent, as the device
+    encodes them; a value out of range is 0 with status EL_ENC_RANGE."""
+    e, lim = layout.exponent, layout.value_max
+    ts, st = [], []
+    for v in x.reshape(-1).tolist():
+        if isinstance(v, float):
+            if math.isnan(v) or math.isinf(v):
+                t = None
+            else:
+                t = 0 if abs(v) < 1e-200 else round(math.ldexp(v, 4 * e))
+        else:
+            t = v << (4 * e) if e >= 0 else round(math.ldexp(float(v), 4 * e))
+        bad = t is None or abs(t) > lim
+        ts.append(0 if bad else t)
+        st.append(EL_ENC_RANGE if bad else 0)
+    return ts, st
+
+
+def _ints(words):
+    from . import _runtime
+    return _runtime.words_to_ints(words)
+
+
+def _to_words(vals, W):
+    from . import _runtime
+    return _runtime.ints_to_words(vals, W)
+
+
+def _gpu() -> bool:
+    from . import _runtime
+    return _runtime.gpu_available()
+
+
+def host_raw_decrypt(c: int, priv_key) -> int:
+    """decryptor.py:33-63 on Python integers: the raw plaintext in [0, n)."""
+    p, q = priv_key.p, priv_key.q
+    mp = (_bigint.powmod(c, p - 1, priv_key.psquare) - 1) // p * priv_key.hp % p
+    mq = (_bigint.powmod(c, q - 1, priv_key.qsquare) - 1) // q * priv_key.hq % q
+    return _bigint.crt(mp, mq, p, q, priv_key.q_inverse, priv_key.public_key.n)
+
+
+class PackedCiphertextBuffer(object):
+    """C = ceil(count / slots) packed ciphertexts: words [C, W], the layout, the number of values and their shape, one
+    obfuscation flag for the buffer, and the exact slot bound."""
+    __slots__ = ("public_key", "words", "layout", "count", "shape", "obfuscated", "bound")
+
+    def __init__(self, public_key, words: np.ndarray, layout: PackedLayout, count: int, shape=None,
+                 obfuscated: bool = False, bound: Optional[int] = None):
+        nb = public_key.n.bit_length()
+        W = (2 * nb + 31) // 32
+        if not isinstance(layout, PackedLayout) or layout.key_bits != nb:
+            raise ValueError("layout does not belong to a key of this size")
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        count = int(count)
+        C = -(-count // layout.slots)
+        if words.shape != (C, W):
+            raise ValueError(f"ciphertext words {words.shape} do not match ({C}, {W}) for {count} values")
+        self.public_key, self.words, self.layout, self.count = public_key, words, layout, count
+        self.shape = tuple(int(v) for v in shape) if shape is not None else (count,)
+        if int(np.prod(self.shape, dtype=np.int64)) != count:
+            raise ValueError("shape does not match the number of values")
+        self.obfuscated = bool(obfuscated)
+        self.bound = layout.value_max if bound is None else int(bound)
+        if not 0 <= self.bound <= layout.slot_max:
+            raise OverflowError(f"slot bound {self.bound} exceeds 2^(slot_bits - 1) - 1")
+
+    def __repr__(self):
+        return f"PackedCiphertextBuffer(shape={self.shape}, {self.layout!r}, bound={self.bound})"
+
+    @property
+    def size(self) -> int:
+        return self.count
+
+    def _like(self, words, bound, obfuscated=False):
+        return PackedCiphertextBuffer(self.public_key, words, self.layout, self.count, self.shape, obfuscated, bound)
+
+    def _exps(self):
+        return np.full(self.words.shape[0], self.layout.exponent, dtype=np.int32)
+
+    def _check_peer(self, other):
+        if not isinstance(other, PackedCiphertextBuffer):
+            raise TypeError(f"unsupported operand {type(other)} for a packed buffer")
+        if other.public_key != self.public_key:
+            raise ValueError("add two numbers have different public key!")
+        if other.layout != self.layout:
+            raise ValueError(f"layouts differ: {self.layout!r} and {other.layout!r}")
+        if other.shape != self.shape:
+            raise ValueError(f"shapes {self.shape} and {other.shape} differ")
+
+    def _check_bound(self, bound: int):
+        if bound > self.layout.slot_max:
+            raise OverflowError(f"slot bound {bound} would exceed 2^{self.layout.slot_bits - 1} - 1: a slot could "
+                                "overflow into its neighbour")
+
+    # ---------------------------------------------------------------- operators
+    def __add__(self, other):
+        return add_packed([self, other])
+
+    def __sub__(self, other):
+        self._check_peer(other)
+        self._check_bound(self.bound + other.bound)
+        return add_packed([self, other * -1])
+
+    def __mul__(self, s):
+        if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)):
+            raise TypeError("a packed buffer multiplies by integers only (a float would change the exponent)")
+        s = int(s)
+        if abs(s) >= 1 << 63:
+            raise OverflowError("scalar must be below 2^63 in magnitude")
+        bound = self.bound * abs(s)
+        self._check_bound(bound)
+        if _gpu():
+            from . import _runtime
+            out, _, _ = _runtime.context(self.public_key).mul(self.words, self._exps(), np.array([s], dtype=np.int64))
+        else:
+            nsq = self.public_key.nsquare
+            out = _to_words([_bigint.scalar_pow(c, abs(s), nsq, s < 0) if s else 1 for c in _ints(self.words)],
+                            self.words.shape[1])
+        return self._like(out, bound)
+
+    __rmul__ = __mul__
+
+    def apply_obfuscation(self) -> "PackedCiphertextBuffer":
+        """Re-randomise every ciphertext in ONE pai_obfuscate call, unless the flag is already set. Returns self."""
+        if self.obfuscated or self.words.shape[0] == 0:
+            self.obfuscated = True
+            return self
+        if _gpu():
+            from .obfuscator import apply_obfuscation_array
+            self.words = apply_obfuscation_array(self.words, self.public_key)
+        else:
+            n, nsq = self.public_key.n, self.public_key.nsquare
+            self.words = _to_words([c * _bigint.powmod(secrets.randbelow(n - 1) + 1, n, nsq) % nsq
+                                    for c in _ints(self.words)], self.words.shape[1])
+        self.obfuscated = True
+        return self
+
+    # ---------------------------------------------------------------- wire
+    def to_wire(self, be_secure: bool = False) -> bytes:
+        """magic | u32 n bytes | n | u32 W | i32 slot_bits, value_bits, exponent, slots | u64 count | u32 ndim |
+        i64 shape[ndim] | u32 bound bytes | bound | u8 flags (bit 0: obfuscated) | u32 words[C][W], little-endian.
+        be_secure=True: apply_obfuscation() first."""
+        if be_secure:
+            self.apply_obfuscation()
+        n = self.public_key.n
+        nbytes = (n.bit_length() + 7) // 8
+        bb = max(1, (self.bound.bit_length() + 7) // 8)
+        return b"".join([_MAGIC, np.uint32(nbytes).tobytes(), n.to_bytes(nbytes, "little"),
+                         np.uint32(self.words.shape[1]).tobytes(),
+                         np.asarray(self.layout.as_tuple(), dtype="<i4").tobytes(), np.uint64(self.count).tobytes(),
+                         np.uint32(len(self.shape)).tobytes(), np.asarray(self.shape, dtype="<i8").tobytes(),
+                         np.uint32(bb).tobytes(), self.bound.to_bytes(bb, "little"),
+                         bytes([1 if self.obfuscated else 0]), np.ascontiguousarray(self.words, dtype="<u4").tobytes()])
+
+    @classmethod
+    def from_wire(cls, buf, public_key=None) -> "PackedCiphertextBuffer":
+        """Inverse of to_wire. `public_key` (optional) must match the key in the buffer. ValueError for anything
+        malformed: a wrong length or W, an invalid layout, a count above C * slots, a bound above the slot, a word row
+        >= n^2."""
+        from .cipher_array import _rows_below
+        from .keypair import PaillierPublicKey
+        mv = memoryview(buf).cast("B")
+        bad = ValueError("corrupted packed ciphertext buffer")
+        if len(mv) < len(_MAGIC) + 4 or bytes(mv[:len(_MAGIC)]) != _MAGIC:
+            raise ValueError("not a flexpai packed ciphertext buffer")
+        o = len(_MAGIC)
+
+        def take(dtype, cnt=1):
+            nonlocal o
+            size = np.dtype(dtype).itemsize * cnt
+            if cnt < 0 or len(mv) < o + size:
+                raise bad
+            out = np.frombuffer(mv, dtype, cnt, o)
+            o += size
+            return out
+
+        nbytes = int(take("<u4")[0])
+        if nbytes == 0 or nbytes > 1024:
+            raise bad
+        n = int.from_bytes(take(np.uint8, nbytes).tobytes(), "little")
+        W = int(take("<u4")[0])
+        if n < 3 or W != (2 * n.bit_length() + 31) // 32:
+            raise bad
+        sb, vb, e, k = (int(v) for v in take("<i4", 4))
+        count = int(take("<u8")[0])
+        ndim = int(take("<u4")[0])
+        if ndim > 32:
+            raise bad
+        shape = tuple(int(v) for v in take("<i8", ndim))
+        bb = int(take("<u4")[0])
+        if bb == 0 or bb > 16:
+            raise bad
+        bound = int.from_bytes(take(np.uint8, bb).tobytes(), "little")
+        flags = int(take(np.uint8)[0])
+        if public_key is None:
+            public_key = PaillierPublicKey(n)
+        elif public_key.n != n:
+            raise ValueError("packed ciphertext buffer was encrypted under a different public key")
+        try:
+            layout = PackedLayout(public_key, sb, vb, e, k)
+        except ValueError:
+            raise bad from None
+        if any(v < 0 for v in shape) or (int(np.prod(shape, dtype=object)) if shape else 1) != count or flags > 1:
+            raise bad
+        if (len(mv) - o) % (4 * W):
+            raise ValueError("corrupted packed ciphertext buffer (length mismatch)")
+        C = (len(mv) - o) // (4 * W)
+        if count > C * k or C != -(-count // k):
+            raise ValueError("corrupted packed ciphertext buffer (count does not match the ciphertexts)")
+        if bound > layout.slot_max:
+            raise ValueError("corrupted packed ciphertext buffer (bound above the slot)")
+        words = take("<u4", C * W).reshape(C, W).copy()
+        if C and not _rows_below(words, public_key.nsquare):
+            raise ValueError("corrupted packed ciphertext buffer (ciphertext >= n^2)")
+        return cls(public_key, words, layout, count, shape, bool(flags & 1), bound)
+
+
+def add_packed(bufs: Sequence[PackedCiphertextBuffer]) -> PackedCiphertextBuffer:
+    """Slot-wise sum of k packed buffers of one key, layout and shape in ONE k-way add (equal exponents: no alignment).
+    The bound of the sum is the sum of the bounds; OverflowError, before any GPU call, if it passes the slot."""
+    bufs = list(bufs)
+    if not bufs:
+        raise ValueError("add_packed needs at least one buffer")
+    a = bufs[0]
+    if not isinstance(a, PackedCiphertextBuffer):
+        raise TypeError(f"unsupported operand {type(a)} for a packed buffer")
+    for b in bufs[1:]:
+        a._check_peer(b)
+    bound = sum(b.bound for b in bufs)
+    a._check_bound(bound)
+    if len(bufs) == 1:
+        return a
+    if _gpu():
+        from . import _runtime
+        out, _ = _runtime.context(a.public_key).add([b.words for b in bufs], [a._exps()] * len(bufs))
+    else:
+        nsq = a.public_key.nsquare
+        rows = [_ints(b.words) for b in bufs]
+        out = _to_words([math.prod(col) % nsq for col in zip(*rows)], a.words.shape[1])
+    return a._like(out, bound)
+
+
+def host_encrypt_packed(x: np.ndarray, layout: PackedLayout, pub_key):
+    """encrypt_packed on Python integers: (words, statuses)."""
+    ts, st = encode_values(x, layout)
+    n, nsq, k = pub_key.n, pub_key.nsquare, layout.slots
+    cts = []
+    for c in range(-(-len(ts) // k)):
+        m = pack_int(ts[c * k:(c + 1) * k], layout.slot_bits) % n
+        cts.append((1 + n * m) % nsq * _bigint.powmod(secrets.randbelow(n - 1) + 1, n, nsq) % nsq)
+    return _to_words(cts, (2 * n.bit_length() + 31) // 32), np.array(st, dtype=np.int32)
+
+
+def host_decrypt_packed(buf: PackedCiphertextBuffer, priv_key):
+    """decrypt_packed on Python integers: the slot integers, or OverflowError."""
+    lay, n = buf.layout, buf.public_key.n
+    ts = []
+    for c in _ints(buf.words):
+        row = unpack_int(host_raw_decrypt(c, priv_key), n, lay.slot_bits, lay.slots)
+        if row is None:
+            raise OverflowError('Overflow detected in decode number')
+        ts += row
+    return ts[:buf.count]

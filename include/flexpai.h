@@ -357,6 +357,47 @@ int pai_segment_add_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp
 int pai_matmul_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t m, size_t K, int dtype,
                    const void* d_x, size_t d, uint32_t* d_out, int32_t* d_exp_out, void* stream);
 
+/* Packed plaintexts: many signed fixed-point values per ciphertext (no reference counterpart; opt-in, both peers must
+ * be flexpai; csrc/kernels_pack.hpp). Every packed ciphertext is an ordinary reference ciphertext
+ * raw_encrypt(M mod n, pk, r), so pai_add, pai_mul by an integer and pai_obfuscate act on all slots at once.
+ *
+ * Layout (n of nb bits): slot_bits sb, a multiple of 8 in [16, 64]; 2 <= value_bits vb <= sb; 1 <= slots k <=
+ *   floor((nb - 2) / sb); exponent e, the library's base-16 exponent (value = t * 16^-e). B = 2^sb. The bound on k
+ *   keeps |M| < 2^(k sb - 1) <= 2^(nb - 3) < max_int = n / 3 - 1. Anything else is PAI_ERR_ARG.
+ * Encode: value i of a call goes to ciphertext i / k, slot i % k (slot 0 least significant). t_i is the library's
+ *   encoding at the fixed exponent e (pai_encrypt with PAI_EXP_FIXED: rint(ldexp(v, 4 e)) for floats, |v| < 1e-200 -> 0).
+ *   A value with |t_i| > 2^(vb - 1) - 1 (NaN and +-inf among them) gets status PAI_EL_ENC_RANGE and is encoded as 0; its
+ *   neighbours are untouched and the call succeeds. Slots past the last value are 0.
+ * Plaintext: M_c = sum_j t_(c k + j) B^j, a SIGNED integer with signed digits; m_c = M_c mod n (negatives are
+ *   n - |M_c|, the library's sign convention). No bias is added and no term count is needed at decode time.
+ * Ciphertext: ct_c = (1 + n m_c) r_c^n mod n^2; r and index_base count CIPHERTEXTS. The bits contract, as for
+ *   pai_obfuscate: ct_c = c0_c * E0_c mod n^2, where E0 is what pai_encrypt_dev writes for ceil(N / k) int64 zeros on the
+ *   same context state with the same obf_mode, r, rng key and index_base: the same route (csrc/encrypt_route.hpp), the
+ *   same break-even counters (counting ciphertexts, not values), the same tables, one sampler decision per call however
+ *   the host-buffer call is chunked. PAI_OBF_NONE gives c0 itself.
+ * Decode: m = D(ct), the raw plaintext of pai_decrypt. M = m if m <= max_int, m - n if m >= n - max_int, otherwise
+ *   every value of that ciphertext gets PAI_EL_OVERFLOW. For j = 0 .. k-1: t_j = ((M + B/2) mod B) - B/2, M <- (M - t_j) / B;
+ *   a non-zero M after k digits is PAI_EL_OVERFLOW for all its values too. Otherwise PAI_EL_OK, mant = t_j and
+ *   val = (double)t_j * 2^(-4 e). Slot sums decode correctly while every slot keeps |sum t| <= 2^(sb - 1) - 1; an
+ *   overflow from one slot into its neighbour cannot be seen in the plaintext (the Python layer keeps an exact bound).
+ *
+ * Outputs: ct_out ceil(N / slots) * W words; status_out N statuses (nullable on encrypt). pai_decrypt_packed without
+ * the private key is PAI_ERR_NOPRIV. The device variants are as asynchronous as pai_encrypt_dev / pai_decrypt_dev and
+ * keep their scratch in the context, like pai_obfuscate_dev; the host-buffer variants chunk like their neighbours. */
+typedef struct { int32_t slot_bits, value_bits, exponent, slots; } pai_pack_layout;
+int pai_pack_max_slots(const pai_ctx* ctx, int slot_bits, int* slots);   /* floor((key_bits - 2) / slot_bits) */
+int pai_encrypt_packed(pai_ctx* ctx, int dtype, const void* x, size_t N, const pai_pack_layout* layout, int obf_mode,
+                       const uint8_t* r_le, size_t r_stride_bytes, size_t r_bytes, const uint8_t* rng_key32,
+                       uint64_t index_base, uint32_t* ct_out, int32_t* status_out);
+int pai_encrypt_packed_dev(pai_ctx* ctx, int dtype, const void* d_x, size_t N, const pai_pack_layout* layout,
+                           int obf_mode, const uint32_t* d_r_words, size_t r_stride_words, size_t r_words,
+                           const uint8_t* rng_key32, uint64_t index_base, uint32_t* d_ct, int32_t* d_status,
+                           void* stream);
+int pai_decrypt_packed(pai_ctx* ctx, const uint32_t* ct, const pai_pack_layout* layout, size_t N, double* val_out,
+                       int64_t* mant_out, int32_t* status_out);
+int pai_decrypt_packed_dev(pai_ctx* ctx, const uint32_t* d_ct, const pai_pack_layout* layout, size_t N, double* d_val,
+                           int64_t* d_mant, int32_t* d_status, void* stream);
+
 /* Multi-GPU: ciphertext shards -> every rank (RCCL, opened with dlopen on first use; one process per GPU).
  * Rank 0 calls pai_comm_unique_id and hands the PAI_COMM_ID_BYTES bytes to the other ranks over any
  * channel; every rank then calls pai_comm_create (collective). */
