@@ -3738,6 +3738,41 @@ int pai_decrypt_packed_dev(pai_ctx* c, const uint32_t* d_ct, const pai_pack_layo
   return 0;
 }
 
+// One k_pack_fold over the ceil(N / slots) outputs: no scratch, no inversion, nothing read back.
+int pai_pack_ciphertexts_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N,
+                             const pai_pack_layout* layout, uint32_t* d_out, int32_t* d_status, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  PackLayout lay;
+  int rc = pack_layout(c, layout, &lay);
+  if (rc) return rc;
+  if (N == 0) return 0;
+  if (!d_ct || !d_exp || !d_out) return fail(PAI_ERR_ARG, "pai_pack_ciphertexts_dev: bad arguments");
+  const size_t W = c->ct_words, C = (N + lay.k - 1) / lay.k;
+  if (d_out < d_ct + N * W && d_ct < d_out + C * W)
+    return fail(PAI_ERR_ARG, "pai_pack_ciphertexts_dev: d_out must not overlap d_ct");
+  HIPCHK(hipSetDevice(c->device));
+  int occ = 1;
+  if (fold_occupancy(c->tpi_e, &occ)) return fail(PAI_ERR_KEY, "unsupported group size");
+  const int gpb = BLOCK / c->tpi_e;
+  PackFoldParams p{};
+  p.ct = d_ct;
+  p.exp = d_exp;
+  p.nvals = (long long)N;
+  p.lay = lay;
+  p.out = d_out;
+  p.status = d_status;
+  p.n = (long long)C;
+  p.N = c->d_N;
+  p.R2 = c->d_R2;
+  p.oneR = c->d_oneR;
+  p.mprime = c->mprime_N;
+  p.ct_words = c->ct_words;
+  const int grid = (int)std::max<long long>(1, std::min<long long>((p.n + gpb - 1) / gpb, (long long)occ * c->cus));
+  HIPCHK(fold_launch(c->tpi_e, p, grid, (hipStream_t)stream));
+  return 0;
+}
+
 // ------------------------------------------------------------------ host-buffer entry points
 struct DevScope {
   std::vector<void*> ptrs;
@@ -4829,6 +4864,48 @@ int pai_decrypt_packed(pai_ctx* c, const uint32_t* ct, const pai_pack_layout* la
   HIPCHK(hipMemcpyAsync(val_out, dval, N * 8, hipMemcpyDeviceToHost, sc));
   if (mant_out) HIPCHK(hipMemcpyAsync(mant_out, dmant, N * 8, hipMemcpyDeviceToHost, sc));
   HIPCHK(hipMemcpyAsync(status_out, dst, N * 4, hipMemcpyDeviceToHost, sc));
+  HIPCHK(hipStreamSynchronize(sc));
+  return 0;
+}
+
+// Chunks of whole outputs (multiples of `slots` values, like pai_encrypt_packed): the inputs of chunk i + 1 go up through
+// the pinned slots while chunk i folds; the outputs, `slots` times smaller, come down at the end.
+int pai_pack_ciphertexts(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, const pai_pack_layout* layout,
+                         uint32_t* ct_out, int32_t* status_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  PackLayout lay;
+  int rc = pack_layout(c, layout, &lay);
+  if (rc) return rc;
+  if (N == 0) return 0;
+  if (!ct || !exp || !ct_out) return fail(PAI_ERR_ARG, "pai_pack_ciphertexts: null buffer");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t W = c->ct_words, K = lay.k, C = (N + K - 1) / K;
+  size_t CH;
+  int nch;
+  if ((rc = host_pipe(c, C, carve_bytes({N * W * 4, N * 4, C * W * 4, N * 4}), K * W * 4, &CH, &nch))) return rc;
+  Carve cv{(char*)c->d_hostio};
+  uint32_t* dct = cv.take<uint32_t>(N * W);
+  int32_t* dexp = cv.take<int32_t>(N);
+  uint32_t* dout = cv.take<uint32_t>(C * W);
+  int32_t* dst = cv.take<int32_t>(N);
+  hipStream_t sc = c->s_comp, sy = c->s_copy;
+  HostCall hc(c);
+  HIPCHK(hipMemcpyAsync(dexp, exp, N * 4, hipMemcpyHostToDevice, sc));
+  for (int i = 0; i < nch; ++i) {
+    const size_t off = (size_t)i * CH, n = std::min(CH, C - off), v0 = off * K, nv = std::min(n * K, N - v0);
+    if (i >= 2) HIPCHK(hipEventSynchronize(c->hev[i - 2]));   // the slot's previous upload is done
+    par_copy(c->h_pin[i & 1], ct + v0 * W, nv * W * 4);
+    HIPCHK(hipMemcpyAsync(dct + v0 * W, c->h_pin[i & 1], nv * W * 4, hipMemcpyHostToDevice, sy));
+    HIPCHK(hipEventRecord(c->hev[i], sy));
+    HIPCHK(hipStreamWaitEvent(sc, c->hev[i], 0));
+    if ((rc = pai_pack_ciphertexts_dev(c, dct + v0 * W, dexp + v0, nv, layout, dout + off * W, dst + v0, sc))) {
+      (void)hipStreamSynchronize(sc);
+      return rc;
+    }
+  }
+  HIPCHK(hipMemcpyAsync(ct_out, dout, C * W * 4, hipMemcpyDeviceToHost, sc));
+  if (status_out) HIPCHK(hipMemcpyAsync(status_out, dst, N * 4, hipMemcpyDeviceToHost, sc));
   HIPCHK(hipStreamSynchronize(sc));
   return 0;
 }

@@ -14,6 +14,9 @@
 //                    normalize do at every key size. c0 = 1 + n |M| or n^2 + 1 - n |M|; with an obfuscator the encrypt
 //                    chain has already written s = r^n into the output row, and c0 s is k_obf_mul's two Montgomery
 //                    products (c0 R^2 R^-1, then s R^-1) and one cond_sub.
+//   k_pack_fold<TPI> k EXISTING ordinary ciphertexts -> one packed ciphertext (pai_pack_ciphertexts), one output per group:
+//                    prod_j c_j^(16^D_j 2^(sb j)) by Horner from the top slot, the exponent alignment folded into the
+//                    squarings (below, in front of the kernel).
 //   k_unpack         raw plaintexts m = D(ct) in [0, n) -> the N values. A block takes UNPACK_CPB ciphertexts: all
 //                    threads copy their words into LDS (coalesced), one thread per ciphertext does the multiword sign
 //                    test against max_int = n / 3 - 1 and forms U = M + H in place (M = m, or m - n), then all
@@ -168,6 +171,113 @@ __global__ __launch_bounds__(BLOCK, 2) void k_pack_mul(PackMulParams p) {
       cond_sub<TPI>(a, m, lane, tig);
     }
     emit_words<TPI>(slot, a, p.ct + t * p.ct_words, p.ct_words, valid, tig);
+  }
+}
+
+// ================================================================= fold (pai_pack_ciphertexts)
+// k existing ordinary ciphertexts -> one packed ciphertext, out = prod_j c_j^(2^(4 D_j + sb j)) mod n^2 with
+// D_j = E - exp_j and 0 <= 4 D_j < sb. One output per group of TPI lanes, Horner from the top slot over the bit
+// positions t = sb j + r: every step squares, and slot j enters at r = 4 D_j, where 4 D_j squarings of its own remain:
+//   (acc^(2^(sb - 4D)) c_j)^(2^(4D)) = acc^(2^sb) c_j^(16^D).
+// The slot a step can inject is j = t / sb for every group of the wave, so the walk over (j, r) is wave-uniform; only
+// the step r at which a group injects differs. A step multiplies when some group of the wave injects there (ballot);
+// the others multiply by 1 (R in the Montgomery domain). Nothing is squared before the wave's first injection, so the
+// top slot costs its own 4 D squarings and a ragged output starts at its own top slot. Per slot: sb squarings, one
+// product by R^2 that takes c_j into the Montgomery domain, one product into acc.
+struct PackFoldParams {
+  const uint32_t* ct;     // [nvals][ct_words] ordinary ciphertexts
+  const int32_t* exp;     // [nvals]; PAD_EXP: the ciphertext 1 of an empty segment
+  long long nvals;
+  PackLayout lay;
+  uint32_t* out;          // [n][ct_words]
+  int32_t* status;        // [nvals], nullable
+  long long n;            // outputs: ceil(nvals / k)
+  const uint32_t* N;      // n^2, limbs (S)
+  const uint32_t* R2;     // R^2 mod n^2
+  const uint32_t* oneR;   // R mod n^2
+  uint32_t mprime;
+  int ct_words;
+};
+
+// 4 D of slot j of output ci, or -1 where the slot contributes the factor 1; the status is written when `record`
+__device__ __forceinline__ int fold_shift(const PackFoldParams& p, long long ci, int j, bool record) {
+  const long long i = ci * p.lay.k + j;
+  if (i >= p.nvals) return -1;
+  const int32_t e = p.exp[i];
+  int st = ST_OK, d4 = -1;
+  if (e != PAD_EXP) {
+    const long long d = (long long)p.lay.fexp - (long long)e;
+    if (d < 0 || 4 * d >= p.lay.sb) st = ST_ENC_RANGE;
+    else d4 = (int)(4 * d);
+  }
+  if (record && p.status) p.status[i] = st;
+  return d4;
+}
+
+template <int TPI>
+__global__ __launch_bounds__(BLOCK, 2) void k_pack_fold(PackFoldParams p) {
+  constexpr int S = TPI * L;
+  constexpr int GPB = BLOCK / TPI;
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const int lane = threadIdx.x & 63;
+  const int tig = threadIdx.x % TPI;
+  const int gib = threadIdx.x / TPI;
+  uint32_t* slot = smem + gib * S;
+  uint32_t* park = smem + (GPB + gib) * S;            // second slot of the group: acc during an injection
+  uint32_t m[L];
+  load_limbs_g<TPI>(p.N, m, tig);
+  const int sb = p.lay.sb, k = p.lay.k;
+
+  for (long long base = (long long)blockIdx.x * GPB; base < p.n; base += (long long)gridDim.x * GPB) {
+    const long long inst = base + gib;
+    const bool valid = inst < p.n;
+    const long long t = valid ? inst : p.n - 1;
+    const int cnt = (int)min((long long)k, p.nvals - t * k);   // slots of this output that hold a value (>= 1)
+    int jtop = cnt - 1;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) jtop = max(jtop, __shfl_xor(jtop, s));
+    uint32_t acc[L];
+    load_limbs_g<TPI>(p.oneR, acc, tig);
+    bool started = false;                                       // wave-uniform: some group has injected
+    for (int j = jtop; j >= 0; --j) {
+      const int d4 = j < cnt ? fold_shift(p, t, j, valid && tig == 0) : -1;
+      int rtop = d4;
+#pragma unroll
+      for (int s = 32; s >= 1; s >>= 1) rtop = max(rtop, __shfl_xor(rtop, s));
+      if (started) rtop = sb - 1;
+      const uint32_t* src = p.ct + (t * k + (j < cnt ? j : 0)) * p.ct_words;
+#pragma unroll 1
+      for (int r = rtop; r >= 0; --r) {
+        if (started) {
+          write_limbs_lds<TPI>(slot, acc, tig);
+          montmul<TPI>(acc, acc, slot, TPI, m, p.mprime, lane, tig);
+        }
+        const bool inj = d4 == r;
+        if (ballot(inj) != 0ull) {
+          // acc waits in the group's second LDS slot while c_j enters the Montgomery domain: acc, c_j, the modulus
+          // and the product's 2 L accumulator registers together do not fit 256 VGPRs
+          wave_lds_fence();
+#pragma unroll
+          for (int i = 0; i < L; ++i) park[tig * L + i] = acc[i];
+          wave_lds_fence();
+          uint32_t b[L];
+          stage_words_to_limbs<TPI>(slot, src, p.ct_words, b, tig);
+#pragma unroll
+          for (int i = 0; i < L; ++i) b[i] = inj ? b[i] : ((tig == 0 && i == 0) ? 1u : 0u);
+          copy_g_to_lds<TPI>(slot, p.R2, tig);
+          montmul<TPI>(b, b, slot, TPI, m, p.mprime, lane, tig);        // c_j R, or R
+          write_limbs_lds<TPI>(slot, b, tig);
+#pragma unroll
+          for (int i = 0; i < L; ++i) acc[i] = park[tig * L + i];
+          montmul<TPI>(acc, acc, slot, TPI, m, p.mprime, lane, tig);
+          started = true;
+        }
+      }
+    }
+    write_one_lds<TPI>(slot, tig);
+    montmul<TPI>(acc, acc, slot, TPI, m, p.mprime, lane, tig);           // leave the Montgomery domain
+    cond_sub<TPI>(acc, m, lane, tig);
+    emit_words<TPI>(slot, acc, p.out + t * p.ct_words, p.ct_words, valid, tig);
   }
 }
 

@@ -47,7 +47,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_next_prime", "pai_prime_last_times", "pai_prime_test", "pai_debug_prime_sieve",
             "pai_obfuscate", "pai_obfuscate_dev",
             "pai_pack_max_slots", "pai_encrypt_packed", "pai_encrypt_packed_dev", "pai_decrypt_packed",
-            "pai_decrypt_packed_dev")
+            "pai_decrypt_packed_dev", "pai_pack_ciphertexts", "pai_pack_ciphertexts_dev")
 PAI_COMM_ID_BYTES = 128
 
 _lib = None
@@ -106,6 +106,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_encrypt_packed_dev.argtypes = [P, I, P, S, P, I, P, S, S, P, U64, P, P, P]
         lib.pai_decrypt_packed.argtypes = [P, P, P, S, P, P, P]
         lib.pai_decrypt_packed_dev.argtypes = [P, P, P, S, P, P, P, P]
+        lib.pai_pack_ciphertexts.argtypes = [P, P, P, S, P, P, P]
+        lib.pai_pack_ciphertexts_dev.argtypes = [P, P, P, S, P, P, P, P]
         lib.pai_mul.argtypes = [P, P, P, S, I, P, S, P, P, P]
         lib.pai_mul_dev.argtypes = [P, P, P, S, I, P, S, P, P, P, P]
         lib.pai_add_plain.argtypes = [P, P, P, S, I, P, S, P, P, P]
@@ -652,6 +654,21 @@ class Context:
         self.calls["pai_decrypt_packed"] += 1
         self._chk(self.lib.pai_decrypt_packed(self._h, _ptr(ct), ctypes.byref(lay), N, _ptr(val), _ptr(mant), _ptr(st)))
         return val, mant, st
+
+    def pack_ciphertexts(self, ct: np.ndarray, exp: np.ndarray, layout) -> Tuple[np.ndarray, np.ndarray]:
+        """pai_pack_ciphertexts: fold the N ordinary ciphertexts ct [N, ct_words] with exponents exp into
+        ceil(N / slots) packed ones under `layout`. Returns (words [C, ct_words], statuses [N])."""
+        ct = np.ascontiguousarray(ct, dtype=np.uint32)
+        exp = np.ascontiguousarray(exp, dtype=np.int32)
+        N = exp.size
+        self._check_words(ct, exp, N)
+        lay = pack_layout(layout)
+        C = -(-N // lay.slots) if lay.slots > 0 else 0
+        out = np.empty((C, self.ct_words), dtype=np.uint32)
+        st = np.empty(N, dtype=np.int32)
+        self.calls["pai_pack_ciphertexts"] += 1
+        self._chk(self.lib.pai_pack_ciphertexts(self._h, _ptr(ct), _ptr(exp), N, ctypes.byref(lay), _ptr(out), _ptr(st)))
+        return out, st
 
     def add(self, cts: Sequence[np.ndarray], exps: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
         k = len(cts)

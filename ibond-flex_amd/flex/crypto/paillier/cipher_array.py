@@ -213,6 +213,11 @@ class PaillierArray(np.ndarray):
             return np.ndarray.__matmul__(np.asarray(self), b)
         return res
 
+    def pack(self, layout, max_abs):
+        """Fold these ciphertexts into a PackedCiphertextBuffer (packed_buffer.pack_ciphertexts)."""
+        from .packed_buffer import pack_ciphertexts
+        return pack_ciphertexts(self, layout, max_abs)
+
 
 def _all_encrypted(flat) -> bool:
     return all(isinstance(e, PaillierEncryptedNumber) for e in flat)

@@ -194,6 +194,11 @@ class CiphertextBuffer(object):
 
     __matmul__ = dot
 
+    def pack(self, layout, max_abs):
+        """Fold these ciphertexts into a PackedCiphertextBuffer (packed_buffer.pack_ciphertexts)."""
+        from .packed_buffer import pack_ciphertexts
+        return pack_ciphertexts(self, layout, max_abs)
+
 
 def add_buffers(bufs: Sequence[CiphertextBuffer]) -> CiphertextBuffer:
     """Element-wise sum of k buffers of one key and shape in ONE k-way add launch (the reference's

@@ -18,6 +18,12 @@ every slot: sums add the bounds, products scale them, and a result whose bound w
 OverflowError before any GPU call. Only integer scalars are supported (a float scalar would change the exponent of a
 whole ciphertext, which the layout fixes).
 
+Results that already exist as ordinary ciphertexts (per-bin sums, integer-weighted sums) are folded into a packed buffer
+by a party with the public key only: pack_ciphertexts(src, layout, max_abs), CiphertextBuffer.pack, PaillierArray.pack,
+parallel_ops.segment_sum_packed (ONE pai_pack_ciphertexts call: out = prod_j c_j^(2^(slot_bits j))). The caller states
+max_abs, since an existing ciphertext cannot show its magnitude. Slots are at most 64 bits wide: integer-valued results
+and values of one fixed precision fit, products of two full-precision float encodings (~106-bit mantissas) do not.
+
 Without a GPU the same operations run on Python integers (small arrays only, as in the rest of the package).
 """
 from __future__ import annotations
@@ -366,6 +372,86 @@ def host_encrypt_packed(x: np.ndarray, layout: PackedLayout, pub_key):
         m = pack_int(ts[c * k:(c + 1) * k], layout.slot_bits) % n
         cts.append((1 + n * m) % nsq * _bigint.powmod(secrets.randbelow(n - 1) + 1, n, nsq) % nsq)
     return _to_words(cts, (2 * n.bit_length() + 31) // 32), np.array(st, dtype=np.int32)
+
+
+_EMPTY_EXP = -(1 << 31)     # the exponent of pai_segment_add's empty segment (ciphertext 1)
+
+
+def host_pack_ciphertexts(cts: Sequence[int], exps: Sequence[int], layout: PackedLayout, pub_key):
+    """pai_pack_ciphertexts on Python integers: (packed ciphertext ints, statuses). Value i contributes
+    c_i^(16^D * 2^(slot_bits j)) to output i // slots, j = i % slots, D = layout.exponent - exps[i] with
+    0 <= 4 D < slot_bits; an empty segment contributes 1; any other exponent is EL_ENC_RANGE and contributes 1."""
+    nsq, k, sb, E = pub_key.nsquare, layout.slots, layout.slot_bits, layout.exponent
+    out, st = [1] * -(-len(cts) // k), []
+    for i, (c, e) in enumerate(zip(cts, exps)):
+        e = int(e)
+        d = E - e
+        if e == _EMPTY_EXP:
+            st.append(0)
+        elif d < 0 or 4 * d >= sb:
+            st.append(EL_ENC_RANGE)
+        else:
+            st.append(0)
+            out[i // k] = out[i // k] * _bigint.powmod(int(c), 1 << (4 * d + sb * (i % k)), nsq) % nsq
+    return out, np.array(st, dtype=np.int32)
+
+
+def _slot_bound(layout: PackedLayout, max_abs, terms: int = 1) -> int:
+    """terms * ceil(max_abs * 16^exponent), or OverflowError where that passes the slot."""
+    if not isinstance(layout, PackedLayout):
+        raise ValueError("layout does not belong to a key of this size")
+    bound = int(terms) * math.ceil(abs(Fraction(max_abs)) * Fraction(16) ** layout.exponent)
+    if bound > layout.slot_max:
+        raise OverflowError(f"slot bound {bound} would exceed 2^{layout.slot_bits - 1} - 1: a slot could overflow "
+                            "into its neighbour")
+    return bound
+
+
+def _fold(pub_key, words, exps, layout: PackedLayout, bound: int, shape) -> "PackedCiphertextBuffer":
+    """One pai_pack_ciphertexts call over words [N, W] / exps [N] (Python integers without a GPU)."""
+    if not isinstance(layout, PackedLayout) or layout.key_bits != pub_key.n.bit_length():
+        raise ValueError("layout does not belong to a key of this size")
+    W = (2 * pub_key.n.bit_length() + 31) // 32
+    if exps.size == 0:
+        out, st = np.zeros((0, W), dtype=np.uint32), np.zeros(0, dtype=np.int32)
+    elif _gpu():
+        from . import _runtime
+        out, st = _runtime.context(pub_key).pack_ciphertexts(words, exps, layout)
+    else:
+        ints, st = host_pack_ciphertexts(_ints(words), exps.tolist(), layout, pub_key)
+        out = _to_words(ints, W)
+    bad = np.flatnonzero(st)
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"pack_ciphertexts: value at index {i} has exponent {int(exps[i])}, outside the layout's range "
+                         f"(0 <= 4 * ({layout.exponent} - exponent) < {layout.slot_bits})")
+    return PackedCiphertextBuffer(pub_key, out, layout, int(exps.size), shape, obfuscated=False, bound=bound)
+
+
+def pack_ciphertexts(src, layout: PackedLayout, max_abs) -> "PackedCiphertextBuffer":
+    """Fold EXISTING ordinary ciphertexts (a CiphertextBuffer, a PaillierArray or an object array of
+    PaillierEncryptedNumber) into a PackedCiphertextBuffer under `layout`, layout.slots per ciphertext, in ONE
+    pai_pack_ciphertexts call; needs the public key only. The values must be integers at the layout's exponent, and the
+    caller vouches for |value| <= max_abs, which an existing ciphertext cannot show: the buffer's bound is
+    ceil(max_abs * 16^exponent), OverflowError before any GPU call if that passes the slot. Every exponent must satisfy
+    0 <= 4 (layout.exponent - exponent) < slot_bits (ValueError names the first index that does not). The result is not
+    re-randomised (obfuscated=False): to_wire(be_secure=True) does that."""
+    from .cipher_buffer import CiphertextBuffer
+    if isinstance(src, CiphertextBuffer):
+        pk, words, exps, shape = src.public_key, src.words, src.exps, src.shape
+    elif isinstance(src, np.ndarray) and src.dtype == object:
+        from .cipher_array import _encrypted_operand, pack
+        A, pk = _encrypted_operand(src)
+        if A is None:
+            raise TypeError("pack_ciphertexts needs a non-empty array of PaillierEncryptedNumber with one public key")
+        words, exps, _ = pack(src, pk)
+        shape = A.shape
+    else:
+        raise TypeError(f"unsupported operand {type(src)} for pack_ciphertexts")
+    if not isinstance(layout, PackedLayout) or layout.key_bits != pk.n.bit_length():
+        raise ValueError("layout does not belong to a key of this size")
+    bound = _slot_bound(layout, max_abs)
+    return _fold(pk, words, np.ascontiguousarray(exps, dtype=np.int32).reshape(-1), layout, bound, shape)
 
 
 def host_decrypt_packed(buf: PackedCiphertextBuffer, priv_key):

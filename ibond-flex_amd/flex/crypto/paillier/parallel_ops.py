@@ -88,6 +88,46 @@ def segment_sum(x: np.ndarray, index_lists) -> list:
     return res
 
 
+def segment_sum_packed(x, index_lists, layout, max_abs):
+    """The per-bin sums of segment_sum as ONE PackedCiphertextBuffer (packed_buffer.py): one pai_segment_add call, then
+    one pai_pack_ciphertexts call that folds layout.slots bin sums into each ciphertext, so the key holder decrypts
+    len(index_lists) / slots ciphertexts; no per-bin object is built. `x` is a CiphertextBuffer, a PaillierArray or an
+    object array of integer-valued ciphertexts with |value| <= max_abs (the caller's assertion); the buffer's bound is
+    (longest bin) * ceil(max_abs * 16^exponent), OverflowError before any GPU call if it passes the slot. Empty bins
+    decode as 0. Without a GPU the same runs on Python integers (small arrays only)."""
+    from . import _runtime
+    from .cipher_array import _encrypted_operand, pack
+    from .cipher_buffer import CiphertextBuffer
+    from .packed_buffer import _EMPTY_EXP, _fold, _ints, _slot_bound, _to_words
+    if isinstance(x, CiphertextBuffer):
+        pk, words, exps = x.public_key, x.words, x.exps
+    else:
+        A, pk = _encrypted_operand(x)
+        if A is None:
+            raise TypeError("segment_sum_packed needs a non-empty array of PaillierEncryptedNumber with one public key")
+        words, exps, _ = pack(x, pk)
+    lists = [np.asarray(i).reshape(-1) for i in index_lists]
+    sizes = np.array([len(i) for i in lists], dtype=np.int64)
+    bound = _slot_bound(layout, max_abs, int(sizes.max()) if sizes.size else 0)
+    idx = np.concatenate(lists).astype(np.int64) if sizes.sum() else np.zeros(0, dtype=np.int64)
+    idx = np.where(idx < 0, idx + exps.size, idx)
+    seg_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    if _runtime.gpu_available():
+        out, oe = _runtime.context(pk).segment_add(words, exps, idx, seg_off)
+    else:
+        cts, nsq, sums, oe = _ints(words), pk.nsquare, [], []
+        for s in range(len(lists)):
+            members = idx[seg_off[s]:seg_off[s + 1]].tolist()
+            E = max((int(exps[i]) for i in members), default=_EMPTY_EXP)
+            acc = 1
+            for i in members:
+                acc = acc * pow(cts[i], 16 ** (E - int(exps[i])), nsq) % nsq
+            sums.append(acc)
+            oe.append(E)
+        out, oe = _to_words(sums, words.shape[1]), np.array(oe, dtype=np.int32)
+    return _fold(pk, out, np.ascontiguousarray(oe, dtype=np.int32), layout, bound, (len(lists),))
+
+
 def good_bad_calc(y: np.ndarray, index_lists):
     """HeteroBin.en_good_bad_calc (hetero_bin.py:27-36) on the GPU: good_s = sum(y[i]), bad_s = len(i) -
     good_s for every bin; returns the two numpy arrays the reference builds."""

@@ -397,6 +397,26 @@ int pai_decrypt_packed(pai_ctx* ctx, const uint32_t* ct, const pai_pack_layout* 
                        int64_t* mant_out, int32_t* status_out);
 int pai_decrypt_packed_dev(pai_ctx* ctx, const uint32_t* d_ct, const pai_pack_layout* layout, size_t N, double* d_val,
                            int64_t* d_mant, int32_t* d_status, void* stream);
+/* Fold EXISTING ordinary ciphertexts into packed ones (FATE's cipher compression; csrc/kernels_pack.hpp k_pack_fold).
+ * Needs the public key only. Value i of the N inputs (ct [N][W], exp [N]) goes to output i / k, slot i % k of the layout
+ * (sb, vb, e = E, k), validated as above; ct_out holds ceil(N / k) * W words, status_out N statuses (nullable).
+ * Shift: D_i = E - exp_i. Where 0 <= 4 D_i < sb the value contributes the factor ct_i^(16^D_i * 2^(sb j)): the reference's
+ *   own alignment (increase_exponent_to) and the slot's place. exp_i = INT32_MIN (the ciphertext 1 of an empty segment of
+ *   pai_segment_add) contributes the factor 1 with PAI_EL_OK. exp_i > E or 4 D_i >= sb is PAI_EL_ENC_RANGE: the factor is 1,
+ *   the slot reads 0, its neighbours are untouched and the call succeeds. Slots past N are the factor 1.
+ * Bits: out_c = product of the contributing factors mod n^2, canonical (below n^2): D(out_c) = sum_j t_j 16^D_j 2^(sb j)
+ *   mod n, the plaintext pai_decrypt_packed decodes. For E = the largest exponent these are the bits of the reference's
+ *   sum(c_j * (1 << (sb * j))) through PaillierEncryptedNumber.__mul__ and __add__. The output is a deterministic
+ *   function of its inputs and is NOT re-randomised: pai_obfuscate does that afterwards. vb is not checked against the
+ *   encrypted values, which the caller cannot see; the caller vouches that every slot keeps |t_j 16^D_j| <= 2^(sb - 1) - 1.
+ * d_out overlapping d_ct is PAI_ERR_ARG. The _dev call never waits on the host (no inversion, no scratch: capturable),
+ * takes the context lock and chains on the previous call's event like its neighbours; the host-buffer call chunks at
+ * multiples of k values, like pai_encrypt_packed. Per output (k - 1) sb + 2 k + 1 products mod n^2 depend on each other, so a
+ * call of few outputs is latency-bound, like one public exponentiation. */
+int pai_pack_ciphertexts(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N,
+                         const pai_pack_layout* layout, uint32_t* ct_out, int32_t* status_out);
+int pai_pack_ciphertexts_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N,
+                             const pai_pack_layout* layout, uint32_t* d_out, int32_t* d_status, void* stream);
 
 /* Multi-GPU: ciphertext shards -> every rank (RCCL, opened with dlopen on first use; one process per GPU).
  * Rank 0 calls pai_comm_unique_id and hands the PAI_COMM_ID_BYTES bytes to the other ranks over any
