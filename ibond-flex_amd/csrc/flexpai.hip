@@ -53,6 +53,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_grp.hpp"
 #include "engine_mul.hpp"
 #include "engine_mm.hpp"
+#include "engine_sd.hpp"
 #include "engine_obf.hpp"
 #include "engine_pack.hpp"
 #include "engine_crtw.hpp"
@@ -274,6 +275,21 @@ struct pai_ctx {
   void* d_mminv = nullptr;      // copy of the ciphertexts with the flagged rows' inverted (only with negative scalars)
   size_t mminv_bytes = 0;
   std::vector<uint8_t> mm_neg, mm_flags;   // host sides of neg_row and of the flags
+  // segmented weighted sums (kernels_sd.hpp): PAI_OPT_SEGDOT_FUSED / PAI_OPT_SEGDOT_PATH
+  bool sd_fused = true;
+  int sd_path = 0;              // last pai_segment_dot[_dev] call: 0 none yet, 1 term path, 2 fused
+  void* d_sdmeta = nullptr;     // index, chunk starts, table slots, block rows, sign flags
+  size_t sdmeta_bytes = 0;
+  void* d_sdbuf = nullptr;      // a slice's gathered entries and terms (term path) / a block's distinct ciphertexts (fused)
+  size_t sdbuf_bytes = 0;
+  void* d_sdpart = nullptr;     // the chunk partials and their exponents
+  size_t sdpart_bytes = 0;
+  // host sides of the metadata (they outlive the call's asynchronous copies)
+  struct SdHost {
+    std::vector<long long> cstart, segch, iota, urows, rows;
+    std::vector<int32_t> uid, tslot, idmap;
+    std::vector<uint8_t> neg, flags;
+  } sd;
   void* d_inv = nullptr;        // batch-inversion prefix products and segment products
   size_t inv_bytes = 0;
   std::vector<uint32_t> inv_host;   // top of the inversion tree (host side of an async copy)
@@ -366,6 +382,9 @@ pai_ctx::~pai_ctx() {
   if (d_mmtab) (void)hipFree(d_mmtab);
   if (d_mmwork) (void)hipFree(d_mmwork);
   if (d_mminv) (void)hipFree(d_mminv);
+  if (d_sdmeta) (void)hipFree(d_sdmeta);
+  if (d_sdbuf) (void)hipFree(d_sdbuf);
+  if (d_sdpart) (void)hipFree(d_sdpart);
   if (d_inv) (void)hipFree(d_inv);
   if (inv_async) {
     if (inv_async->pin) (void)hipHostFree(inv_async->pin);
@@ -2197,6 +2216,7 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       c->crt4_min = value;
       return 0;
     case PAI_OPT_MATMUL_FUSED: c->mm_fused = value != 0; return 0;
+    case PAI_OPT_SEGDOT_FUSED: c->sd_fused = value != 0; return 0;
     case PAI_OPT_OBF_CHUNK:
       if (value < 64) return fail(PAI_ERR_ARG, "PAI_OPT_OBF_CHUNK must be >= 64");
       c->obf_chunk = value;
@@ -2235,6 +2255,8 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_CRT4_MIN: *value = (int)std::min<long long>(c->crt4_min, INT32_MAX); return 0;
     case PAI_OPT_MATMUL_FUSED: *value = c->mm_fused ? 1 : 0; return 0;
     case PAI_OPT_MATMUL_PATH: *value = c->mm_path; return 0;
+    case PAI_OPT_SEGDOT_FUSED: *value = c->sd_fused ? 1 : 0; return 0;
+    case PAI_OPT_SEGDOT_PATH: *value = c->sd_path; return 0;
     case PAI_OPT_OBF_CHUNK: *value = c->obf_chunk; return 0;
     case PAI_OPT_STAGE_TIMING: *value = c->timing ? 1 : 0; return 0;
     case PAI_OPT_LANE_DECRYPT: *value = (c->dec_lane_ok && c->dec_lane_enabled) ? 1 : 0; return 0;
@@ -4328,6 +4350,335 @@ int pai_matmul_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_
   return add_dev(c, cur, cur_e, (int)Kc, (long long)Np, d_out, d_exp_out, st);
 }
 
+// ------------------------------------------------------------------ segmented weighted sums (kernels_sd.hpp)
+// out_s = sum over t in [seg_off[s], seg_off[s+1]) of ct[index[t]] (x) x[t]. Both paths cut every segment into chunks of
+// MM_KC consecutive entries (the last one ragged, none across two segments), write one partial per chunk into a flat
+// list and leave the list to the segmented add (identity index, offsets = chunk counts): a partial is the exact residue
+// of its chunk at the chunk's largest exponent on either path, so the bits depend neither on the path nor on how the
+// chunks are grouped into slices or blocks.
+//
+//   term path   slices of SD_SLICE_CHUNKS chunks: k_sd_gather copies the slice's ct[index[t]], pai_mul_dev forms the terms
+//               (k_mul, one batch inversion) and one pai_segment_add_dev pass sums every chunk
+//   fused path  k_sd_sign flags the distinct ciphertexts that meet a negative scalar; blocks of consecutive chunks whose
+//               distinct ciphertexts fit the table budget (mm_table_budget, halved once the block holds a flagged one):
+//               k_sd_gather compacts them in table-slot order, batch_invert inverts a copy's flagged rows, k_mm_tab
+//               builds the tables and k_sd_acc runs the block's chunks
+constexpr size_t SD_SLICE_CHUNKS = 8192;   // 131 072 terms: 2 x 64 MiB of term buffer at 2048 bits
+
+// Which calls take the fused path (PAI_OPT_SEGDOT_FUSED = 1, the default). A table costs 15 products (36 with the
+// inverse) and pays off over the entries of its block that share it, hence the reuse factor entries / tables in the
+// place of pai_matmul's d; a chunk is a chain of about 4 nw + 16 nw dependent products, so a small call takes the
+// chain's time whatever its size. Measured on an MI355X against gather + pai_mul_dev + pai_segment_add_dev
+// (tools/segdot_ab.py, profiles/segdot_ab.json; 1024 and 2048 bits): faster by more than the spread
+// at 65 536 entries and more with reuse >= 16 (1.05x .. 1.4x at 1024 bits, 1.2x .. 1.7x at 2048; 2.1x .. 3.3x from
+// 262 144 entries), slower at 16 384 entries and fewer (0.66x .. 0.80x) and at reuse <= 4 whatever the size
+// (0.19x .. 0.96x). "Tables" counts what the blocks build: a call whose distinct ciphertexts do not fit one block builds
+// a ciphertext's table again in every block that names it (random indices over 16 384 ciphertexts at 2048 bits: 8
+// blocks, 0.40x). Calls outside that class keep the term path; 4096-bit keys use the same constants, unmeasured.
+constexpr size_t SD_MIN_REUSE = 16;
+constexpr size_t SD_MIN_ENTRIES = 65536;
+
+// tables the blocks of segdot_fused build when a block holds at most `limit` distinct ciphertexts
+static size_t sd_tables_blocked(const pai_ctx::SdHost& h, size_t limit) {
+  std::vector<long long> stamp(h.urows.size(), -1);
+  size_t total = 0, nd = 0;
+  long long id = 0;
+  for (size_t q = 0; q + 1 < h.cstart.size(); ++q) {
+    size_t fresh = 0;
+    for (long long t = h.cstart[q]; t < h.cstart[q + 1]; ++t)
+      if (stamp[h.uid[t]] != id) stamp[h.uid[t]] = id, ++fresh;
+    if (nd + fresh > limit && nd > 0) {                             // the chunk opens the next block
+      ++id;
+      fresh = nd = 0;
+      for (long long t = h.cstart[q]; t < h.cstart[q + 1]; ++t)
+        if (stamp[h.uid[t]] != id) stamp[h.uid[t]] = id, ++fresh;
+    }
+    nd += fresh;
+    total += fresh;
+  }
+  return total;
+}
+
+static bool sd_take_fused(const pai_ctx* c, size_t nnz) {
+  if (!c->sd_fused || nnz == 0) return false;
+  if (const char* e = xcheck_env("FLEXPAI_SD_ALWAYS"))
+    if (atoi(e) != 0) return true;
+  const size_t U = c->sd.urows.size();
+  if (nnz < SD_MIN_ENTRIES || nnz < SD_MIN_REUSE * U) return false;
+  // signs are not known yet: blocks as if one were present
+  const size_t limit = std::max<size_t>(mm_table_budget() / mm_entry_bytes(c->tpi_e) / 2, 1);
+  return U <= limit || nnz >= SD_MIN_REUSE * sd_tables_blocked(c->sd, limit);
+}
+
+static size_t sd_slice_chunks() {
+  if (const char* e = xcheck_env("FLEXPAI_SD_SLICE")) {           // test build: slicing at small shapes
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    if (v > 0) return (size_t)v;
+  }
+  return SD_SLICE_CHUNKS;
+}
+
+static int sd_gather(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, const long long* d_rows, size_t n,
+                     uint32_t* out, int32_t* out_exp, hipStream_t st) {
+  SdGatherParams g{};
+  g.ct = d_ct;
+  g.exp = d_exp;
+  g.rows = d_rows;
+  g.n = (long long)n;
+  g.out = out;
+  g.out_exp = out_exp;
+  g.ct_words = c->ct_words;
+  HIPCHK(sd_gather_launch(g, c->cus, st));
+  return 0;
+}
+
+// term path: the partials of all chunks, slice by slice (d_index: the index array on the device)
+static int segdot_terms(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, const long long* d_index, int dtype,
+                        const void* d_x, uint32_t* part, int32_t* pexp, int32_t* d_status, hipStream_t st) {
+  auto& h = c->sd;
+  const size_t W = c->ct_words, nch = h.cstart.size() - 1, esz = dtype == PAI_F32 ? 4 : 8, slice = sd_slice_chunks();
+  const size_t cap = std::min(slice, nch) * MM_KC;                // entries of a slice, at most
+  const size_t o_in = 0, o_out = align16(o_in + cap * W * 4), o_ein = align16(o_out + cap * W * 4),
+               o_eout = align16(o_ein + cap * 4), need = align16(o_eout + cap * 4);
+  int rc = ensure_buf(&c->d_sdbuf, &c->sdbuf_bytes, need);
+  if (rc) return rc;
+  char* b = (char*)c->d_sdbuf;
+  uint32_t *tin = (uint32_t*)(b + o_in), *tout = (uint32_t*)(b + o_out);
+  int32_t *ein = (int32_t*)(b + o_ein), *eout = (int32_t*)(b + o_eout);
+  std::vector<long long> off;
+  for (size_t qa = 0; qa < nch; qa += slice) {
+    const size_t qb = std::min(nch, qa + slice);
+    const long long ta = h.cstart[qa], n = h.cstart[qb] - ta;
+    if ((rc = sd_gather(c, d_ct, d_exp, d_index + ta, (size_t)n, tin, ein, st))) return rc;
+    if ((rc = pai_mul_dev(c, tin, ein, (size_t)n, dtype, (const char*)d_x + (size_t)ta * esz, 1, tout, eout,
+                          d_status ? d_status + ta : nullptr, st)))
+      return rc;
+    off.resize(qb - qa + 1);
+    for (size_t q = qa; q <= qb; ++q) off[q - qa] = h.cstart[q] - ta;
+    // (synchronises `st` before it returns: `off` may be rewritten)
+    if ((rc = pai_segment_add_dev(c, tout, eout, (size_t)n, (const int64_t*)h.iota.data(), (const int64_t*)off.data(), qb - qa,
+                                  part + qa * W, pexp + qa, st)))
+      return rc;
+  }
+  return 0;
+}
+
+// fused path: the partials of all chunks, block by block. d_index, d_cstart: the device sides of index and of the chunk
+// starts; d_uid [nnz]: room for the entries' distinct ids, which the table slots overwrite once the signs are known.
+static int segdot_fused(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, const long long* d_index,
+                        const long long* d_cstart, int32_t* d_uid, size_t nnz, int dtype, const void* d_x, uint32_t* part,
+                        int32_t* pexp, int32_t* d_status, hipStream_t st) {
+  auto& h = c->sd;
+  const size_t W = c->ct_words, nch = h.cstart.size() - 1, U = h.urows.size(), eb = mm_entry_bytes(c->tpi_e);
+  // signs (and pai_mul's statuses) of the entries -> flags of the distinct ciphertexts
+  // sdbuf: [neg | block rows | block flags | the block's ciphertexts]; the rows of all blocks together are at most nnz
+  const size_t o_neg = 0, o_rows = align16(o_neg + U), o_flags = align16(o_rows + nnz * 8), o_ct = align16(o_flags + nnz);
+  int rc = ensure_buf(&c->d_sdbuf, &c->sdbuf_bytes, o_ct);
+  if (rc) return rc;
+  uint8_t* d_neg = (uint8_t*)c->d_sdbuf + o_neg;
+  HIPCHK(hipMemsetAsync(d_neg, 0, U, st));
+  HIPCHK(hipMemcpyAsync(d_uid, h.uid.data(), nnz * 4, hipMemcpyHostToDevice, st));
+  SdSignParams sp{};
+  sp.x = d_x;
+  sp.dtype = dtype;
+  sp.nnz = (long long)nnz;
+  sp.uid = d_uid;
+  sp.neg = d_neg;
+  sp.status = d_status;
+  HIPCHK(sd_sign_launch(sp, c->cus, st));
+  h.neg.assign(U, 0);
+  HIPCHK(hipMemcpyAsync(h.neg.data(), d_neg, U, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+
+  // blocks of consecutive chunks; every block numbers its distinct ciphertexts in order of first use
+  struct Block {
+    size_t q0, q1, roff, nd;
+    bool has_neg;
+  };
+  std::vector<Block> blocks;
+  const size_t cap = std::max<size_t>(mm_table_budget() / eb, 1);
+  std::vector<long long> stamp(U, -1);
+  std::vector<int32_t> slot_of(U, 0);
+  h.rows.clear();
+  h.tslot.resize(nnz);
+  for (size_t q = 0; q < nch;) {
+    Block b{q, q, h.rows.size(), 0, false};
+    const long long id = (long long)blocks.size();
+    for (; q < nch; ++q) {
+      const size_t before = h.rows.size();
+      bool hn = b.has_neg;
+      for (long long t = h.cstart[q]; t < h.cstart[q + 1]; ++t) {
+        const int32_t u = h.uid[t];
+        if (stamp[u] != id) {
+          stamp[u] = id;
+          slot_of[u] = (int32_t)(h.rows.size() - b.roff);
+          h.rows.push_back(u);
+          hn = hn || h.neg[u] != 0;
+        }
+      }
+      const size_t limit = std::max<size_t>(hn ? cap / 2 : cap, 1);
+      if (h.rows.size() - b.roff > limit && q > b.q0) {             // the chunk opens the next block
+        for (size_t r = before; r < h.rows.size(); ++r) stamp[h.rows[r]] = -1;
+        h.rows.resize(before);
+        break;
+      }
+      b.has_neg = hn;
+      for (long long t = h.cstart[q]; t < h.cstart[q + 1]; ++t) h.tslot[t] = slot_of[h.uid[t]];
+    }
+    b.q1 = q;
+    b.nd = h.rows.size() - b.roff;
+    blocks.push_back(b);
+  }
+  size_t max_nd = 1, max_tab = 1;
+  for (const Block& b : blocks) {
+    max_nd = std::max(max_nd, b.nd);
+    max_tab = std::max(max_tab, b.nd * (b.has_neg ? 2 : 1));
+  }
+  if (max_tab >= (size_t)INT32_MAX / 2) return fail(PAI_ERR_ARG, "pai_segment_dot_dev: table block too large");
+  h.flags.resize(h.rows.size());
+  for (size_t r = 0; r < h.rows.size(); ++r) {
+    h.flags[r] = h.neg[h.rows[r]];
+    h.rows[r] = h.urows[h.rows[r]];                                 // distinct id -> row of ct
+  }
+  if ((rc = ensure_buf(&c->d_sdbuf, &c->sdbuf_bytes, o_ct + max_nd * W * 4))) return rc;
+  char* sb = (char*)c->d_sdbuf;
+  long long* d_rows = (long long*)(sb + o_rows);
+  uint8_t* d_flags = (uint8_t*)(sb + o_flags);
+  uint32_t* cbuf = (uint32_t*)(sb + o_ct);
+  if ((rc = ensure_buf(&c->d_mmtab, &c->mmtab_bytes, max_tab * eb))) return rc;
+  HIPCHK(hipMemcpyAsync(d_uid, h.tslot.data(), nnz * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_rows, h.rows.data(), h.rows.size() * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_flags, h.flags.data(), h.flags.size(), hipMemcpyHostToDevice, st));
+  for (const Block& b : blocks) {
+    if ((rc = sd_gather(c, d_ct, nullptr, d_rows + b.roff, b.nd, cbuf, nullptr, st))) return rc;
+    uint32_t* inv = nullptr;
+    if (b.has_neg) {
+      if ((rc = ensure_buf(&c->d_mminv, &c->mminv_bytes, max_nd * W * 4))) return rc;
+      inv = (uint32_t*)c->d_mminv;
+      HIPCHK(hipMemcpyAsync(inv, cbuf, b.nd * W * 4, hipMemcpyDeviceToDevice, st));
+      if ((rc = batch_invert(c, inv, d_flags + b.roff, (long long)b.nd, st))) return rc;
+    }
+    MmTabParams tp{};
+    tp.ct = cbuf;
+    tp.inv = inv;
+    tp.neg_row = d_flags + b.roff;
+    tp.K = (long long)b.nd;
+    tp.mb = 1;
+    tp.kb = (long long)b.nd;
+    tp.has_neg = b.has_neg ? 1 : 0;
+    tp.tab = (uint32_t*)c->d_mmtab;
+    tp.N = c->d_N;
+    tp.R2 = c->d_R2;
+    tp.oneR = c->d_oneR;
+    tp.mprime = c->mprime_N;
+    tp.ct_words = c->ct_words;
+    HIPCHK(mm_tab_launch(c->tpi_e, tp, c->cus, st));
+    SdAccParams ap{};
+    ap.exp = d_exp;
+    ap.x = d_x;
+    ap.dtype = dtype;
+    ap.index = d_index;
+    ap.tslot = d_uid;
+    ap.cstart = d_cstart;
+    ap.q0 = (int)b.q0;
+    ap.q1 = (int)b.q1;
+    ap.ne = (int)b.nd;
+    ap.tab = tp.tab;
+    ap.part = part;
+    ap.pexp = pexp;
+    ap.N = c->d_N;
+    ap.oneR = c->d_oneR;
+    ap.mprime = c->mprime_N;
+    ap.ct_words = c->ct_words;
+    HIPCHK(sd_acc_launch(c->tpi_e, ap, c->cus, st));
+  }
+  return 0;
+}
+
+int pai_segment_dot_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* index,
+                        const int64_t* seg_off, size_t nseg, int dtype, const void* d_x, uint32_t* d_out,
+                        int32_t* d_exp_out, int32_t* d_status, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (nseg == 0) return 0;
+  if (!seg_off || !d_out || !d_exp_out || dtype < 0 || dtype > 2) return fail(PAI_ERR_ARG, "pai_segment_dot_dev: bad arguments");
+  if (seg_off[0] != 0) return fail(PAI_ERR_ARG, "pai_segment_dot_dev: seg_off[0] must be 0");
+  for (size_t s = 0; s < nseg; ++s)
+    if (seg_off[s + 1] < seg_off[s]) return fail(PAI_ERR_ARG, "pai_segment_dot_dev: offsets must not decrease");
+  const size_t nnz = (size_t)seg_off[nseg];
+  if (nnz > 0 && (!d_ct || !d_exp || !index || !d_x)) return fail(PAI_ERR_ARG, "pai_segment_dot_dev: bad arguments");
+  for (size_t t = 0; t < nnz; ++t)
+    if (index[t] < 0 || (size_t)index[t] >= N) return fail(PAI_ERR_ARG, "pai_segment_dot_dev: index out of range");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t W = c->ct_words;
+  auto& h = c->sd;
+  // chunks: ceil(len / MM_KC) per segment, consecutive
+  h.cstart.clear();
+  h.segch.assign(1, 0);
+  for (size_t s = 0; s < nseg; ++s) {
+    for (long long t = seg_off[s]; t < seg_off[s + 1]; t += MM_KC) h.cstart.push_back(t);
+    h.segch.push_back((long long)h.cstart.size());
+  }
+  h.cstart.push_back((long long)nnz);
+  const size_t nch = h.cstart.size() - 1;
+  if (nch >= (size_t)INT32_MAX) return fail(PAI_ERR_ARG, "pai_segment_dot_dev: too many partial products");
+  h.iota.resize(std::max(nch, std::min(nch, sd_slice_chunks()) * MM_KC));
+  for (size_t i = 0; i < h.iota.size(); ++i) h.iota[i] = (long long)i;
+  // the distinct ciphertexts of the call (urows) and every entry's place among them (uid): in order of first use
+  // through a map over the N rows, or ascending through a sort where N dwarfs the entries
+  h.uid.resize(nnz);
+  if (N / 8 <= nnz + 4096) {
+    h.idmap.assign(N, -1);
+    h.urows.clear();
+    for (size_t t = 0; t < nnz; ++t) {
+      int32_t& u = h.idmap[(size_t)index[t]];
+      if (u < 0) {
+        if (h.urows.size() >= (size_t)INT32_MAX - 1) return fail(PAI_ERR_ARG, "pai_segment_dot_dev: too many ciphertexts");
+        u = (int32_t)h.urows.size();
+        h.urows.push_back((long long)index[t]);
+      }
+      h.uid[t] = u;
+    }
+  } else {
+    h.urows.assign(index, index + nnz);
+    std::sort(h.urows.begin(), h.urows.end());
+    h.urows.erase(std::unique(h.urows.begin(), h.urows.end()), h.urows.end());
+    if (h.urows.size() >= (size_t)INT32_MAX) return fail(PAI_ERR_ARG, "pai_segment_dot_dev: too many ciphertexts");
+    for (size_t t = 0; t < nnz; ++t)
+      h.uid[t] = (int32_t)(std::lower_bound(h.urows.begin(), h.urows.end(), (long long)index[t]) - h.urows.begin());
+  }
+  const bool fused = sd_take_fused(c, nnz);
+  c->sd_path = fused ? 2 : 1;
+  const size_t o_pexp = align16(std::max<size_t>(nch, 1) * W * 4);
+  int rc = ensure_buf(&c->d_sdpart, &c->sdpart_bytes, o_pexp + align16(std::max<size_t>(nch, 1) * 4));
+  if (rc) return rc;
+  uint32_t* part = (uint32_t*)c->d_sdpart;
+  int32_t* pexp = (int32_t*)((char*)c->d_sdpart + o_pexp);
+  if (nnz > 0) {
+    const size_t o_cs = align16(nnz * 8), o_uid = align16(o_cs + (nch + 1) * 8);
+    if ((rc = ensure_buf(&c->d_sdmeta, &c->sdmeta_bytes, o_uid + align16(nnz * 4)))) return rc;
+    long long* d_index = (long long*)c->d_sdmeta;
+    long long* d_cstart = (long long*)((char*)c->d_sdmeta + o_cs);
+    int32_t* d_uid = (int32_t*)((char*)c->d_sdmeta + o_uid);
+    static_assert(sizeof(long long) == sizeof(int64_t), "index upload");
+    HIPCHK(hipMemcpyAsync(d_index, index, nnz * 8, hipMemcpyHostToDevice, st));
+    if (fused) {
+      HIPCHK(hipMemcpyAsync(d_cstart, h.cstart.data(), (nch + 1) * 8, hipMemcpyHostToDevice, st));
+      rc = segdot_fused(c, d_ct, d_exp, d_index, d_cstart, d_uid, nnz, dtype, d_x, part, pexp, d_status, st);
+    } else {
+      rc = segdot_terms(c, d_ct, d_exp, d_index, dtype, d_x, part, pexp, d_status, st);
+    }
+    if (rc) {
+      (void)hipStreamSynchronize(st);   // the caller's index array may go once the call has returned
+      return rc;
+    }
+  }
+  // the partials of segment s are rows segch[s] .. segch[s + 1]; an empty segment has none (ciphertext 1, INT32_MIN)
+  return pai_segment_add_dev(c, part, pexp, nch, (const int64_t*)h.iota.data(), (const int64_t*)h.segch.data(), nseg, d_out,
+                             d_exp_out, stream);
+}
+
 int pai_mul(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, int dtype, const void* x, size_t x_stride,
             uint32_t* ct_out, int32_t* exp_out, int32_t* status_out) {
   if (!c) return fail(PAI_ERR_ARG, "null ctx");
@@ -4433,6 +4784,39 @@ int pai_matmul(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t m, siz
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(ct_out, dout, m * d * W * 4, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(exp_out, dexo, m * d * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pai_segment_dot(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, const int64_t* index,
+                    const int64_t* seg_off, size_t nseg, int dtype, const void* x, uint32_t* ct_out, int32_t* exp_out,
+                    int32_t* status_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  if (nseg == 0) return 0;
+  if ((N && (!ct || !exp)) || !seg_off || !ct_out || !exp_out || dtype < 0 || dtype > 2 || seg_off[0] != 0 ||
+      seg_off[nseg] < 0 || (seg_off[nseg] > 0 && !x))
+    return fail(PAI_ERR_ARG, "pai_segment_dot: bad arguments");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t W = c->ct_words, esz = dtype == PAI_F32 ? 4 : 8, nnz = (size_t)seg_off[nseg];
+  DevScope ds;
+  uint32_t* dct = ds.alloc<uint32_t>(N * W);
+  int32_t* dexp = ds.alloc<int32_t>(N);
+  void* dx = ds.alloc<uint8_t>(nnz * esz);
+  uint32_t* dout = ds.alloc<uint32_t>(nseg * W);
+  int32_t* dexo = ds.alloc<int32_t>(nseg);
+  int32_t* dst = ds.alloc<int32_t>(nnz);
+  if (!dct || !dexp || !dx || !dout || !dexo || !dst) return fail(PAI_ERR_HIP, "pai_segment_dot: device allocation failed");
+  if (N) {
+    HIPCHK(hipMemcpy(dct, ct, N * W * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dexp, exp, N * 4, hipMemcpyHostToDevice));
+  }
+  if (nnz) HIPCHK(hipMemcpy(dx, x, nnz * esz, hipMemcpyHostToDevice));
+  int rc = pai_segment_dot_dev(c, dct, dexp, N, index, seg_off, nseg, dtype, dx, dout, dexo, dst, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(ct_out, dout, nseg * W * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(exp_out, dexo, nseg * 4, hipMemcpyDeviceToHost));
+  if (status_out && nnz) HIPCHK(hipMemcpy(status_out, dst, nnz * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 

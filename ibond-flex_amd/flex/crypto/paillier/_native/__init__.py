@@ -32,6 +32,7 @@ PAI_OPT_SPLIT_SAMPLER, PAI_OPT_ROWS_MAX = 13, 14
 PAI_OPT_CRT4_MIN = 15
 PAI_OPT_MATMUL_FUSED, PAI_OPT_MATMUL_PATH = 16, 17
 PAI_OPT_OBF_CHUNK = 18
+PAI_OPT_SEGDOT_FUSED, PAI_OPT_SEGDOT_PATH = 20, 21     # 19 is not assigned
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
 PFB_NBASES = 33
 
@@ -47,7 +48,8 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_next_prime", "pai_prime_last_times", "pai_prime_test", "pai_debug_prime_sieve",
             "pai_obfuscate", "pai_obfuscate_dev",
             "pai_pack_max_slots", "pai_encrypt_packed", "pai_encrypt_packed_dev", "pai_decrypt_packed",
-            "pai_decrypt_packed_dev", "pai_pack_ciphertexts", "pai_pack_ciphertexts_dev")
+            "pai_decrypt_packed_dev", "pai_pack_ciphertexts", "pai_pack_ciphertexts_dev",
+            "pai_segment_dot", "pai_segment_dot_dev")
 PAI_COMM_ID_BYTES = 128
 
 _lib = None
@@ -114,6 +116,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_add_plain_dev.argtypes = [P, P, P, S, I, P, S, P, P, P, P]
         lib.pai_segment_add.argtypes = [P, P, P, S, P, P, S, P, P]
         lib.pai_segment_add_dev.argtypes = [P, P, P, S, P, P, S, P, P, P]
+        lib.pai_segment_dot.argtypes = [P, P, P, S, P, P, S, I, P, P, P, P]
+        lib.pai_segment_dot_dev.argtypes = [P, P, P, S, P, P, S, I, P, P, P, P, P]
         lib.pai_matmul.argtypes = [P, P, P, S, S, I, P, S, P, P]
         lib.pai_matmul_dev.argtypes = [P, P, P, S, S, I, P, S, P, P, P]
         lib.pai_comm_unique_id.argtypes = [P]
@@ -387,6 +391,21 @@ class Context:
     def matmul_path(self) -> int:
         """The path of this context's last matmul call: 0 = none yet, 1 = term path, 2 = fused."""
         return int(self._get_option(PAI_OPT_MATMUL_PATH))
+
+    @property
+    def segdot_fused(self) -> bool:
+        """True when segment_dot may run the fused windowed multi-exponentiation (kernels_sd.hpp: the default, for calls
+        with enough reuse per distinct ciphertext and enough chunks to fill the chip), False for the term path always."""
+        return bool(self._get_option(PAI_OPT_SEGDOT_FUSED))
+
+    def set_segdot_fused(self, enabled: bool):
+        """False keeps segment_dot on gather + k_mul + batch inversion + segmented add over all entries; same bits."""
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_SEGDOT_FUSED, 1 if enabled else 0))
+
+    @property
+    def segdot_path(self) -> int:
+        """The path of this context's last segment_dot call: 0 = none yet, 1 = term path, 2 = fused."""
+        return int(self._get_option(PAI_OPT_SEGDOT_PATH))
 
     @property
     def obf_chunk(self) -> int:
@@ -738,6 +757,31 @@ class Context:
         self._chk(self.lib.pai_segment_add(self._h, _ptr(ct), _ptr(exp), exp.size, _ptr(index), _ptr(seg_off), nseg,
                                         _ptr(out), _ptr(oe)))
         return out, oe
+
+    def segment_dot(self, ct: np.ndarray, exp: np.ndarray, index: np.ndarray, seg_off: np.ndarray, x: np.ndarray):
+        """Per-segment weighted sums: segment s = sum over t in [seg_off[s], seg_off[s+1]) of ct[index[t]] (x) x[t]
+        (x: one float32 / float64 / int64 scalar per entry). Returns (words [nseg, W], exponents [nseg], statuses
+        [nnz], pai_mul's); an empty segment gives ciphertext 1 and exponent INT32_MIN."""
+        ct = np.ascontiguousarray(ct, dtype=np.uint32)
+        exp = np.ascontiguousarray(exp, dtype=np.int32)
+        index = np.ascontiguousarray(index, dtype=np.int64)
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.int64)
+        x = np.ascontiguousarray(x)
+        nseg = seg_off.size - 1
+        self._check_words(ct, exp, exp.size)
+        if x.ndim != 1 or x.size != index.size:
+            raise ValueError("segment_dot: one scalar per index entry")
+        if nseg >= 0 and seg_off.size and int(seg_off[-1]) != index.size:
+            raise ValueError("segment_dot: seg_off[-1] must equal the number of entries")
+        self.calls["pai_segment_dot"] += 1
+        out = np.empty((max(nseg, 0), self.ct_words), dtype=np.uint32)
+        oe = np.empty(max(nseg, 0), dtype=np.int32)
+        st = np.zeros(index.size, dtype=np.int32)
+        if nseg <= 0:
+            return out, oe, st
+        self._chk(self.lib.pai_segment_dot(self._h, _ptr(ct), _ptr(exp), exp.size, _ptr(index), _ptr(seg_off), nseg,
+                                        scalar_dtype(x), _ptr(x), _ptr(out), _ptr(oe), _ptr(st)))
+        return out, oe, st
 
     def matmul(self, ct: np.ndarray, exp: np.ndarray, m: int, K: int, x: np.ndarray, d: int):
         """(m x K encrypted) @ (K x d plain) -> (m d ciphertext words, m d exponents), row-major."""

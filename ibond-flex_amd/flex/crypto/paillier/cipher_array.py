@@ -202,13 +202,17 @@ class PaillierArray(np.ndarray):
         return np.ndarray.__truediv__(np.asarray(self), other)
 
     def dot(self, b, out=None):
-        res = dot_plain(self, b) if out is None else NotImplemented
+        res = dot_sparse(self, b) if out is None else NotImplemented
+        if res is NotImplemented and out is None:
+            res = dot_plain(self, b)
         if res is NotImplemented:
             return np.asarray(self).dot(b, out) if out is not None else np.asarray(self).dot(b)
         return res
 
     def __matmul__(self, b):
-        res = dot_plain(self, b)
+        res = dot_sparse(self, b)
+        if res is NotImplemented:
+            res = dot_plain(self, b)
         if res is NotImplemented:
             return np.ndarray.__matmul__(np.asarray(self), b)
         return res
@@ -465,6 +469,27 @@ def dot_plain(a, b):
     shape = tuple(([m] if A.ndim == 2 else []) + ([d] if x.ndim == 2 else []))
     res = materialize(pk, out, oe, shape if shape else (1,), obfuscated=False)
     return res.reshape(-1)[0] if not shape else res
+
+
+def dot_sparse(a, b):
+    """Encrypted (K,) or (m, K) array times a sparse (K, d) matrix (any object that offers .tocsc(); scipy is not
+    imported): every output is the sum over the column's STORED entries, explicit zeros included, as one
+    segmented weighted sum (pai_segment_dot; Python integers without a GPU). NotImplemented for other operands."""
+    from .cipher_buffer import segment_dot_args, segment_dot_words, sparse_csc, sparse_segments
+    csc = sparse_csc(b)
+    if csc is None:
+        return NotImplemented
+    A, pk = _encrypted_operand(a)
+    if A is None or A.ndim not in (1, 2):
+        return NotImplemented
+    indptr, indices, data, (K, d) = csc
+    if K != A.shape[-1]:
+        raise ValueError(f"dot: shapes {A.shape} and {(K, d)} not aligned")
+    m = A.shape[0] if A.ndim == 2 else 1
+    words, exps, _ = pack(a if A is a else A, pk)
+    idx, off, w = segment_dot_args(exps.size, *sparse_segments(indptr, indices, data, m, K, d))
+    out, oe = segment_dot_words(pk, words, exps, idx, off, w)
+    return materialize(pk, out, oe, (m, d) if A.ndim == 2 else (d,), obfuscated=False)
 
 
 # ------------------------------------------------------------------ ciphertext + plaintext

@@ -177,8 +177,31 @@ class CiphertextBuffer(object):
     def __truediv__(self, s):
         return self * (1 / s)
 
+    def segment_dot(self, index, seg_off, weights) -> "CiphertextBuffer":
+        """Segmented weighted sums, shape (nseg,): out[s] = sum over t in [seg_off[s], seg_off[s+1]) of
+        self[index[t]] * weights[t] (flat indices; pai_segment_dot, one call). Each term is the reference's __mul__, each
+        sum its __add__ chain; a weight that does not encode raises ValueError naming its position. An empty segment
+        is ciphertext 1 at exponent 0, an unobfuscated encryption of 0. Without a GPU the same runs on Python integers."""
+        idx, off, w = segment_dot_args(self.size, index, seg_off, weights)
+        out, oe = segment_dot_words(self.public_key, self.words, self.exps, idx, off, w)
+        return self._like(out, oe, 0, (off.size - 1,))
+
+    def _dot_sparse(self, csc):
+        indptr, indices, data, (K, d) = csc
+        if len(self.shape) not in (1, 2) or K != self.shape[-1]:
+            raise ValueError(f"dot: shapes {self.shape} and {(K, d)} not aligned")
+        m = self.shape[0] if len(self.shape) == 2 else 1
+        idx, off, w = sparse_segments(indptr, indices, data, m, K, d)
+        out = self.segment_dot(idx, off, w)
+        return out.reshape((m, d) if len(self.shape) == 2 else (d,))
+
     def dot(self, b):
-        """(K,) or (m, K) encrypted @ (K,) or (K, d) plain, numpy semantics (he_otp_lr_ft1/train.py:160)."""
+        """(K,) or (m, K) encrypted @ (K,) or (K, d) plain, numpy semantics (he_otp_lr_ft1/train.py:160). A sparse
+        (K, d) matrix (anything that offers .tocsc()) runs as segment_dot over its stored entries, explicit zeros
+        included: columns are the segments, row i of an (m, K) buffer offsets the indices by i K."""
+        csc = sparse_csc(b)
+        if csc is not None:
+            return self._dot_sparse(csc)
         x = np.asarray(b)
         if len(self.shape) not in (1, 2) or x.ndim not in (1, 2) or x.shape[0] != self.shape[-1]:
             raise ValueError(f"dot: shapes {self.shape} and {x.shape} not aligned")
@@ -214,6 +237,89 @@ def add_buffers(bufs: Sequence[CiphertextBuffer]) -> CiphertextBuffer:
         return a
     out, oe = a._ctx().add([b.words for b in bufs], [b.exps for b in bufs])
     return a._like(out, oe)
+
+
+def sparse_csc(b):
+    """(indptr, indices, data, shape) of a 2-D sparse matrix in CSC form, for any object that offers .tocsc() (duck
+    typing: scipy is not imported here); None for everything else."""
+    if isinstance(b, np.ndarray) or not hasattr(b, "tocsc"):
+        return None
+    c = b.tocsc()
+    shape = tuple(int(v) for v in c.shape)
+    if len(shape) != 2:
+        raise ValueError(f"dot: sparse operand of shape {shape} is not a matrix")
+    indptr = np.asarray(c.indptr, dtype=np.int64).reshape(-1)
+    indices = np.asarray(c.indices, dtype=np.int64).reshape(-1)
+    data = np.asarray(c.data).reshape(-1)
+    if indptr.size != shape[1] + 1 or indices.size != data.size:
+        raise ValueError("dot: malformed CSC operand")
+    return indptr, indices, data, shape
+
+
+def sparse_segments(indptr, indices, data, m: int, K: int, d: int):
+    """(index, seg_off, weights) of an (m, K) encrypted times (K, d) CSC product: segment i d + j is column j over the
+    ciphertexts of row i."""
+    nnz = indices.size
+    if indices.size and (indices.min() < 0 or indices.max() >= K):
+        raise ValueError("dot: sparse row index out of range")
+    idx = (indices[None, :] + (np.arange(m, dtype=np.int64) * K)[:, None]).reshape(-1)
+    off = (indptr[None, :-1] + (np.arange(m, dtype=np.int64) * nnz)[:, None]).reshape(-1)
+    off = np.concatenate([off, [m * nnz]]).astype(np.int64)
+    return idx, off, np.tile(data, m)
+
+
+def segment_dot_args(N: int, index, seg_off, weights):
+    """Checked (index int64 [nnz], seg_off int64 [nseg + 1], weights of a device dtype [nnz])."""
+    from .cipher_array import _plain_array
+    idx = np.asarray(index)
+    off = np.asarray(seg_off)
+    w = np.asarray(weights)
+    if idx.ndim != 1 or off.ndim != 1 or w.ndim != 1:
+        raise ValueError("segment_dot: index, seg_off and weights must be one-dimensional")
+    if (idx.size and idx.dtype.kind not in "iu") or (off.dtype.kind not in "iu"):
+        raise TypeError("segment_dot: index and seg_off must be integers")
+    idx = idx.astype(np.int64)
+    off = off.astype(np.int64)
+    if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+        raise ValueError("segment_dot: seg_off must start at 0 and must not decrease")
+    if off[-1] != idx.size or w.size != idx.size:
+        raise ValueError(f"segment_dot: {idx.size} indices, {w.size} weights, seg_off ends at {int(off[-1])}")
+    if idx.size and (idx.min() < 0 or idx.max() >= N):
+        raise IndexError(f"segment_dot: index out of range for {N} ciphertexts")
+    x = _plain_array(w) if w.size else w.astype(np.float64)
+    if x is None:
+        raise TypeError(f"segment_dot: unsupported weight dtype {w.dtype}")
+    return idx, off, np.ascontiguousarray(x)
+
+
+def segment_dot_words(pk, words, exps, idx, off, w):
+    """(words [nseg, W], exponents [nseg]) of the segmented weighted sums over checked arguments: pai_segment_dot on the
+    GPU, the per-element operators on Python integers without one. Empty segments: ciphertext 1, exponent 0."""
+    from . import _runtime
+    nseg = off.size - 1
+    W = words.shape[1]
+    if _runtime.gpu_available():
+        out, oe, st = _runtime.context(pk).segment_dot(words, exps, idx, off, w)
+        bad = np.flatnonzero(st)
+        if bad.size:
+            t = int(bad[0])
+            raise ValueError(f"segment_dot: weight {w[t]!r} at index {t} does not encode")
+        oe = np.where(np.diff(off) == 0, 0, oe).astype(np.int32)
+        return out, oe
+    cts = _ints(words)
+    vals, oe = [], []
+    for s in range(nseg):
+        acc = None
+        for t in range(int(off[s]), int(off[s + 1])):
+            i = int(idx[t])
+            try:
+                term = PaillierEncryptedNumber(pk, cts[i], int(exps[i])) * w[t]
+            except (ValueError, OverflowError) as e:
+                raise ValueError(f"segment_dot: weight {w[t]!r} at index {t} does not encode") from e
+            acc = term if acc is None else acc + term
+        vals.append(1 if acc is None else acc.ciphertext(False))
+        oe.append(0 if acc is None else acc.exponent)
+    return _runtime.ints_to_words(vals, W).reshape(nseg, W), np.array(oe, dtype=np.int32)
 
 
 def _plain(y, N: int) -> np.ndarray:

@@ -88,6 +88,40 @@ def segment_sum(x: np.ndarray, index_lists) -> list:
     return res
 
 
+def segment_dot(x: np.ndarray, index_lists, weight_lists) -> list:
+    """``[sum(x[i] * w for i, w in zip(idx, ws)) for idx, ws in zip(index_lists, weight_lists)]`` (weighted per-bin sums,
+    sparse gradient columns) as ONE segmented weighted sum on the GPU (pai_segment_dot), shaped like segment_sum: the
+    ``0 + S`` of Python's sum follows as one batched add_plain, and an empty segment gives the int 0. Without a GPU the
+    same runs on Python integers."""
+    from .cipher_array import _encrypted_operand, materialize, pack
+    from .cipher_buffer import segment_dot_args, segment_dot_words
+    lists = [np.asarray(i).reshape(-1) for i in index_lists]
+    wlists = [np.asarray(w).reshape(-1) for w in weight_lists]
+    if len(lists) != len(wlists) or any(i.size != w.size for i, w in zip(lists, wlists)):
+        raise ValueError("segment_dot: index_lists and weight_lists differ in shape")
+    flat = np.asarray(x).reshape(-1)
+    A, pk = _encrypted_operand(flat)
+    if A is None:
+        return [sum(flat[i] * w for i, w in zip(idx.tolist(), ws)) for idx, ws in zip(lists, wlists)]
+    sizes = np.array([len(i) for i in lists], dtype=np.int64)
+    idx = np.concatenate(lists).astype(np.int64) if sizes.sum() else np.zeros(0, dtype=np.int64)
+    idx = np.where(idx < 0, idx + flat.size, idx)          # numpy negative indices, like x[i]
+    wts = np.concatenate(wlists) if sizes.sum() else np.zeros(0, dtype=np.float64)
+    seg_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    words, exps, _ = pack(x, pk)
+    out, oe = segment_dot_words(pk, words, exps, *segment_dot_args(exps.size, idx, seg_off, wts))
+    nz = np.flatnonzero(sizes)
+    res = [0] * len(lists)
+    if nz.size:
+        sums = materialize(pk, out[nz], oe[nz], (nz.size,), obfuscated=False)
+        total = add_plain(sums, 0)                          # Python's sum starts from the int 0
+        if total is NotImplemented:
+            total = np.array([0 + s for s in sums], dtype=object)
+        for k, s in zip(nz.tolist(), np.asarray(total).reshape(-1)):
+            res[k] = s
+    return res
+
+
 def segment_sum_packed(x, index_lists, layout, max_abs):
     """The per-bin sums of segment_sum as ONE PackedCiphertextBuffer (packed_buffer.py): one pai_segment_add call, then
     one pai_pack_ciphertexts call that folds layout.slots bin sums into each ciphertext, so the key holder decrypts

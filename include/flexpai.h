@@ -24,6 +24,8 @@
  *   pai_matmul[_dev]      <- ndarray.dot of encrypted by plain (he_otp_lr_ft1/train.py:160,
  *                            he_otp_lr_ft2/train.py:188): per output sum_k c_ik (x) x_kj, i.e. __mul__ then
  *                            __add__ (encrypted_number.py:65-69, 86-113, 166-185)
+ *   pai_segment_dot[_dev] <- the same dot over the STORED entries of a sparse plain matrix, and weighted per-bin
+ *                            sums: per segment sum_t c[index[t]] (x) x[t], __mul__ then __add__
  *   pai_obfuscate[_dev]   <- PaillierEncryptedNumber.apply_obfuscation / ciphertext(be_secure=True) over arrays
  *                            (encrypted_number.py:50-63 -> apply_obfuscation obfuscator.py:23-37): c * r^n mod n^2
  *   pai_next_prime        <- gmpy2.next_prime(r) of getprimeover    flex/crypto/gmpy_math.py:77-87, the two prime
@@ -188,6 +190,15 @@ typedef struct pai_comm pai_comm;
 
 #define PAI_OPT_OBF_CHUNK 18     /* elements per slice of an in-place pai_obfuscate_dev (default 262 144, at least 64): the
                                   * call keeps r^n of one slice in a buffer of the context. Same bits for every value */
+#define PAI_OPT_SEGDOT_FUSED 20  /* 1 (default): pai_segment_dot[_dev] runs the fused windowed multi-exponentiation
+                                  * (kernels_sd.hpp: k_sd_sign, k_mm_tab over the distinct ciphertexts of a block of
+                                  * chunks, k_sd_acc, then the segmented add over the chunk partials) for the calls it was
+                                  * measured faster on: at least 65 536 entries that reuse every table the blocks
+                                  * build at least 16 times (1024 and 2048 bits on an MI355X; the
+                                  * same constants at 4096 bits, unmeasured); 0: every call gathers its entries and runs k_mul,
+                                  * one batch inversion and the segmented add over them. Same bits either way */
+#define PAI_OPT_SEGDOT_PATH 21   /* read-only: the path of this context's last pai_segment_dot[_dev] call: 0 = none yet,
+                                  * 1 = term path, 2 = fused                                                     */
 
 /* Number of visible GPUs (0 when there is none or the runtime cannot start). */
 int pai_device_count(int* count);
@@ -315,6 +326,24 @@ int pai_add_plain(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N
  * with exponent INT32_MIN. The _dev variant synchronises `stream` once per reduction level. */
 int pai_segment_add(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, const int64_t* index,
                     const int64_t* seg_off, size_t nseg, uint32_t* ct_out, int32_t* exp_out);
+/* Segmented weighted sum, the sparse encrypted-by-plain product: out_s = sum over t in [seg_off[s], seg_off[s+1]) of
+ * ct[index[t]] (x) x[t]. index holds nnz = seg_off[nseg] entries in [0, N) and may repeat an entry inside a segment and
+ * across segments; seg_off holds nseg + 1 non-decreasing offsets, seg_off[0] = 0; both are host arrays in both variants,
+ * as for pai_segment_add. x holds nnz scalars of PAI_F32 / PAI_F64 / PAI_I64 aligned with index (a device pointer in the
+ * _dev variant). A bad index, a decreasing offset or a null pointer is PAI_ERR_ARG before any launch.
+ *   Term t of segment s is ct[index[t]] (x) x[t] exactly as pai_mul forms it: FixedPointNumber.encode of the scalar,
+ *   invert(ct) for a negative mantissa, exponent exp[index[t]] + e(x[t]). The terms of a segment are summed with
+ *   __add__'s alignment to the segment's largest exponent; stored zeros count towards that maximum, as in pai_matmul.
+ *   An empty segment yields ciphertext 1 with exponent INT32_MIN. ct_out and exp_out equal, bit for bit, pai_mul over
+ *   the gathered entries followed by pai_segment_add over consecutive ranges, entries whose scalar does not encode
+ *   included (the factor 1); status_out (nullable, nnz entries) holds pai_mul's statuses. A ciphertext without inverse
+ *   mod n^2 that meets a negative scalar ends the call with PAI_ERR_NOINV. The output is not re-randomised.
+ * PAI_OPT_SEGDOT_FUSED / PAI_OPT_SEGDOT_PATH: window tables are built once per distinct ciphertext that a block of
+ * chunks (16 consecutive entries of one segment) references, so the cost follows the stored entries; same bits on
+ * either path. The _dev variant synchronises `stream` (sign flags, batch inversion, every level of the segmented add). */
+int pai_segment_dot(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, const int64_t* index,
+                    const int64_t* seg_off, size_t nseg, int dtype, const void* x, uint32_t* ct_out, int32_t* exp_out,
+                    int32_t* status_out);
 /* Encrypted (m x K, row-major ciphertexts + exponents) times plain (K x d, row-major, dtype as above):
  * out[i][j] = sum_k ct[i][k] (x) x[k][j] with the reference's exponent alignment (bit-identical to
  * numpy's object dot over PaillierEncryptedNumber, whose sums are order independent). By default a product of
@@ -356,6 +385,9 @@ int pai_segment_add_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp
                         const int64_t* seg_off, size_t nseg, uint32_t* d_out, int32_t* d_exp_out, void* stream);
 int pai_matmul_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t m, size_t K, int dtype,
                    const void* d_x, size_t d, uint32_t* d_out, int32_t* d_exp_out, void* stream);
+int pai_segment_dot_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* index,
+                        const int64_t* seg_off, size_t nseg, int dtype, const void* d_x, uint32_t* d_out,
+                        int32_t* d_exp_out, int32_t* d_status, void* stream);
 
 /* Packed plaintexts: many signed fixed-point values per ciphertext (no reference counterpart; opt-in, both peers must
  * be flexpai; csrc/kernels_pack.hpp). Every packed ciphertext is an ordinary reference ciphertext
