@@ -56,6 +56,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_sd.hpp"
 #include "engine_obf.hpp"
 #include "engine_pack.hpp"
+#include "engine_pool.hpp"
 #include "engine_crtw.hpp"
 #include "engine_pe1.hpp"
 #include "engine_pe4.hpp"
@@ -265,6 +266,20 @@ struct pai_ctx {
   void* d_pack = nullptr;
   size_t pack_bytes = 0;
   uint32_t* d_pack_consts = nullptr;
+  // obfuscator pool (kernels_pool.hpp): a FIFO ring of ready r^n in split rows, the constants of its kernels (they depend
+  // on n alone and are uploaded with the first ring), and the plain rho of the composed path (PAI_OPT_POOL_FUSED = 0)
+  struct Pool {
+    uint32_t* rows = nullptr;     // [cap][row_words], dev_malloc
+    size_t cap = 0, head = 0, ready = 0;
+    uint64_t taken = 0;           // entries consumed over the context's life
+    int row_words = 0;
+    uint32_t *d_nneg = nullptr, *d_R2n = nullptr, *d_R2n84 = nullptr;
+    uint32_t nprime = 0, dprime = 0;
+    bool consts = false;
+    bool fused = true;            // PAI_OPT_POOL_FUSED
+    void* d_rho = nullptr;
+    size_t rho_bytes = 0;
+  } pool;
   // fused matrix product (kernels_mm.hpp): PAI_OPT_MATMUL_FUSED / PAI_OPT_MATMUL_PATH
   bool mm_fused = true;
   int mm_path = 0;              // last pai_matmul[_dev] call: 0 none yet, 1 term path, 2 fused
@@ -393,6 +408,8 @@ pai_ctx::~pai_ctx() {
   if (d_plain) (void)hipFree(d_plain);
   if (d_obf) (void)hipFree(d_obf);
   if (d_pack) (void)hipFree(d_pack);
+  if (pool.rows) (void)hipFree(pool.rows);
+  if (pool.d_rho) (void)hipFree(pool.d_rho);
   if (d_seg) (void)hipFree(d_seg);
   if (d_addplan) (void)hipFree(d_addplan);
 }
@@ -2100,6 +2117,7 @@ static int setup_crt(pai_ctx* c, const HBig& p, const HBig& q) {
 }
 
 static int set_private_impl(pai_ctx* c, HBig p, HBig q);
+static void pool_drop(pai_ctx* c);
 
 // Transactional: on any failure every private-key allocation of this call is released and the
 // context is left exactly as before (public-key operations keep working, a retry starts clean).
@@ -2113,6 +2131,7 @@ int pai_ctx_set_private(pai_ctx* c, const uint8_t* p_le, const uint8_t* q_le, si
   if (cmp(p, q) == 0) return fail(PAI_ERR_KEY, "p and q have to be different");
   if (cmp(q, p) < 0) std::swap(p, q);   // keypair.py:57-62
   if (c->has_priv) return 0;            // same key (p q == n): already set
+  pool_drop(c);                         // the pool belongs to the party the context was; a key holder fills its own
   c->in_priv = true;
   int rc;
   {
@@ -2217,6 +2236,7 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       return 0;
     case PAI_OPT_MATMUL_FUSED: c->mm_fused = value != 0; return 0;
     case PAI_OPT_SEGDOT_FUSED: c->sd_fused = value != 0; return 0;
+    case PAI_OPT_POOL_FUSED: c->pool.fused = value != 0; return 0;
     case PAI_OPT_OBF_CHUNK:
       if (value < 64) return fail(PAI_ERR_ARG, "PAI_OPT_OBF_CHUNK must be >= 64");
       c->obf_chunk = value;
@@ -2257,6 +2277,7 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_MATMUL_PATH: *value = c->mm_path; return 0;
     case PAI_OPT_SEGDOT_FUSED: *value = c->sd_fused ? 1 : 0; return 0;
     case PAI_OPT_SEGDOT_PATH: *value = c->sd_path; return 0;
+    case PAI_OPT_POOL_FUSED: *value = c->pool.fused ? 1 : 0; return 0;
     case PAI_OPT_OBF_CHUNK: *value = c->obf_chunk; return 0;
     case PAI_OPT_STAGE_TIMING: *value = c->timing ? 1 : 0; return 0;
     case PAI_OPT_LANE_DECRYPT: *value = (c->dec_lane_ok && c->dec_lane_enabled) ? 1 : 0; return 0;
@@ -3213,6 +3234,9 @@ static int launch_crt4(pai_ctx* c, const EncParams& e, hipStream_t st) {
 static int encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mode, int32_t fixed_exp, int obf_mode,
                        const uint32_t* d_r_words, size_t r_stride_words, size_t r_words, const uint8_t* rng_key32,
                        uint64_t index_base, uint32_t* d_ct, int32_t* d_exp, int32_t* d_status, hipStream_t st);
+static int pool_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mode, int32_t fixed_exp,
+                            uint32_t* d_ct, int32_t* d_exp, int32_t* d_status, hipStream_t st);
+static int pool_check_take(pai_ctx* c, size_t N, const char* who);
 
 int pai_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mode, int32_t fixed_exp, int obf_mode,
                     const uint32_t* d_r_words, size_t r_stride_words, size_t r_words, const uint8_t* rng_key32,
@@ -3224,6 +3248,8 @@ int pai_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mo
   if (obf_mode == PAI_OBF_GIVEN && (!d_r_words || r_words == 0 || r_words > (size_t)c->ct_words))
     return fail(PAI_ERR_ARG, "pai_encrypt_dev: r must be given with 0 < r_words <= ct_words");
   if (obf_mode == PAI_OBF_RNG && !rng_key32) return fail(PAI_ERR_ARG, "pai_encrypt_dev: rng key required");
+  if (obf_mode == PAI_OBF_POOL)
+    return pool_encrypt_dev(c, dtype, d_x, N, exp_mode, fixed_exp, d_ct, d_exp, d_status, (hipStream_t)stream);
   if (obf_mode < 0 || obf_mode > 2) return fail(PAI_ERR_ARG, "pai_encrypt_dev: bad obf_mode");
   return encrypt_dev(c, dtype, d_x, N, exp_mode, fixed_exp, obf_mode, d_r_words, r_stride_words, r_words, rng_key32,
                      index_base, d_ct, d_exp, d_status, (hipStream_t)stream);
@@ -3344,6 +3370,8 @@ static int launch_obf_mul(pai_ctx* c, const uint32_t* ct, const uint32_t* s, uin
   return 0;
 }
 
+static int pool_obfuscate_dev(pai_ctx* c, const uint32_t* d_ct, size_t N, uint32_t* d_out, hipStream_t st);
+
 // r^n is the encryption of the integer 0 (c0 = 1) by the same route as pai_encrypt_dev takes for these N elements, this
 // obfuscator and this index_base; then one k_obf_mul. Out of place r^n goes straight into d_out; in place the call walks
 // slices of obf_chunk elements through a buffer of its own (not ensure_work's: the encrypt chains reallocate that one
@@ -3355,8 +3383,8 @@ int pai_obfuscate_dev(pai_ctx* c, const uint32_t* d_ct, size_t N, int obf_mode, 
   CtxLock lk(c, (hipStream_t)stream);
   if (N == 0) return 0;
   if (!d_ct || !d_out) return fail(PAI_ERR_ARG, "pai_obfuscate_dev: bad arguments");
-  if (obf_mode != PAI_OBF_GIVEN && obf_mode != PAI_OBF_RNG)
-    return fail(PAI_ERR_ARG, "pai_obfuscate_dev: obf_mode must be PAI_OBF_GIVEN or PAI_OBF_RNG");
+  if (obf_mode != PAI_OBF_GIVEN && obf_mode != PAI_OBF_RNG && obf_mode != PAI_OBF_POOL)
+    return fail(PAI_ERR_ARG, "pai_obfuscate_dev: obf_mode must be PAI_OBF_GIVEN, PAI_OBF_RNG or PAI_OBF_POOL");
   if (obf_mode == PAI_OBF_GIVEN && (!d_r_words || r_words == 0 || r_words > (size_t)c->ct_words))
     return fail(PAI_ERR_ARG, "pai_obfuscate_dev: r must be given with 0 < r_words <= ct_words");
   if (obf_mode == PAI_OBF_RNG && !rng_key32) return fail(PAI_ERR_ARG, "pai_obfuscate_dev: rng key required");
@@ -3366,6 +3394,7 @@ int pai_obfuscate_dev(pai_ctx* c, const uint32_t* d_ct, size_t N, int obf_mode, 
     return fail(PAI_ERR_ARG, "pai_obfuscate_dev: d_out must be d_ct or not overlap it");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
+  if (obf_mode == PAI_OBF_POOL) return pool_obfuscate_dev(c, d_ct, N, d_out, st);
   const size_t CH = in_place ? std::min(N, (size_t)c->obf_chunk) : N;
   const size_t rn_bytes = in_place ? align16(CH * W * 4) : 0, x_bytes = align16(CH * 8), e_bytes = align16(CH * 4);
   int rc = ensure_buf(&c->d_obf, &c->obf_bytes, rn_bytes + x_bytes + 2 * e_bytes);
@@ -3384,6 +3413,242 @@ int pai_obfuscate_dev(pai_ctx* c, const uint32_t* d_ct, size_t N, int obf_mode, 
                           index_base + off, s, ex, status, st)))
       return rc;
     if ((rc = launch_obf_mul(c, d_ct + off * W, s, d_out + off * W, (long long)n, st))) return rc;
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------ obfuscator pool (kernels_pool.hpp)
+// A FIFO ring of ready r^n owned by the context. Fills and puts append at (head + ready) % cap, takes advance head; both
+// move under the context's mutex when the call enqueues its work, and the device work of successive calls is ordered by
+// the context's tail event, so a fill is complete before the take that follows it, on any stream.
+
+// Waits for the context's queued device work, then frees the ring (re-keying, pai_pool_reserve)
+static void pool_drop(pai_ctx* c) {
+  pai_ctx::Pool& pl = c->pool;
+  if (!pl.rows) return;
+  if (c->tail_ev) (void)hipEventSynchronize(c->tail_ev);
+  (void)hipFree(pl.rows);
+  pl.rows = nullptr;
+  pl.cap = pl.head = pl.ready = 0;
+}
+
+// The constants of the pool kernels: they depend on n alone and stay with the context
+static int pool_consts(pai_ctx* c) {
+  pai_ctx::Pool& pl = c->pool;
+  if (pl.consts) return 0;
+  const int S = c->S_e;
+  const size_t Rbits = (size_t)LB * S;
+  const HBig nneg = sub(pow2(Rbits), c->n);
+  int rc;
+  if ((rc = upload_to(c->allocs, nneg.limbs(S, LB), &pl.d_nneg)) ||
+      (rc = upload_to(c->allocs, mul_pow2_mod(HBig(1), 2 * Rbits, c->n).limbs(S, LB), &pl.d_R2n)) ||
+      (rc = upload_to(c->allocs, mul_pow2_mod(HBig(1), 2 * Rbits + 3 * LB, c->n).limbs(S, LB), &pl.d_R2n84)))
+    return rc;
+  pl.nprime = mont_prime(c->n, LB);
+  pl.dprime = mont_prime(nneg, LB);
+  pl.row_words = 2 * c->pt_words;
+  pl.consts = true;
+  return 0;
+}
+
+static PoolRing pool_ring(const pai_ctx* c, size_t first) {
+  const pai_ctx::Pool& pl = c->pool;
+  return PoolRing{pl.rows, (long long)pl.cap, (long long)first, pl.row_words, c->pt_words};
+}
+
+static int pool_grid(pai_ctx* c, int which, long long n) {
+  int occ = 1;
+  if (pool_occupancy(c->tpi_e, which, &occ)) return 0;
+  const int gpb = BLOCK / c->tpi_e;
+  return (int)std::max<long long>(1, std::min<long long>((n + gpb - 1) / gpb, (long long)occ * c->cus));
+}
+
+static int pool_check_take(pai_ctx* c, size_t N, const char* who) {
+  const pai_ctx::Pool& pl = c->pool;
+  if (!pl.rows) return fail(PAI_ERR_ARG, std::string(who) + ": PAI_OBF_POOL without a pool (pai_pool_reserve)");
+  if (N > pl.ready)
+    return fail(PAI_ERR_ARG, std::string(who) + ": the call takes " + std::to_string(N) + " obfuscators, the pool holds " +
+                                 std::to_string(pl.ready));
+  return 0;
+}
+
+// The head moves here, when the call is about to enqueue its work: whatever happens afterwards, these entries are spent
+static size_t pool_advance(pai_ctx* c, size_t N) {
+  pai_ctx::Pool& pl = c->pool;
+  const size_t first = pl.head;
+  pl.head = (pl.head + N) % pl.cap;
+  pl.ready -= N;
+  pl.taken += N;
+  return first;
+}
+
+static int pool_check_room(pai_ctx* c, size_t count, const char* who) {
+  const pai_ctx::Pool& pl = c->pool;
+  if (!pl.rows) return fail(PAI_ERR_ARG, std::string(who) + ": no pool (pai_pool_reserve)");
+  if (count > pl.cap - pl.ready)
+    return fail(PAI_ERR_ARG, std::string(who) + ": " + std::to_string(count) + " entries do not fit the " +
+                                 std::to_string(pl.cap - pl.ready) + " free of " + std::to_string(pl.cap));
+  return 0;
+}
+
+// plain rho [n][W] -> the n ring rows behind the ready ones, which they join
+static int pool_append(pai_ctx* c, const uint32_t* d_rho, size_t n, hipStream_t st) {
+  pai_ctx::Pool& pl = c->pool;
+  PoolSplitParams p{};
+  p.rho = d_rho;
+  p.ring = pool_ring(c, (pl.head + pl.ready) % pl.cap);
+  p.n = (long long)n;
+  p.nl = c->d_nl;
+  p.nneg = pl.d_nneg;
+  p.R2n = pl.d_R2n;
+  p.R2n84 = pl.d_R2n84;
+  p.nprime = pl.nprime;
+  p.dprime = pl.dprime;
+  p.ct_words = c->ct_words;
+  const int grid = pool_grid(c, 2, p.n);
+  if (!grid) return fail(PAI_ERR_KEY, "unsupported group size");
+  HIPCHK(pool_split_launch(c->tpi_e, p, grid, st));
+  pl.ready += n;
+  return 0;
+}
+
+static PoolEncParams pool_enc_params(pai_ctx* c, size_t first, size_t N, uint32_t* d_ct) {
+  PoolEncParams p{};
+  p.ring = pool_ring(c, first);
+  p.dst.ct = d_ct;
+  p.dst.ct_words = c->ct_words;
+  p.n = (long long)N;
+  p.nl = c->d_nl;
+  p.nprime = c->pool.nprime;
+  return p;
+}
+
+// rows first .. first + N (wrapping) -> plain rho words
+static int pool_join(pai_ctx* c, size_t first, size_t N, uint32_t* d_rho, hipStream_t st) {
+  const PoolEncParams p = pool_enc_params(c, first, N, d_rho);
+  const int grid = pool_grid(c, 1, p.n);
+  if (!grid) return fail(PAI_ERR_KEY, "unsupported group size");
+  HIPCHK(pool_join_launch(c->tpi_e, p, grid, st));
+  return 0;
+}
+
+// pai_encrypt_dev with PAI_OBF_POOL below its argument checks: k_pool_enc, or (PAI_OPT_POOL_FUSED = 0) the kernels already
+// pinned to the reference: k_pool_join, the PAI_OBF_NONE encryption, k_obf_mul
+static int pool_encrypt_dev(pai_ctx* c, int dtype, const void* d_x, size_t N, int exp_mode, int32_t fixed_exp,
+                            uint32_t* d_ct, int32_t* d_exp, int32_t* d_status, hipStream_t st) {
+  int rc = pool_check_take(c, N, "pai_encrypt_dev");
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  if (!c->pool.fused && (rc = ensure_buf(&c->pool.d_rho, &c->pool.rho_bytes, N * c->ct_words * 4))) return rc;
+  const size_t first = pool_advance(c, N);
+  if (c->pool.fused) {
+    PoolEncParams p = pool_enc_params(c, first, N, d_ct);
+    p.src = EncPlain{d_x, dtype, exp_mode, fixed_exp};
+    p.dst.exp = d_exp;
+    p.dst.status = d_status;
+    const int grid = pool_grid(c, 0, p.n);
+    if (!grid) return fail(PAI_ERR_KEY, "unsupported group size");
+    stage_reset(c);
+    stage_mark(c, 0, st);
+    HIPCHK(pool_enc_launch(c->tpi_e, p, grid, st));
+    stage_mark(c, 1, st);
+    return 0;
+  }
+  uint32_t* rho = (uint32_t*)c->pool.d_rho;
+  if ((rc = pool_join(c, first, N, rho, st))) return rc;
+  if ((rc = encrypt_dev(c, dtype, d_x, N, exp_mode, fixed_exp, PAI_OBF_NONE, nullptr, 0, 0, nullptr, 0, d_ct, d_exp,
+                        d_status, st)))
+    return rc;
+  return launch_obf_mul(c, d_ct, rho, d_ct, (long long)N, st);
+}
+
+// pai_obfuscate_dev with PAI_OBF_POOL: the pooled rho joined straight into d_out (out of place) or, slice by slice, into
+// the buffer the in-place call keeps its r^n in; then k_obf_mul
+static int pool_obfuscate_dev(pai_ctx* c, const uint32_t* d_ct, size_t N, uint32_t* d_out, hipStream_t st) {
+  int rc = pool_check_take(c, N, "pai_obfuscate_dev");
+  if (rc) return rc;
+  const size_t W = c->ct_words;
+  const bool in_place = d_out == d_ct;
+  const size_t CH = in_place ? std::min(N, (size_t)c->obf_chunk) : N;
+  if (in_place && (rc = ensure_buf(&c->d_obf, &c->obf_bytes, align16(CH * W * 4)))) return rc;
+  const size_t first = pool_advance(c, N);
+  for (size_t off = 0; off < N; off += CH) {
+    const size_t n = std::min(CH, N - off);
+    uint32_t* s = in_place ? (uint32_t*)c->d_obf : d_out + off * W;
+    if ((rc = pool_join(c, (first + off) % c->pool.cap, n, s, st))) return rc;
+    if ((rc = launch_obf_mul(c, d_ct + off * W, s, d_out + off * W, (long long)n, st))) return rc;
+  }
+  return 0;
+}
+
+int pai_pool_reserve(pai_ctx* c, size_t capacity) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  HIPCHK(hipSetDevice(c->device));
+  pool_drop(c);
+  if (capacity == 0) return 0;
+  int rc = pool_consts(c);
+  if (rc) return rc;
+  void* rows = nullptr;
+  HIPCHK(dev_malloc(&rows, capacity * c->pool.row_words * 4));
+  c->pool.rows = (uint32_t*)rows;
+  c->pool.cap = capacity;
+  return 0;
+}
+
+int pai_pool_info(pai_ctx* c, uint64_t* capacity, uint64_t* ready, uint64_t* taken_total) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  if (capacity) *capacity = c->pool.cap;
+  if (ready) *ready = c->pool.ready;
+  if (taken_total) *taken_total = c->pool.taken;
+  return 0;
+}
+
+int pai_pool_put_dev(pai_ctx* c, const uint32_t* d_rho, size_t count, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (count == 0) return 0;
+  if (!d_rho) return fail(PAI_ERR_ARG, "pai_pool_put_dev: null buffer");
+  const int rc = pool_check_room(c, count, "pai_pool_put_dev");
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  return pool_append(c, d_rho, count, (hipStream_t)stream);
+}
+
+// Entry j is what pai_encrypt_dev writes for int64 zero at global index index_base + j: the encryption runs by that
+// call's route into a slice buffer (the one pai_obfuscate_dev's in-place call keeps), one sampler decision for all
+// `count` entries (ObfCall), and k_pool_split moves each slice into the ring
+int pai_pool_fill_dev(pai_ctx* c, size_t count, int obf_mode, const uint32_t* d_r_words, size_t r_stride_words,
+                      size_t r_words, const uint8_t* rng_key32, uint64_t index_base, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (obf_mode != PAI_OBF_GIVEN && obf_mode != PAI_OBF_RNG)
+    return fail(PAI_ERR_ARG, "pai_pool_fill_dev: obf_mode must be PAI_OBF_GIVEN or PAI_OBF_RNG");
+  if (obf_mode == PAI_OBF_GIVEN && (!d_r_words || r_words == 0 || r_words > (size_t)c->ct_words))
+    return fail(PAI_ERR_ARG, "pai_pool_fill_dev: r must be given with 0 < r_words <= ct_words");
+  if (obf_mode == PAI_OBF_RNG && !rng_key32) return fail(PAI_ERR_ARG, "pai_pool_fill_dev: rng key required");
+  if (count == 0) return 0;
+  int rc = pool_check_room(c, count, "pai_pool_fill_dev");
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t W = c->ct_words, CH = std::min(count, (size_t)c->obf_chunk);
+  const size_t rn_bytes = align16(CH * W * 4), x_bytes = align16(CH * 8), e_bytes = align16(CH * 4);
+  if ((rc = ensure_buf(&c->d_obf, &c->obf_bytes, rn_bytes + x_bytes + 2 * e_bytes))) return rc;
+  uint32_t* rn = (uint32_t*)c->d_obf;
+  int64_t* zeros = (int64_t*)((char*)c->d_obf + rn_bytes);
+  int32_t* ex = (int32_t*)((char*)zeros + x_bytes);
+  int32_t* status = (int32_t*)((char*)ex + e_bytes);
+  HIPCHK(hipMemsetAsync(zeros, 0, CH * 8, st));
+  ObfCall oc(c, obf_mode, (long long)count);
+  for (size_t off = 0; off < count; off += CH) {
+    const size_t n = std::min(CH, count - off);
+    if ((rc = encrypt_dev(c, PAI_I64, zeros, n, PAI_EXP_AUTO, 0, obf_mode,
+                          d_r_words ? d_r_words + off * r_stride_words : nullptr, r_stride_words, r_words, rng_key32,
+                          index_base + off, rn, ex, status, st)))
+      return rc;
+    if ((rc = pool_append(c, rn, n, st))) return rc;
   }
   return 0;
 }
@@ -4913,6 +5178,11 @@ int pai_encrypt(pai_ctx* c, int dtype, const void* x, size_t N, int exp_mode, in
   if (N == 0) return 0;
   if (!x || !ct_out || !exp_out) return fail(PAI_ERR_ARG, "pai_encrypt: null buffer");
   if (obf_mode == PAI_OBF_GIVEN && (!r_le || r_bytes == 0)) return fail(PAI_ERR_ARG, "pai_encrypt: r required");
+  if (obf_mode == PAI_OBF_POOL) {   // the whole call or nothing: its chunks then take their entries in order
+    if (dtype < 0 || dtype > 2) return fail(PAI_ERR_ARG, "pai_encrypt: bad dtype");
+    const int prc = pool_check_take(c, N, "pai_encrypt");
+    if (prc) return prc;
+  }
   HIPCHK(hipSetDevice(c->device));
   const size_t esz = dtype == PAI_F32 ? 4 : 8, W = c->ct_words;
   const size_t r_words = obf_mode == PAI_OBF_GIVEN ? (r_bytes + 3) / 4 : 0;
@@ -5037,8 +5307,12 @@ int pai_obfuscate(pai_ctx* c, const uint32_t* ct, size_t N, int obf_mode, const 
   CtxLock lk(c);
   if (N == 0) return 0;
   if (!ct || !ct_out) return fail(PAI_ERR_ARG, "pai_obfuscate: null buffer");
-  if (obf_mode != PAI_OBF_GIVEN && obf_mode != PAI_OBF_RNG)
-    return fail(PAI_ERR_ARG, "pai_obfuscate: obf_mode must be PAI_OBF_GIVEN or PAI_OBF_RNG");
+  if (obf_mode != PAI_OBF_GIVEN && obf_mode != PAI_OBF_RNG && obf_mode != PAI_OBF_POOL)
+    return fail(PAI_ERR_ARG, "pai_obfuscate: obf_mode must be PAI_OBF_GIVEN, PAI_OBF_RNG or PAI_OBF_POOL");
+  if (obf_mode == PAI_OBF_POOL) {   // the whole call or nothing: its chunks then take their entries in order
+    const int prc = pool_check_take(c, N, "pai_obfuscate");
+    if (prc) return prc;
+  }
   if (obf_mode == PAI_OBF_GIVEN && (!r_le || r_bytes == 0 || r_bytes > (size_t)c->ct_words * 4))
     return fail(PAI_ERR_ARG, "pai_obfuscate: r must be given with 0 < r_bytes <= 4 ct_words");
   if (obf_mode == PAI_OBF_RNG && !rng_key32) return fail(PAI_ERR_ARG, "pai_obfuscate: rng key required");
@@ -5095,6 +5369,59 @@ int pai_obfuscate(pai_ctx* c, const uint32_t* ct, size_t N, int obf_mode, const 
   HIPCHK(hipStreamSynchronize(sc));
   HIPCHK(hipStreamSynchronize(sy));
   return 0;
+}
+
+// The host-buffer sides of the pool: the words go up once into the host-io buffer and the device call follows on the
+// context's compute stream; both wait for it, like their neighbours
+static int pool_host_upload(pai_ctx* c, const std::vector<uint32_t>& words, uint32_t** d_out) {
+  if (!c->s_comp) HIPCHK(hipStreamCreateWithFlags(&c->s_comp, hipStreamNonBlocking));
+  if (c->tail_ev) HIPCHK(hipEventSynchronize(c->tail_ev));   // the buffer may still be read by the previous call
+  const int rc = ensure_buf(&c->d_hostio, &c->hostio_bytes, std::max<size_t>(words.size(), 1) * 4);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(c->d_hostio, words.data(), words.size() * 4, hipMemcpyHostToDevice, c->s_comp));
+  HIPCHK(hipStreamSynchronize(c->s_comp));
+  *d_out = (uint32_t*)c->d_hostio;
+  return 0;
+}
+
+int pai_pool_put(pai_ctx* c, const uint32_t* rho, size_t count) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  if (count == 0) return 0;
+  if (!rho) return fail(PAI_ERR_ARG, "pai_pool_put: null buffer");
+  int rc = pool_check_room(c, count, "pai_pool_put");
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  uint32_t* d = nullptr;
+  if ((rc = pool_host_upload(c, std::vector<uint32_t>(rho, rho + count * c->ct_words), &d))) return rc;
+  rc = pai_pool_put_dev(c, d, count, c->s_comp);
+  HIPCHK(hipStreamSynchronize(c->s_comp));
+  return rc;
+}
+
+int pai_pool_fill(pai_ctx* c, size_t count, int obf_mode, const uint8_t* r_le, size_t r_stride_bytes, size_t r_bytes,
+                  const uint8_t* rng_key32, uint64_t index_base) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  if (obf_mode != PAI_OBF_GIVEN && obf_mode != PAI_OBF_RNG)
+    return fail(PAI_ERR_ARG, "pai_pool_fill: obf_mode must be PAI_OBF_GIVEN or PAI_OBF_RNG");
+  if (obf_mode == PAI_OBF_GIVEN && (!r_le || r_bytes == 0 || r_bytes > (size_t)c->ct_words * 4))
+    return fail(PAI_ERR_ARG, "pai_pool_fill: r must be given with 0 < r_bytes <= 4 ct_words");
+  if (obf_mode == PAI_OBF_RNG && !rng_key32) return fail(PAI_ERR_ARG, "pai_pool_fill: rng key required");
+  if (count == 0) return 0;
+  int rc = pool_check_room(c, count, "pai_pool_fill");
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t r_words = obf_mode == PAI_OBF_GIVEN ? (r_bytes + 3) / 4 : 0;
+  const size_t r_cnt = obf_mode == PAI_OBF_GIVEN ? (r_stride_bytes ? count : 1) : 0;
+  std::vector<uint32_t> hr(r_cnt * r_words, 0);
+  for (size_t i = 0; i < r_cnt; ++i) std::memcpy(&hr[i * r_words], r_le + i * r_stride_bytes, r_bytes);
+  uint32_t* dr = nullptr;
+  if ((rc = pool_host_upload(c, hr, &dr))) return rc;
+  rc = pai_pool_fill_dev(c, count, obf_mode, r_cnt ? dr : nullptr, r_stride_bytes ? r_words : 0, r_words, rng_key32,
+                         index_base, c->s_comp);
+  HIPCHK(hipStreamSynchronize(c->s_comp));
+  return rc;
 }
 
 int pai_decrypt(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, double* val_out, int64_t* mant_out,

@@ -23,6 +23,7 @@ XCHECK_LIB_PATH = os.path.join(_HERE, "libflexpai_xcheck.so")
 
 PAI_F32, PAI_F64, PAI_I64 = 0, 1, 2
 PAI_OBF_NONE, PAI_OBF_GIVEN, PAI_OBF_RNG = 0, 1, 2
+PAI_OBF_POOL = 3     # the call's obfuscators come from the context's pool (pai_pool_*), in order, each exactly once
 PAI_EXP_AUTO, PAI_EXP_FIXED = 0, 1
 EL_OK, EL_INT, EL_INT_BIG, EL_OVERFLOW, EL_FLOAT_OVF, EL_ENC_RANGE = 0, 1, 2, 3, 4, 5
 
@@ -33,6 +34,7 @@ PAI_OPT_CRT4_MIN = 15
 PAI_OPT_MATMUL_FUSED, PAI_OPT_MATMUL_PATH = 16, 17
 PAI_OPT_OBF_CHUNK = 18
 PAI_OPT_SEGDOT_FUSED, PAI_OPT_SEGDOT_PATH = 20, 21     # 19 is not assigned
+PAI_OPT_POOL_FUSED = 22
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
 PFB_NBASES = 33
 
@@ -49,7 +51,8 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_obfuscate", "pai_obfuscate_dev",
             "pai_pack_max_slots", "pai_encrypt_packed", "pai_encrypt_packed_dev", "pai_decrypt_packed",
             "pai_decrypt_packed_dev", "pai_pack_ciphertexts", "pai_pack_ciphertexts_dev",
-            "pai_segment_dot", "pai_segment_dot_dev")
+            "pai_segment_dot", "pai_segment_dot_dev",
+            "pai_pool_reserve", "pai_pool_fill", "pai_pool_fill_dev", "pai_pool_put", "pai_pool_put_dev", "pai_pool_info")
 PAI_COMM_ID_BYTES = 128
 
 _lib = None
@@ -103,6 +106,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_decrypt_dev.argtypes = [P, P, P, S, P, P, P, P, P]
         lib.pai_obfuscate.argtypes = [P, P, S, I, P, S, S, P, U64, P]
         lib.pai_obfuscate_dev.argtypes = [P, P, S, I, P, S, S, P, U64, P, P]
+        lib.pai_pool_reserve.argtypes = [P, S]
+        lib.pai_pool_fill.argtypes = [P, S, I, P, S, S, P, U64]
+        lib.pai_pool_fill_dev.argtypes = [P, S, I, P, S, S, P, U64, P]
+        lib.pai_pool_put.argtypes = [P, P, S]
+        lib.pai_pool_put_dev.argtypes = [P, P, S, P]
+        lib.pai_pool_info.argtypes = [P, P, P, P]
         lib.pai_pack_max_slots.argtypes = [P, I, P]
         lib.pai_encrypt_packed.argtypes = [P, I, P, S, P, I, P, S, S, P, U64, P, P]
         lib.pai_encrypt_packed_dev.argtypes = [P, I, P, S, P, I, P, S, S, P, U64, P, P, P]
@@ -626,6 +635,54 @@ class Context:
         self._chk(self.lib.pai_obfuscate(self._h, _ptr(ct), N, obf_mode, _ptr(r_buf) if r_buf is not None else None,
                                          r_stride, r_bytes, key, index_base, _ptr(out)))
         return out
+
+    # ----------------------------------------------------------------- obfuscator pool (include/flexpai.h)
+    def pool_reserve(self, capacity: int):
+        """(Re)allocate the ring of ready obfuscators for `capacity` entries, dropping its contents; 0 frees it."""
+        self._chk(self.lib.pai_pool_reserve(self._h, int(capacity)))
+
+    def pool_fill(self, count: int, obf_mode: int = PAI_OBF_RNG, r: Optional[Sequence[int]] = None,
+                  r_scalar: Optional[int] = None, rng_key: Optional[bytes] = None, index_base: int = 0):
+        """Append `count` entries: entry j is what encrypt writes for the integer 0 at global index index_base + j with
+        this obf_mode (PAI_OBF_GIVEN or PAI_OBF_RNG) and r or key, by that encryption's route."""
+        r_buf, r_stride, r_bytes = None, 0, 0
+        if obf_mode == PAI_OBF_GIVEN:
+            r_bytes = self.ct_words * 4
+            if r_scalar is not None:
+                r_buf = np.frombuffer(int_to_le(r_scalar, r_bytes), dtype=np.uint8).copy()
+            else:
+                r_buf = np.frombuffer(b"".join(int_to_le(v, r_bytes) for v in r), dtype=np.uint8).copy()
+                r_stride = r_bytes
+        key = rng_key if rng_key is not None else os.urandom(32)
+        self.calls["pai_pool_fill"] += 1
+        self._chk(self.lib.pai_pool_fill(self._h, int(count), obf_mode, _ptr(r_buf) if r_buf is not None else None,
+                                         r_stride, r_bytes, key, index_base))
+
+    def pool_put(self, rho):
+        """Append caller-made obfuscators: [count, ct_words] uint32 words, or a sequence of ints, each < n^2."""
+        if not isinstance(rho, np.ndarray):
+            rho = ints_to_words(rho, self.ct_words)
+        rho = np.ascontiguousarray(rho, dtype=np.uint32)
+        if rho.ndim != 2 or rho.shape[1] != self.ct_words:
+            raise ValueError(f"obfuscator buffer shape {rho.shape} does not match (count, {self.ct_words})")
+        self.calls["pai_pool_put"] += 1
+        self._chk(self.lib.pai_pool_put(self._h, _ptr(rho), rho.shape[0]))
+
+    def pool_info(self) -> Tuple[int, int, int]:
+        """(capacity, ready, taken_total)."""
+        cap, ready, taken = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self.lib.pai_pool_info(self._h, ctypes.byref(cap), ctypes.byref(ready), ctypes.byref(taken)))
+        return int(cap.value), int(ready.value), int(taken.value)
+
+    @property
+    def pool_fused(self) -> bool:
+        """True when pooled encryption runs k_pool_enc (the default), False for k_pool_join + the PAI_OBF_NONE
+        encryption + k_obf_mul."""
+        return bool(self._get_option(PAI_OPT_POOL_FUSED))
+
+    def set_pool_fused(self, enabled: bool):
+        """Same bits either way."""
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_POOL_FUSED, 1 if enabled else 0))
 
     # ----------------------------------------------------------------- packed plaintexts (include/flexpai.h)
     def pack_max_slots(self, slot_bits: int) -> int:

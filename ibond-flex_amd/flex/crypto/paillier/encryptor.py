@@ -61,14 +61,17 @@ class PaillierEncryptor(object):
 
     def _encrypt_numpy(self, values_numpy: np.ndarray, precision: int = None, random_value: int = None) -> np.ndarray:
         """encryptor.py:71-97, one batched GPU launch."""
-        from . import _native, _runtime
+        from . import _native, _runtime, obfuscator_pool
         from .cipher_array import PaillierArray, materialize
         s = values_numpy.shape
         flat = values_numpy.reshape(-1)
         if flat.size == 0:
             return PaillierArray(np.array([], dtype=object).reshape(s))
         x, bad = _device_input(flat)
-        if x is None:
+        # without a GPU, obfuscators prepared ahead of time that cover the array serve it element by element
+        host_pool = (x is not None and random_value is None
+                     and obfuscator_pool.obfuscators_ready(self.pub_key) >= flat.size and not _runtime.gpu_available())
+        if x is None or host_pool:
             # mixed object arrays and non-numeric dtypes: per-element semantics of the reference
             # (raises the same TypeError for unsupported element types)
             el = [self._encrypt(v, precision, random_value) for v in flat]
@@ -80,7 +83,12 @@ class PaillierEncryptor(object):
             exp_mode, fixed_exp = _native.PAI_EXP_FIXED, math.floor(math.log(precision, FixedPointNumber.BASE))
         ctx = _runtime.context(self.pub_key)
         if random_value is None:
-            ct, ex, st = ctx.encrypt(x, exp_mode, fixed_exp, _native.PAI_OBF_RNG)
+            with obfuscator_pool.lock:       # obfuscators prepared ahead of time, when they cover the whole array
+                pooled = obfuscator_pool.device_pool(self.pub_key, x.size)
+                if pooled is not None:
+                    ct, ex, st = pooled.encrypt(x, exp_mode, fixed_exp, _native.PAI_OBF_POOL)
+            if pooled is None:
+                ct, ex, st = ctx.encrypt(x, exp_mode, fixed_exp, _native.PAI_OBF_RNG)
             obfuscated = True
         elif random_value:
             ct, ex, st = ctx.encrypt(x, exp_mode, fixed_exp, _native.PAI_OBF_GIVEN,
@@ -104,7 +112,7 @@ class PaillierEncryptor(object):
         """Encrypt an array into a CiphertextBuffer (cipher_buffer.py): the device words, exponents and
         obfuscation flags, no PaillierEncryptedNumber per element. Same ciphertext distribution as
         encrypt(values); for callers that ship (to_wire) or sum ciphertexts without touching them."""
-        from . import _native, _runtime
+        from . import _native, _runtime, obfuscator_pool
         from .cipher_buffer import CiphertextBuffer
         values = np.asarray(values)
         s = values.shape
@@ -115,7 +123,12 @@ class PaillierEncryptor(object):
         if precision is not None:
             exp_mode, fixed_exp = _native.PAI_EXP_FIXED, math.floor(math.log(precision, FixedPointNumber.BASE))
         ctx = _runtime.context(self.pub_key)
-        ct, ex, st = ctx.encrypt(x, exp_mode, fixed_exp, _native.PAI_OBF_RNG)
+        with obfuscator_pool.lock:           # obfuscators prepared ahead of time, when they cover the whole array
+            pooled = obfuscator_pool.device_pool(self.pub_key, x.size)
+            if pooled is not None:
+                ct, ex, st = pooled.encrypt(x, exp_mode, fixed_exp, _native.PAI_OBF_POOL)
+        if pooled is None:
+            ct, ex, st = ctx.encrypt(x, exp_mode, fixed_exp, _native.PAI_OBF_RNG)
         bad_idx = np.nonzero(st != _native.EL_OK)[0]
         if bad_idx.size:
             # beyond the device's 64-bit fixed-point range: the host encoder (raises like the reference)
@@ -147,6 +160,16 @@ class PaillierEncryptor(object):
             raise ValueError(f"encrypt_packed: value at index {int(bad[0])} is outside the layout's range "
                              f"(|v * 16^{layout.exponent}| <= 2^{layout.value_bits - 1} - 1)")
         return PackedCiphertextBuffer(self.pub_key, ct, layout, x.size, values.shape, obfuscated=True)
+
+    def prepare_obfuscators(self, count: int, chunk: int = 65536) -> int:
+        """Draw `count` obfuscators r^n now, while this party waits for its peer; the encryptions and
+        re-randomisations that follow spend one each instead of an exponentiation (obfuscator_pool.py)."""
+        from . import obfuscator_pool
+        return obfuscator_pool.prepare_obfuscators(self.pub_key, count, chunk)
+
+    def obfuscators_ready(self) -> int:
+        from . import obfuscator_pool
+        return obfuscator_pool.obfuscators_ready(self.pub_key)
 
     def encrypt(self, value, precision: int = None, random_value: int = None):
         """encryptor.py:99-114"""

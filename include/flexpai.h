@@ -28,6 +28,8 @@
  *                            sums: per segment sum_t c[index[t]] (x) x[t], __mul__ then __add__
  *   pai_obfuscate[_dev]   <- PaillierEncryptedNumber.apply_obfuscation / ciphertext(be_secure=True) over arrays
  *                            (encrypted_number.py:50-63 -> apply_obfuscation obfuscator.py:23-37): c * r^n mod n^2
+ *   pai_pool_*            <- (no reference counterpart) r^n mod n^2 drawn ahead of time into a ring of the context; PAI_OBF_POOL
+ *                            encryptions and re-randomisations then spend one entry each, (1 + n m) rho mod n^2
  *   pai_next_prime        <- gmpy2.next_prime(r) of getprimeover    flex/crypto/gmpy_math.py:77-87, the two prime
  *                            searches of generate_paillier_keypair  flex/crypto/paillier/keypair.py:93-127 (one batch):
  *                            a sieve by the odd primes below 2000 on the host, then Miller-Rabin on 16-lane rows
@@ -94,6 +96,8 @@ typedef struct pai_comm pai_comm;
 #define PAI_OBF_NONE 0   /* random_value == 0 : c = 1 + n*m                      (encryptor.py:61-67) */
 #define PAI_OBF_GIVEN 1  /* explicit r per element (r_stride 0 = one r for all)  (obfuscator.py:35)  */
 #define PAI_OBF_RNG 2    /* device ChaCha20 CSPRNG keyed by rng_key, nonce = global element index    */
+#define PAI_OBF_POOL 3   /* take the call's obfuscators from the context's pool, in order, each exactly once
+                            (pai_pool_*, below); pai_encrypt[_dev] and pai_obfuscate[_dev] only              */
 
 /* exponent modes for encode (fixedpoint_number.py:63-82) */
 #define PAI_EXP_AUTO 0   /* precision=None: exponent from frexp / 0 for ints */
@@ -199,6 +203,9 @@ typedef struct pai_comm pai_comm;
                                   * one batch inversion and the segmented add over them. Same bits either way */
 #define PAI_OPT_SEGDOT_PATH 21   /* read-only: the path of this context's last pai_segment_dot[_dev] call: 0 = none yet,
                                   * 1 = term path, 2 = fused                                                     */
+#define PAI_OPT_POOL_FUSED 22    /* 1 (default): pai_encrypt[_dev] with PAI_OBF_POOL runs k_pool_enc (kernels_pool.hpp: the
+                                  * half-width product a + n ((b + M a) mod n)); 0: k_pool_join, the PAI_OBF_NONE
+                                  * encryption and k_obf_mul, the kernels pinned to the reference. Same bits either way */
 
 /* Number of visible GPUs (0 when there is none or the runtime cannot start). */
 int pai_device_count(int* count);
@@ -449,6 +456,51 @@ int pai_pack_ciphertexts(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, s
                          const pai_pack_layout* layout, uint32_t* ct_out, int32_t* status_out);
 int pai_pack_ciphertexts_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N,
                              const pai_pack_layout* layout, uint32_t* d_out, int32_t* d_status, void* stream);
+
+/* Obfuscator pool: r^n drawn ahead of time (no reference counterpart: the reference draws r and raises it to n inside
+ * every encrypt, obfuscator.py:23-37). r^n does not depend on the plaintext, so a party draws obfuscators while it waits
+ * for its peer and spends one per fresh ciphertext when the plaintext arrives: the online step is (1 + n m) rho mod n^2
+ * alone (csrc/kernels_pool.hpp, DESIGN.md §5 "Pooled obfuscators"). The pool is a FIFO ring of ready obfuscators in device
+ * memory, one per context, owned by the context.
+ *
+ *   pai_pool_reserve   (re)allocates the ring for `capacity` entries, dropping its contents; 0 frees it. 2 ceil(key bits
+ *                      / 32) words per entry (the W words of a ciphertext; 512 MB per 2^20 entries at 2048 bits), from the
+ *                      allocator of the call buffers: released table memory goes back to the driver first when the device
+ *                      is full. Waits for the context's queued device work.
+ *   pai_pool_fill[_dev] appends `count` entries. Entry j is, bit for bit, the E0 that pai_encrypt_dev writes for int64
+ *                      zero at global index index_base + j with the same obf_mode (PAI_OBF_GIVEN or PAI_OBF_RNG; anything
+ *                      else is PAI_ERR_ARG), r or rng key, on the same context state: the fill takes that encryption's
+ *                      route (csrc/encrypt_route.hpp) and counts towards the same break-even counters, exactly as
+ *                      pai_obfuscate does (one sampler decision per fill), so pooled ciphertexts have the distribution of
+ *                      the party's ordinary ones. Arguments as for pai_encrypt / pai_encrypt_dev.
+ *   pai_pool_put[_dev] appends caller-made rho rows [count][W], each < n^2 (the parity tests; obfuscators made on another
+ *                      device). The caller vouches that they are n-th residues of uniform r; the arithmetic is right for
+ *                      every rho < n^2.
+ *   pai_pool_info      capacity, ready entries, entries taken over the context's life (each nullable).
+ *
+ * Ring limits: a fill or put of more than capacity - ready entries is PAI_ERR_ARG; nothing is appended and unconsumed
+ *   entries are never overwritten. A take of more than `ready` (or without a ring) is PAI_ERR_ARG with both numbers in
+ *   pai_last_error(); nothing is consumed. A host-buffer call checks its whole count before its first chunk.
+ * Consumers: pai_encrypt[_dev] and pai_obfuscate[_dev] accept PAI_OBF_POOL; r and rng arguments are ignored. Element i
+ *   of the call uses the entry at head + i, wrapping at capacity: out_i = (1 + n m_i) rho_i mod n^2, and ct_i rho_i mod
+ *   n^2. Exponents and statuses are exactly those of the same call with PAI_OBF_NONE; an element whose status is not OK
+ *   still consumes its entry. pai_encrypt_packed[_dev] with PAI_OBF_POOL is PAI_ERR_ARG.
+ * Exactly once: a call advances the head under the context's mutex when it enqueues its work, and a call that fails
+ *   after that point does not give entries back: two ciphertexts under one rho reveal the difference of their
+ *   plaintexts ("Obfuscator keys").
+ * Lifetime: pai_ctx_set_private (re-keying) and pai_ctx_destroy drop the pool.
+ * Threads and streams: the rule of the other entry points holds -- calls on one context run one after the other, and a
+ *   _dev call's stream first waits for the context's previous device work -- so a fill is complete before the take that
+ *   follows it, on any stream. An encryption that arrives during a long fill therefore waits for it: fill in slices
+ *   (the Python layer's prepare_obfuscators fills 65 536 entries per call). */
+int pai_pool_reserve(pai_ctx* ctx, size_t capacity);
+int pai_pool_fill(pai_ctx* ctx, size_t count, int obf_mode, const uint8_t* r_le, size_t r_stride_bytes, size_t r_bytes,
+                  const uint8_t* rng_key32, uint64_t index_base);
+int pai_pool_fill_dev(pai_ctx* ctx, size_t count, int obf_mode, const uint32_t* d_r_words, size_t r_stride_words,
+                      size_t r_words, const uint8_t* rng_key32, uint64_t index_base, void* stream);
+int pai_pool_put(pai_ctx* ctx, const uint32_t* rho, size_t count);
+int pai_pool_put_dev(pai_ctx* ctx, const uint32_t* d_rho, size_t count, void* stream);
+int pai_pool_info(pai_ctx* ctx, uint64_t* capacity, uint64_t* ready, uint64_t* taken_total);
 
 /* Multi-GPU: ciphertext shards -> every rank (RCCL, opened with dlopen on first use; one process per GPU).
  * Rank 0 calls pai_comm_unique_id and hands the PAI_COMM_ID_BYTES bytes to the other ranks over any
