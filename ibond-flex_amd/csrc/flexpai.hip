@@ -54,6 +54,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_mul.hpp"
 #include "engine_mm.hpp"
 #include "engine_sd.hpp"
+#include "engine_hist.hpp"
 #include "engine_obf.hpp"
 #include "engine_pack.hpp"
 #include "engine_pool.hpp"
@@ -305,6 +306,20 @@ struct pai_ctx {
     std::vector<int32_t> uid, tslot, idmap;
     std::vector<uint8_t> neg, flags;
   } sd;
+  // histograms (kernels_hist.hpp): the scratch budget of one feature block, the device buffers and the host sides
+  // of the metadata (they outlive the call's asynchronous copies)
+  size_t hist_scratch = (size_t)256 << 20;
+  void* d_histmeta = nullptr;   // counts (when the caller wants none), member offsets, cursors, runs
+  size_t histmeta_bytes = 0;
+  void* d_histwork = nullptr;   // one feature block's member lists and gather rows
+  size_t histwork_bytes = 0;
+  void* d_histpart = nullptr;   // the runs' partials and their exponents
+  size_t histpart_bytes = 0;
+  struct HistHost {
+    std::vector<long long> cnt, index, segoff;
+    std::vector<int32_t> cell_off;
+    std::vector<int2> runs;
+  } hist;
   void* d_inv = nullptr;        // batch-inversion prefix products and segment products
   size_t inv_bytes = 0;
   std::vector<uint32_t> inv_host;   // top of the inversion tree (host side of an async copy)
@@ -400,6 +415,9 @@ pai_ctx::~pai_ctx() {
   if (d_sdmeta) (void)hipFree(d_sdmeta);
   if (d_sdbuf) (void)hipFree(d_sdbuf);
   if (d_sdpart) (void)hipFree(d_sdpart);
+  if (d_histmeta) (void)hipFree(d_histmeta);
+  if (d_histwork) (void)hipFree(d_histwork);
+  if (d_histpart) (void)hipFree(d_histpart);
   if (d_inv) (void)hipFree(d_inv);
   if (inv_async) {
     if (inv_async->pin) (void)hipHostFree(inv_async->pin);
@@ -5023,6 +5041,289 @@ int pai_segment_add(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(ct_out, dout, nseg * W * 4, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(exp_out, dexo, nseg * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ------------------------------------------------------------------ histograms (kernels_hist.hpp)
+// Cell sums of one ciphertext vector over an [N][F] matrix of bin ids and an optional node id per sample. The counts
+// of all cells come back to the host once (k_hist_count; the closing segmented add needs host offsets anyway); every
+// cell is cut into runs of HIST_RUN members. The features are then processed in blocks whose member lists fit the
+// scratch budget: k_hist_scatter places the sample ids and one k_hist_acc launch reads the lists and writes a canonical
+// partial per run at the run's largest exponent (the test build's other variant: k_hist_rows turns the runs into gather
+// rows, which then count towards the budget, and k_add sums them). A partial is the exact
+// residue of its run, so the bits depend neither on the order inside a list nor on runs or blocks. The runs of a cell
+// are consecutive rows of its block; the closing pai_segment_add_dev names them through an index of one entry per RUN
+// (the identity when the call is one block).
+//
+// HIST_MAX_CELLS: counts, member offsets and cursors take 16 bytes per cell on the device and 28 on the host, and the
+// outputs W words: 2^24 cells are 8 GiB of output at 2048 bits, beyond which no caller's buffer goes.
+constexpr size_t HIST_MAX_CELLS = (size_t)1 << 24;
+constexpr size_t HIST_HOST_CHUNK = 65536;          // samples per chunk of the host-buffer variant
+constexpr size_t HIST_HOST_PART_BYTES = (size_t)1 << 30;   // bound on the chunks' cell sums of the host-buffer variant
+
+static size_t hist_budget(const pai_ctx* c) {
+  if (const char* e = xcheck_env("FLEXPAI_HIST_SCRATCH_BYTES")) {   // test build: feature blocks at small shapes
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    if (v > 0) return (size_t)v;
+  }
+  return c->hist_scratch;
+}
+
+// The variant that sums the runs (test build: $FLEXPAI_HIST_ACC = 0 k_hist_rows + k_add over runs of HIST_RUN,
+// 1 k_hist_acc) and the run length of k_hist_acc ($FLEXPAI_HIST_RUN); same bits whichever is taken. The defaults are
+// the fastest of tools/hist_ab.py on N = 262 144, F = 16, B = 32 (profiles/hist_ab.json): k_hist_acc
+// over runs of 64 takes 3.8 ms at 1024 bits and 10.1 ms at 2048 where k_add over gather rows takes 4.2 and 10.3, runs of
+// 128 take 4.6 and 11.1 and runs of 256 take 5.5 and 14.1 (4 M members in runs of 256 are 16 384 lane groups, fewer than
+// the chip holds).
+constexpr bool HIST_ACC_DEFAULT = true;
+static bool hist_use_acc() {
+  if (const char* e = xcheck_env("FLEXPAI_HIST_ACC")) return atoi(e) != 0;
+  return HIST_ACC_DEFAULT;
+}
+static size_t hist_run_len(bool acc) {
+  if (acc)
+    if (const char* e = xcheck_env("FLEXPAI_HIST_RUN")) {
+      const unsigned long long v = strtoull(e, nullptr, 10);
+      if (v >= 1 && v <= 65536) return (size_t)v;
+    }
+  return HIST_RUN;
+}
+
+static int hist_check(const void* ct, const void* exp, size_t N, int bin_dtype, const void* bins, size_t F, size_t bin_stride,
+                      const int32_t* node, size_t nodes, size_t B, const void* ct_out, const void* exp_out, const char* who) {
+  const std::string w(who);
+  if ((N && (!ct || !exp || !bins)) || !ct_out || !exp_out) return fail(PAI_ERR_ARG, w + ": null pointer");
+  if (bin_dtype != PAI_BIN_U8 && bin_dtype != PAI_BIN_U16) return fail(PAI_ERR_ARG, w + ": bin_dtype must be PAI_BIN_U8 or PAI_BIN_U16");
+  if (F == 0 || bin_stride < F) return fail(PAI_ERR_ARG, w + ": bin_stride must be at least F >= 1");
+  if (B == 0 || B > (bin_dtype == PAI_BIN_U8 ? (size_t)256 : (size_t)65536)) return fail(PAI_ERR_ARG, w + ": B out of range for the bin type");
+  if (nodes == 0 || (!node && nodes != 1)) return fail(PAI_ERR_ARG, w + ": nodes must be >= 1, and 1 without node ids");
+  if (nodes > HIST_MAX_CELLS || F > HIST_MAX_CELLS || nodes * F > HIST_MAX_CELLS || nodes * F * B > HIST_MAX_CELLS)
+    return fail(PAI_ERR_ARG, w + ": more than 2^24 cells");
+  if (N >= ((size_t)1 << 31) || N * F >= ((size_t)1 << 31)) return fail(PAI_ERR_ARG, w + ": N F must be below 2^31");
+  if (N && (N - 1) > (SIZE_MAX / 2 - F) / bin_stride) return fail(PAI_ERR_ARG, w + ": bin matrix too large");
+  return 0;
+}
+
+int pai_histogram_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int bin_dtype, const void* d_bins,
+                      size_t F, size_t bin_stride, const int32_t* d_node, size_t nodes, size_t B, uint32_t* d_out,
+                      int32_t* d_exp_out, int64_t* d_count_out, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  int rc = hist_check(d_ct, d_exp, N, bin_dtype, d_bins, F, bin_stride, d_node, nodes, B, d_out, d_exp_out, "pai_histogram_dev");
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const bool acc = hist_use_acc();
+  const size_t W = c->ct_words, cells = nodes * F * B, R = hist_run_len(acc), row_bytes = acc ? 0 : R * 8;
+  auto& h = c->hist;
+  // counts of all cells
+  const size_t o_off = d_count_out ? 0 : align16(cells * 8), o_cur = align16(o_off + cells * 4), o_runs = align16(o_cur + cells * 4);
+  if ((rc = ensure_buf(&c->d_histmeta, &c->histmeta_bytes, o_runs))) return rc;
+  unsigned long long* d_cnt = d_count_out ? (unsigned long long*)d_count_out : (unsigned long long*)c->d_histmeta;
+  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "count_out");
+  HistParams hp{};
+  hp.bins = d_bins;
+  hp.bin_u16 = bin_dtype == PAI_BIN_U16 ? 1 : 0;
+  hp.stride = (long long)bin_stride;
+  hp.node = d_node;
+  hp.nodes = (int)nodes;
+  hp.B = (int)B;
+  hp.N = (long long)N;
+  hp.F = (long long)F;
+  hp.count = d_cnt;
+  HIPCHK(hipMemsetAsync(d_cnt, 0, cells * 8, st));
+  h.cnt.assign(cells, 0);
+  if (N) {
+    hp.f0 = 0;
+    hp.f1 = (long long)F;
+    HIPCHK(hist_count_launch(hp, c->cus, st));
+    HIPCHK(hipMemcpyAsync(h.cnt.data(), d_cnt, cells * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  // feature blocks: members (4 bytes each) and k_add's gather rows (8 R bytes per run) within the budget, one feature
+  // at least
+  struct Block {
+    size_t f0, f1, entries, runs, row0;
+  };
+  std::vector<Block> blocks;
+  const size_t budget = hist_budget(c);
+  size_t total_runs = 0;
+  {
+    Block b{0, 0, 0, 0, 0};
+    for (size_t f = 0; f < F; ++f) {
+      size_t ent = 0, runs = 0;
+      for (size_t v = 0; v < nodes; ++v)
+        for (size_t q = 0; q < B; ++q) {
+          const long long n = h.cnt[(v * F + f) * B + q];
+          if (n < 0 || (size_t)n > N) return fail(PAI_ERR_HIP, "pai_histogram_dev: cell count out of range");
+          ent += (size_t)n;
+          runs += ((size_t)n + R - 1) / R;
+        }
+      if (b.f1 > b.f0 && (b.entries + ent) * 4 + (b.runs + runs) * row_bytes > budget) {
+        blocks.push_back(b);
+        total_runs += b.runs;
+        b = Block{f, f, 0, 0, total_runs};
+      }
+      b.f1 = f + 1;
+      b.entries += ent;
+      b.runs += runs;
+    }
+    blocks.push_back(b);
+    total_runs += b.runs;
+  }
+  if (total_runs >= (size_t)INT32_MAX) return fail(PAI_ERR_ARG, "pai_histogram_dev: too many runs");
+  // member offsets (relative to the block's list) and runs in block order (v, f, b); the cells' partial rows
+  h.cell_off.assign(cells, 0);
+  h.runs.clear();
+  h.runs.reserve(total_runs);
+  std::vector<long long>& row0 = h.index;   // first: the first partial row of every cell
+  row0.assign(cells, 0);
+  size_t max_ent = 1, max_runs = 1;
+  for (const Block& b : blocks) {
+    size_t off = 0;
+    for (size_t v = 0; v < nodes; ++v)
+      for (size_t f = b.f0; f < b.f1; ++f)
+        for (size_t q = 0; q < B; ++q) {
+          const size_t cell = (v * F + f) * B + q, n = (size_t)h.cnt[cell];
+          h.cell_off[cell] = (int32_t)off;
+          row0[cell] = (long long)h.runs.size();
+          for (size_t t = 0; t < n; t += R) h.runs.push_back(make_int2((int)(off + t), (int)std::min(R, n - t)));
+          off += n;
+        }
+    max_ent = std::max(max_ent, b.entries);
+    max_runs = std::max(max_runs, b.runs);
+  }
+  h.segoff.assign(cells + 1, 0);
+  for (size_t cell = 0; cell < cells; ++cell) h.segoff[cell + 1] = h.segoff[cell] + (long long)(((size_t)h.cnt[cell] + R - 1) / R);
+  {
+    std::vector<long long> idx(total_runs);
+    for (size_t cell = 0; cell < cells; ++cell)
+      for (long long q = h.segoff[cell]; q < h.segoff[cell + 1]; ++q) idx[q] = row0[cell] + (q - h.segoff[cell]);
+    h.index.swap(idx);
+  }
+  if (total_runs) {
+    if ((rc = ensure_buf(&c->d_histmeta, &c->histmeta_bytes, o_runs + align16(total_runs * 8)))) return rc;
+    // (a grown buffer lost the counts it may have held: they are on the host)
+    if (!d_count_out) {
+      d_cnt = (unsigned long long*)c->d_histmeta;
+      HIPCHK(hipMemcpyAsync(d_cnt, h.cnt.data(), cells * 8, hipMemcpyHostToDevice, st));
+    }
+  }
+  char* mb = (char*)c->d_histmeta;
+  int32_t* d_off = (int32_t*)(mb + o_off);
+  unsigned* d_cur = (unsigned*)(mb + o_cur);
+  int2* d_runs = (int2*)(mb + o_runs);
+  const size_t o_g = align16(max_ent * 4);
+  if ((rc = ensure_buf(&c->d_histwork, &c->histwork_bytes, o_g + max_runs * row_bytes))) return rc;
+  int32_t* d_mem = (int32_t*)c->d_histwork;
+  long long* d_g = (long long*)((char*)c->d_histwork + o_g);
+  const size_t o_pexp = align16(std::max<size_t>(total_runs, 1) * W * 4);
+  if ((rc = ensure_buf(&c->d_histpart, &c->histpart_bytes, o_pexp + align16(std::max<size_t>(total_runs, 1) * 4)))) return rc;
+  uint32_t* part = (uint32_t*)c->d_histpart;
+  int32_t* pexp = (int32_t*)((char*)c->d_histpart + o_pexp);
+  if (total_runs) {
+    HIPCHK(hipMemcpyAsync(d_off, h.cell_off.data(), cells * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_cur, 0, cells * 4, st));
+    HIPCHK(hipMemcpyAsync(d_runs, h.runs.data(), total_runs * 8, hipMemcpyHostToDevice, st));
+    hp.count = d_cnt;
+    hp.cell_off = d_off;
+    hp.cursor = d_cur;
+    hp.members = d_mem;
+    for (const Block& b : blocks) {
+      if (!b.runs) continue;
+      HIPCHK(hipMemsetAsync(d_mem, 0, b.entries * 4, st));
+      hp.f0 = (long long)b.f0;
+      hp.f1 = (long long)b.f1;
+      HIPCHK(hist_scatter_launch(hp, c->cus, st));
+      if (acc) {
+        HistAccParams ap{};
+        ap.cts = d_ct;
+        ap.exps = d_exp;
+        ap.members = d_mem;
+        ap.runs = d_runs + b.row0;
+        ap.nruns = (long long)b.runs;
+        ap.out = part + b.row0 * W;
+        ap.out_exp = pexp + b.row0;
+        ap.N = c->d_N;
+        ap.RS = c->d_RS;
+        ap.mprime = c->mprime_N;
+        ap.ct_words = c->ct_words;
+        HIPCHK(hist_acc_launch(c->tpi_e, ap, c->cus, st));
+        continue;
+      }
+      HistRowsParams rp{};
+      rp.members = d_mem;
+      rp.runs = d_runs + b.row0;
+      rp.nruns = (long long)b.runs;
+      rp.gidx = d_g;
+      HIPCHK(hist_rows_launch(rp, c->cus, st));
+      if ((rc = run_add(c, add_params(d_ct, d_exp, HIST_RUN, (long long)b.runs, part + b.row0 * W, pexp + b.row0, d_g), st))) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+      }
+    }
+  }
+  // the partials of cell s are rows index[segoff[s] .. segoff[s + 1]); an empty cell has none (ciphertext 1, INT32_MIN)
+  return pai_segment_add_dev(c, part, pexp, total_runs, (const int64_t*)h.index.data(), (const int64_t*)h.segoff.data(), cells, d_out,
+                             d_exp_out, stream);
+}
+
+int pai_histogram(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, int bin_dtype, const void* bins, size_t F,
+                  size_t bin_stride, const int32_t* node, size_t nodes, size_t B, uint32_t* ct_out, int32_t* exp_out,
+                  int64_t* count_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  int rc = hist_check(ct, exp, N, bin_dtype, bins, F, bin_stride, node, nodes, B, ct_out, exp_out, "pai_histogram");
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t W = c->ct_words, cells = nodes * F * B, bsz = bin_dtype == PAI_BIN_U16 ? 2 : 1;
+  // chunks of samples; their cell sums [chunk][cells] are the operands of one k-way add (an empty cell: PAD_EXP)
+  size_t chunk = HIST_HOST_CHUNK;
+  if (const char* e = xcheck_env("FLEXPAI_HIST_CHUNK")) {           // test build: chunks at small shapes
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    if (v > 0) chunk = (size_t)v;
+  }
+  const size_t kmax = std::max<size_t>(HIST_HOST_PART_BYTES / (cells * W * 4), 1);
+  if ((N + chunk - 1) / chunk > kmax) chunk = (N + kmax - 1) / kmax;
+  const size_t k = std::max<size_t>((N + chunk - 1) / chunk, 1), nc = std::min(chunk, std::max<size_t>(N, 1));
+  DevScope ds;
+  uint32_t* dct = ds.alloc<uint32_t>(nc * W);
+  int32_t* dexp = ds.alloc<int32_t>(nc);
+  uint8_t* dbins = ds.alloc<uint8_t>(nc * bin_stride * bsz);
+  int32_t* dnode = node ? ds.alloc<int32_t>(nc) : nullptr;
+  uint32_t* dpart = ds.alloc<uint32_t>(k * cells * W);
+  int32_t* dpexp = ds.alloc<int32_t>(k * cells);
+  int64_t* dcnt = ds.alloc<int64_t>(cells);
+  uint32_t* dout = k > 1 ? ds.alloc<uint32_t>(cells * W) : dpart;
+  int32_t* dexo = k > 1 ? ds.alloc<int32_t>(cells) : dpexp;
+  if (!dct || !dexp || !dbins || (node && !dnode) || !dpart || !dpexp || !dcnt || !dout || !dexo)
+    return fail(PAI_ERR_HIP, "pai_histogram: device allocation failed");
+  std::vector<int64_t> cnt(cells);
+  if (count_out) std::fill(count_out, count_out + cells, (int64_t)0);
+  for (size_t q = 0; q < k; ++q) {
+    const size_t i0 = q * chunk, n = N ? std::min(chunk, N - i0) : 0;
+    if (n) {
+      HIPCHK(hipMemcpy(dct, ct + i0 * W, n * W * 4, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(dexp, exp + i0, n * 4, hipMemcpyHostToDevice));
+      // (the last row of a strided matrix ends after its F elements)
+      HIPCHK(hipMemcpy(dbins, (const char*)bins + i0 * bin_stride * bsz, ((n - 1) * bin_stride + F) * bsz, hipMemcpyHostToDevice));
+      if (node) HIPCHK(hipMemcpy(dnode, node + i0, n * 4, hipMemcpyHostToDevice));
+    }
+    rc = pai_histogram_dev(c, dct, dexp, n, bin_dtype, dbins, F, bin_stride, dnode, nodes, B, dpart + q * cells * W, dpexp + q * cells,
+                           dcnt, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    if (count_out) {
+      HIPCHK(hipMemcpy(cnt.data(), dcnt, cells * 8, hipMemcpyDeviceToHost));
+      for (size_t s = 0; s < cells; ++s) count_out[s] += cnt[s];
+    }
+  }
+  if (k > 1) {
+    if ((rc = add_dev(c, dpart, dpexp, (int)k, (long long)cells, dout, dexo, nullptr))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+  }
+  HIPCHK(hipMemcpy(ct_out, dout, cells * W * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(exp_out, dexo, cells * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -35,6 +35,8 @@ PAI_OPT_MATMUL_FUSED, PAI_OPT_MATMUL_PATH = 16, 17
 PAI_OPT_OBF_CHUNK = 18
 PAI_OPT_SEGDOT_FUSED, PAI_OPT_SEGDOT_PATH = 20, 21     # 19 is not assigned
 PAI_OPT_POOL_FUSED = 22
+PAI_BIN_U8, PAI_BIN_U16 = 0, 1
+HIST_RUN = 64          # PAI_HIST_RUN: members of a histogram cell that one k_hist_acc instance sums
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
 PFB_NBASES = 33
 
@@ -51,7 +53,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_obfuscate", "pai_obfuscate_dev",
             "pai_pack_max_slots", "pai_encrypt_packed", "pai_encrypt_packed_dev", "pai_decrypt_packed",
             "pai_decrypt_packed_dev", "pai_pack_ciphertexts", "pai_pack_ciphertexts_dev",
-            "pai_segment_dot", "pai_segment_dot_dev",
+            "pai_segment_dot", "pai_segment_dot_dev", "pai_histogram", "pai_histogram_dev",
             "pai_pool_reserve", "pai_pool_fill", "pai_pool_fill_dev", "pai_pool_put", "pai_pool_put_dev", "pai_pool_info")
 PAI_COMM_ID_BYTES = 128
 
@@ -127,6 +129,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_segment_add_dev.argtypes = [P, P, P, S, P, P, S, P, P, P]
         lib.pai_segment_dot.argtypes = [P, P, P, S, P, P, S, I, P, P, P, P]
         lib.pai_segment_dot_dev.argtypes = [P, P, P, S, P, P, S, I, P, P, P, P, P]
+        lib.pai_histogram.argtypes = [P, P, P, S, I, P, S, S, P, S, S, P, P, P]
+        lib.pai_histogram_dev.argtypes = [P, P, P, S, I, P, S, S, P, S, S, P, P, P, P]
         lib.pai_matmul.argtypes = [P, P, P, S, S, I, P, S, P, P]
         lib.pai_matmul_dev.argtypes = [P, P, P, S, S, I, P, S, P, P, P]
         lib.pai_comm_unique_id.argtypes = [P]
@@ -814,6 +818,38 @@ class Context:
         self._chk(self.lib.pai_segment_add(self._h, _ptr(ct), _ptr(exp), exp.size, _ptr(index), _ptr(seg_off), nseg,
                                         _ptr(out), _ptr(oe)))
         return out, oe
+
+    def histogram(self, ct: np.ndarray, exp: np.ndarray, bins: np.ndarray, n_bins: int, node=None, n_nodes: int = 1):
+        """Per-cell sums of the N ciphertexts over bins [N, F] (uint8 / uint16, rows may be strided) and an optional
+        int32 node id per sample (pai_histogram, one call, no index list). Returns (words [n_nodes F n_bins, W],
+        exponents, counts int64), cell (v, f, b) at (v F + f) n_bins + b; an empty cell gives ciphertext 1 and exponent
+        INT32_MIN. The arguments are the checked ones of cipher_buffer.histogram_args."""
+        ct = np.ascontiguousarray(ct, dtype=np.uint32)
+        exp = np.ascontiguousarray(exp, dtype=np.int32)
+        N = exp.size
+        self._check_words(ct, exp, N)
+        if bins.ndim != 2 or bins.shape[0] != N or bins.dtype not in (np.uint8, np.uint16):
+            raise ValueError("histogram: bins must be a uint8 / uint16 matrix with one row per ciphertext")
+        isz = bins.dtype.itemsize
+        F = bins.shape[1]
+        if N > 1 and F > 0 and (bins.strides[1] != isz or bins.strides[0] % isz or bins.strides[0] < F * isz):
+            raise ValueError("histogram: bins must be C-contiguous or row-strided")
+        stride = bins.strides[0] // isz if N > 1 and F > 0 else max(F, 1)
+        if bins.size and N <= 1:
+            bins = np.ascontiguousarray(bins)
+        if node is not None:
+            node = np.ascontiguousarray(node, dtype=np.int32)
+            if node.shape != (N,):
+                raise ValueError("histogram: one node id per ciphertext")
+        cells = int(n_nodes) * F * int(n_bins)
+        self.calls["pai_histogram"] += 1
+        out = np.empty((max(cells, 0), self.ct_words), dtype=np.uint32)
+        oe = np.empty(max(cells, 0), dtype=np.int32)
+        cnt = np.empty(max(cells, 0), dtype=np.int64)
+        self._chk(self.lib.pai_histogram(self._h, _ptr(ct), _ptr(exp), N, PAI_BIN_U16 if isz == 2 else PAI_BIN_U8,
+                                      _ptr(bins), F, stride, _ptr(node) if node is not None else None, int(n_nodes),
+                                      int(n_bins), _ptr(out), _ptr(oe), _ptr(cnt)))
+        return out, oe, cnt
 
     def segment_dot(self, ct: np.ndarray, exp: np.ndarray, index: np.ndarray, seg_off: np.ndarray, x: np.ndarray):
         """Per-segment weighted sums: segment s = sum over t in [seg_off[s], seg_off[s+1]) of ct[index[t]] (x) x[t]

@@ -217,6 +217,18 @@ class CiphertextBuffer(object):
 
     __matmul__ = dot
 
+    def histogram(self, bins, n_bins: int, node=None, n_nodes: int = 1):
+        """Per-cell sums of these N ciphertexts (flat order) over the bin ids bins [N, F] (uint8 / uint16) and an optional
+        node id per sample: (CiphertextBuffer of shape (n_nodes, F, n_bins), int64 counts of that shape), cell
+        [v, f, b] = the sum of the samples with node == v and bins[:, f] == b, in ONE pai_histogram call with no index
+        list. A node id outside [0, n_nodes) and a bin id >= n_bins put the sample in no cell (of that feature). Each
+        sum is the reference's __add__ chain over the members; an empty cell is ciphertext 1 at exponent 0, an
+        unobfuscated encryption of 0. Without a GPU the same runs on Python integers."""
+        b, nd, shape = histogram_args(self.size, bins, n_bins, node, n_nodes)
+        out, oe, cnt = histogram_words(self.public_key, self.words, self.exps, b, int(n_bins), nd, int(n_nodes))
+        oe = np.where(cnt == 0, 0, oe).astype(np.int32)
+        return self._like(out, oe, 0, shape), cnt.reshape(shape)
+
     def pack(self, layout, max_abs):
         """Fold these ciphertexts into a PackedCiphertextBuffer (packed_buffer.pack_ciphertexts)."""
         from .packed_buffer import pack_ciphertexts
@@ -320,6 +332,76 @@ def segment_dot_words(pk, words, exps, idx, off, w):
         vals.append(1 if acc is None else acc.ciphertext(False))
         oe.append(0 if acc is None else acc.exponent)
     return _runtime.ints_to_words(vals, W).reshape(nseg, W), np.array(oe, dtype=np.int32)
+
+
+EMPTY_EXP = -(1 << 31)      # the exponent of an empty cell or segment (ciphertext 1)
+
+
+def histogram_args(N: int, bins, n_bins, node, n_nodes):
+    """Checked (bins uint8 / uint16 [N, F] with contiguous rows, node int32 [N] or None, (n_nodes, F, n_bins))."""
+    if not isinstance(bins, np.ndarray) or bins.dtype not in (np.uint8, np.uint16):
+        raise TypeError("histogram: bins must be a numpy array of uint8 or uint16")
+    if bins.ndim != 2 or bins.shape[0] != N or bins.shape[1] == 0:
+        raise ValueError(f"histogram: bins must have shape ({N}, F) with F >= 1, not {bins.shape}")
+    isz = bins.dtype.itemsize
+    F = bins.shape[1]
+    if N > 1 and (bins.strides[1] != isz or bins.strides[0] % isz or bins.strides[0] < F * isz):
+        raise ValueError("histogram: bins must be C-contiguous or row-strided (contiguous rows)")
+    if isinstance(n_bins, (bool, np.bool_)) or not isinstance(n_bins, (int, np.integer)):
+        raise TypeError("histogram: n_bins must be an integer")
+    if not 1 <= int(n_bins) <= (256 if isz == 1 else 65536):
+        raise ValueError(f"histogram: n_bins must be in 1 .. {256 if isz == 1 else 65536} for {bins.dtype} bins")
+    if isinstance(n_nodes, (bool, np.bool_)) or not isinstance(n_nodes, (int, np.integer)):
+        raise TypeError("histogram: n_nodes must be an integer")
+    if int(n_nodes) < 1:
+        raise ValueError("histogram: n_nodes must be at least 1")
+    if node is None:
+        if int(n_nodes) != 1:
+            raise ValueError("histogram: n_nodes must be 1 without node ids")
+    else:
+        node = np.asarray(node)
+        if node.dtype.kind not in "iu":
+            raise TypeError("histogram: node must hold integers")
+        if node.shape != (N,):
+            raise ValueError(f"histogram: node must have shape ({N},), not {node.shape}")
+        node = np.clip(node, -1, int(n_nodes)).astype(np.int32)       # out of range stays out of range
+    if int(n_nodes) * F * int(n_bins) > 1 << 24:
+        raise ValueError("histogram: more than 2^24 cells")
+    if N * F >= 1 << 31:
+        raise ValueError("histogram: bins must hold fewer than 2^31 entries")
+    return bins, node, (int(n_nodes), F, int(n_bins))
+
+
+def histogram_cells(bins, n_bins: int, node, n_nodes: int):
+    """Host side of the cell rule: the flat cell (v F + f) n_bins + b of every (sample, feature) pair, -1 where the
+    sample is in no cell of that feature; shape [N, F]."""
+    N, F = bins.shape
+    b = bins.astype(np.int64)
+    v = np.zeros(N, dtype=np.int64) if node is None else node.astype(np.int64)
+    ok = (b < n_bins) & ((v >= 0) & (v < n_nodes))[:, None]
+    cell = (v[:, None] * F + np.arange(F, dtype=np.int64)[None, :]) * n_bins + b
+    return np.where(ok, cell, -1)
+
+
+def histogram_words(pk, words, exps, bins, n_bins: int, node, n_nodes: int):
+    """(words [cells, W], exponents [cells], counts int64 [cells]) of the histogram over checked arguments: pai_histogram
+    on the GPU, products of Python integers without one. Empty cells: ciphertext 1, exponent EMPTY_EXP."""
+    from . import _runtime
+    if _runtime.gpu_available():
+        return _runtime.context(pk).histogram(words, exps, bins, n_bins, node, n_nodes)
+    W = words.shape[1]
+    cells = n_nodes * bins.shape[1] * n_bins
+    cell = histogram_cells(bins, n_bins, node, n_nodes)
+    cts, nsq = _ints(words), pk.nsquare
+    E = np.full(cells, EMPTY_EXP, dtype=np.int64)
+    ii, ff = np.nonzero(cell >= 0)
+    np.maximum.at(E, cell[ii, ff], np.asarray(exps, dtype=np.int64)[ii])
+    cnt = np.bincount(cell[ii, ff], minlength=cells).astype(np.int64)
+    acc = [1] * cells
+    for i, f in zip(ii.tolist(), ff.tolist()):
+        s = int(cell[i, f])
+        acc[s] = acc[s] * pow(cts[i], 16 ** (int(E[s]) - int(exps[i])), nsq) % nsq
+    return _runtime.ints_to_words(acc, W).reshape(cells, W), E.astype(np.int32), cnt
 
 
 def _plain(y, N: int) -> np.ndarray:

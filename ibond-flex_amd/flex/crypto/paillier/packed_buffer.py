@@ -243,6 +243,27 @@ class PackedCiphertextBuffer(object):
 
     __rmul__ = __mul__
 
+    def histogram(self, bins, n_bins: int, node=None, n_nodes: int = 1):
+        """Histogram of samples encrypted as packed ciphertexts, ONE ciphertext per sample (count == samples * slots:
+        g and h of a sample in two slots): (PackedCiphertextBuffer of shape (n_nodes, F, n_bins, slots) with this layout,
+        int64 counts of shape (n_nodes, F, n_bins)) from one pai_histogram call, every slot summed per cell at once. The
+        bound is this buffer's bound * counts.max(); the counts are taken on the host first, so that OverflowError is
+        raised before any GPU call if it passes the slot. Empty cells decode as 0 in every slot."""
+        from .cipher_buffer import histogram_args, histogram_cells, histogram_words
+        k, N = self.layout.slots, self.words.shape[0]
+        if self.count != N * k:
+            raise ValueError(f"histogram: {self.count} values do not fill {N} ciphertexts of {k} slots (one ciphertext "
+                             "per sample)")
+        b, nd, shape = histogram_args(N, bins, n_bins, node, n_nodes)
+        cells = shape[0] * shape[1] * shape[2]
+        cell = histogram_cells(b, shape[2], nd, shape[0])
+        cnt = np.bincount(cell[cell >= 0], minlength=cells).astype(np.int64)
+        bound = self.bound * (int(cnt.max()) if cnt.size else 0)
+        self._check_bound(bound)
+        out, _, _ = histogram_words(self.public_key, self.words, self._exps(), b, shape[2], nd, shape[0])
+        return (PackedCiphertextBuffer(self.public_key, out, self.layout, cells * k, shape + (k,), False, bound),
+                cnt.reshape(shape))
+
     def apply_obfuscation(self) -> "PackedCiphertextBuffer":
         """Re-randomise every ciphertext in ONE pai_obfuscate call, unless the flag is already set. Returns self."""
         if self.obfuscated or self.words.shape[0] == 0:

@@ -351,6 +351,31 @@ int pai_segment_add(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t
 int pai_segment_dot(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, const int64_t* index,
                     const int64_t* seg_off, size_t nseg, int dtype, const void* x, uint32_t* ct_out, int32_t* exp_out,
                     int32_t* status_out);
+/* Encrypted histogram: the per-cell sums of N ciphertexts over an [N][F] matrix of bin ids (row-major, bin_stride >= F
+ * elements per row, PAI_BIN_U8 or PAI_BIN_U16) and an optional node id per sample (node nullable: every sample in node
+ * 0, nodes must be 1). Cell (v, f, b) has index (v F + f) B + b and sums the samples i with node[i] == v and
+ * bins[i][f] == b; no index list exists on the host (per-bin sums of all features of IV_FFS at once, and the
+ * (node, feature, bin) sums of encrypted g and h in gradient boosting).
+ *   A sample with node[i] < 0 or node[i] >= nodes is in no cell, and a bin id >= B is in no cell of that feature (a
+ *   "missing" value); neither is an error. ct_out / exp_out of a cell equal pai_segment_add over the cell's members bit
+ *   for bit (prod c_i^(16^(E - e_i)) mod n^2, canonical, E the cell's largest exponent), whatever the order of the
+ *   members, the runs, the feature blocks or the host variant's chunks. An empty cell yields ciphertext 1 with exponent
+ *   INT32_MIN. count_out (nullable, nodes F B entries) holds the members per cell. The output is not re-randomised; the
+ *   call needs the public key only.
+ *   PAI_ERR_ARG before any launch: a null pointer, bin_stride < F, F = 0, B = 0 or B above 256 (u8) / 65536 (u16),
+ *   nodes = 0, nodes F B above 2^24 cells, N F at or above 2^31.
+ * Members of a cell are summed in runs of PAI_HIST_RUN by k_hist_acc, which reads the member lists built on the device,
+ * and the runs' partials by the segmented add. The features are processed in blocks whose member lists fit a scratch
+ * budget of the context (256 MiB). The host-buffer variant moves the samples in chunks of 65536 and combines the chunks'
+ * cell sums with one k-way add.
+ * The _dev variant (device pointers for ct, exp, bins, node and all outputs) takes the context lock and chains on the
+ * previous call's event like every _dev call; it synchronises `stream` once to read the cell counts and then as often
+ * as the closing pai_segment_add_dev over the partials (once per reduction level). */
+enum { PAI_BIN_U8 = 0, PAI_BIN_U16 = 1 };
+#define PAI_HIST_RUN 64
+int pai_histogram(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int bin_dtype, const void* bins,
+                  size_t F, size_t bin_stride, const int32_t* node, size_t nodes, size_t B, uint32_t* ct_out,
+                  int32_t* exp_out, int64_t* count_out);
 /* Encrypted (m x K, row-major ciphertexts + exponents) times plain (K x d, row-major, dtype as above):
  * out[i][j] = sum_k ct[i][k] (x) x[k][j] with the reference's exponent alignment (bit-identical to
  * numpy's object dot over PaillierEncryptedNumber, whose sums are order independent). By default a product of
@@ -395,6 +420,9 @@ int pai_matmul_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, siz
 int pai_segment_dot_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* index,
                         const int64_t* seg_off, size_t nseg, int dtype, const void* d_x, uint32_t* d_out,
                         int32_t* d_exp_out, int32_t* d_status, void* stream);
+int pai_histogram_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int bin_dtype,
+                      const void* d_bins, size_t F, size_t bin_stride, const int32_t* d_node, size_t nodes, size_t B,
+                      uint32_t* d_out, int32_t* d_exp_out, int64_t* d_count_out, void* stream);
 
 /* Packed plaintexts: many signed fixed-point values per ciphertext (no reference counterpart; opt-in, both peers must
  * be flexpai; csrc/kernels_pack.hpp). Every packed ciphertext is an ordinary reference ciphertext
