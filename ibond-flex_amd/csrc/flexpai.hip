@@ -55,6 +55,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_mm.hpp"
 #include "engine_sd.hpp"
 #include "engine_hist.hpp"
+#include "engine_scan.hpp"
 #include "engine_obf.hpp"
 #include "engine_pack.hpp"
 #include "engine_pool.hpp"
@@ -320,6 +321,11 @@ struct pai_ctx {
     std::vector<int32_t> cell_off;
     std::vector<int2> runs;
   } hist;
+  // prefix sums (kernels_scan.hpp): PAI_OPT_SCAN_TILE / PAI_OPT_SCAN_PATH
+  int scan_tile = 0;            // 0: automatic tile length of the blocked path
+  int scan_path = 0;            // last pai_cumsum[_dev] call: 0 none yet, 1 row chains, 2 blocked
+  void* d_scan = nullptr;       // the blocked path's tile totals and their scans, all levels
+  size_t scan_bytes = 0;
   void* d_inv = nullptr;        // batch-inversion prefix products and segment products
   size_t inv_bytes = 0;
   std::vector<uint32_t> inv_host;   // top of the inversion tree (host side of an async copy)
@@ -418,6 +424,7 @@ pai_ctx::~pai_ctx() {
   if (d_histmeta) (void)hipFree(d_histmeta);
   if (d_histwork) (void)hipFree(d_histwork);
   if (d_histpart) (void)hipFree(d_histpart);
+  if (d_scan) (void)hipFree(d_scan);
   if (d_inv) (void)hipFree(d_inv);
   if (inv_async) {
     if (inv_async->pin) (void)hipHostFree(inv_async->pin);
@@ -2255,6 +2262,10 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
     case PAI_OPT_MATMUL_FUSED: c->mm_fused = value != 0; return 0;
     case PAI_OPT_SEGDOT_FUSED: c->sd_fused = value != 0; return 0;
     case PAI_OPT_POOL_FUSED: c->pool.fused = value != 0; return 0;
+    case PAI_OPT_SCAN_TILE:
+      if (value < 0) return fail(PAI_ERR_ARG, "PAI_OPT_SCAN_TILE must be >= 0");
+      c->scan_tile = value;
+      return 0;
     case PAI_OPT_OBF_CHUNK:
       if (value < 64) return fail(PAI_ERR_ARG, "PAI_OPT_OBF_CHUNK must be >= 64");
       c->obf_chunk = value;
@@ -2296,6 +2307,8 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_SEGDOT_FUSED: *value = c->sd_fused ? 1 : 0; return 0;
     case PAI_OPT_SEGDOT_PATH: *value = c->sd_path; return 0;
     case PAI_OPT_POOL_FUSED: *value = c->pool.fused ? 1 : 0; return 0;
+    case PAI_OPT_SCAN_TILE: *value = c->scan_tile; return 0;
+    case PAI_OPT_SCAN_PATH: *value = c->scan_path; return 0;
     case PAI_OPT_OBF_CHUNK: *value = c->obf_chunk; return 0;
     case PAI_OPT_STAGE_TIMING: *value = c->timing ? 1 : 0; return 0;
     case PAI_OPT_LANE_DECRYPT: *value = (c->dec_lane_ok && c->dec_lane_enabled) ? 1 : 0; return 0;
@@ -5324,6 +5337,158 @@ int pai_histogram(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, 
   }
   HIPCHK(hipMemcpy(ct_out, dout, cells * W * 4, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(exp_out, dexo, cells * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ------------------------------------------------------------------ prefix sums (kernels_scan.hpp)
+// Row chains: one k_scan lane group per (o, i) row. Blocked: the rows are cut into tiles of T; k_scan writes the tiles'
+// totals, the totals [outer][tiles][inner] are scanned by the same routine (recursively), and k_scan runs per tile from
+// the scanned total of the tiles before it. The automatic T gives the chip's resident lane groups (scan_slots) one
+// tile each, but no tile shorter than SCAN_TILE_FLOOR: a tile costs its total (one product per element, against two
+// for the chain) and a carry product, and short tiles deepen the recursion.
+// SCAN_TILE_FLOOR = 8, from the forced tiles of tools/cumsum_ab.py (profiles/cumsum_ab.json), at
+// 1024 / 2048 bits: one vector of 2^18 elements takes 2.90 / 5.50 ms in tiles of 4, 3.31 / 5.77 in tiles of 8, 4.64 / 7.33
+// in tiles of 16, 6.86 / 10.72 in tiles of 32 and 11.20 / 17.54 in tiles of 64; 8192 rows of 32 take 1.00 / 2.47 ms in
+// tiles of 4, 0.86 / 1.92 in tiles of 8, 1.30 / 2.05 in tiles of 16 and 1.36 / 2.16 as row chains; 1024 rows of 256 take
+// 1.39 / 3.25, 1.44 / 2.90 and 1.88 / 3.04 ms in tiles of 4, 8 and 16. Tiles of 4 win by 4 to 12 % on the vector and on 1024 x 256 at
+// 1024 bits and lose by 12 to 29 % on the rows of 32 at both sizes and on 1024 x 256 at 2048 bits.
+constexpr long long SCAN_TILE_FLOOR = 8;
+
+static long long scan_tile_for(const pai_ctx* c, long long rows, long long L, long long slots) {
+  if (c->scan_tile > 0) return std::min<long long>(c->scan_tile, L);
+  const long long want = (slots + rows - 1) / rows;          // tiles per row that fill the chip once
+  if (want <= 1) return L;
+  return std::min(L, std::max(SCAN_TILE_FLOOR, (L + want - 1) / want));
+}
+
+// bytes of d_scan that a scan of [outer][L][inner] needs below itself: per level the tiles' totals and their scan
+static size_t scan_scratch(const pai_ctx* c, long long outer, long long L, long long inner, long long slots) {
+  size_t total = 0;
+  for (;;) {
+    const long long T = scan_tile_for(c, outer * inner, L, slots);
+    if (T >= L || T < 2) return total;
+    const long long tiles = (L + T - 1) / T;
+    const size_t n = (size_t)(outer * tiles * inner);
+    total += 2 * (align16(n * c->ct_words * 4) + align16(n * 4));
+    L = tiles;
+  }
+}
+
+static int scan_level(pai_ctx* c, const uint32_t* ct, const int32_t* exp, long long outer, long long L, long long inner, int reverse,
+                      uint32_t* out, int32_t* exp_out, char* scratch, long long slots, int depth, hipStream_t st) {
+  ScanParams p{};
+  p.ct = ct;
+  p.exp = exp;
+  p.outer = outer;
+  p.L = L;
+  p.inner = inner;
+  p.reverse = reverse;
+  p.N = c->d_N;
+  p.R2 = c->d_R2;
+  p.oneR = c->d_oneR;
+  p.RS = c->d_RS;
+  p.mprime = c->mprime_N;
+  p.ct_words = c->ct_words;
+  long long T = scan_tile_for(c, outer * inner, L, slots);
+  if (T < 2) T = L;                                          // tiles of one element would never shorten the totals
+  if (T >= L) {
+    p.T = L;
+    p.tiles = 1;
+    p.emit_all = 1;
+    p.out = out;
+    p.out_exp = exp_out;
+    if (depth == 0) c->scan_path = 1;
+    HIPCHK(scan_launch(c->tpi_e, p, c->cus, st));
+    return 0;
+  }
+  if (depth == 0) c->scan_path = 2;
+  const long long tiles = (L + T - 1) / T;
+  const size_t n = (size_t)(outer * tiles * inner), wb = align16(n * c->ct_words * 4), eb = align16(n * 4);
+  uint32_t* tot = (uint32_t*)scratch;
+  int32_t* tot_e = (int32_t*)(scratch + wb);
+  uint32_t* car = (uint32_t*)(scratch + wb + eb);
+  int32_t* car_e = (int32_t*)(scratch + 2 * wb + eb);
+  p.T = T;
+  p.tiles = tiles;
+  p.emit_all = 0;
+  p.out = tot;
+  p.out_exp = tot_e;
+  HIPCHK(scan_launch(c->tpi_e, p, c->cus, st));
+  int rc = scan_level(c, tot, tot_e, outer, tiles, inner, reverse, car, car_e, scratch + 2 * (wb + eb), slots, depth + 1, st);
+  if (rc) return rc;
+  p.emit_all = 1;
+  p.carry = car;
+  p.carry_exp = car_e;
+  p.out = out;
+  p.out_exp = exp_out;
+  HIPCHK(scan_launch(c->tpi_e, p, c->cus, st));
+  return 0;
+}
+
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+
+// 1: nothing to do, 0: go on, < 0: error
+static int scan_check(const pai_ctx* c, const void* ct, const void* exp, size_t outer, size_t L, size_t inner, int flags,
+                      const void* ct_out, const void* exp_out, const char* who) {
+  const std::string w(who);
+  if (flags & ~PAI_SCAN_REVERSE) return fail(PAI_ERR_ARG, w + ": unknown flag bits");
+  if (outer == 0 || L == 0 || inner == 0) return 1;
+  if (!ct || !exp || !ct_out || !exp_out) return fail(PAI_ERR_ARG, w + ": null pointer");
+  const size_t lim = (size_t)1 << 31;
+  if (outer >= lim || L >= lim || inner >= lim || outer * L >= lim || outer * L * inner >= lim)
+    return fail(PAI_ERR_ARG, w + ": outer L inner must be below 2^31");
+  const size_t n = outer * L * inner, cb = n * c->ct_words * 4, eb = n * 4;
+  if (ranges_overlap(ct, cb, ct_out, cb) || ranges_overlap(exp, eb, exp_out, eb) || ranges_overlap(ct, cb, exp_out, eb) ||
+      ranges_overlap(exp, eb, ct_out, cb))
+    return fail(PAI_ERR_ARG, w + ": the output overlaps the input");
+  return 0;
+}
+
+int pai_cumsum_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t outer, size_t L, size_t inner, int flags,
+                   uint32_t* d_out, int32_t* d_exp_out, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  int rc = scan_check(c, d_ct, d_exp, outer, L, inner, flags, d_out, d_exp_out, "pai_cumsum_dev");
+  if (rc) return rc < 0 ? rc : 0;
+  HIPCHK(hipSetDevice(c->device));
+  const long long slots = scan_slots(c->tpi_e, c->cus);
+  if (slots <= 0) return fail(PAI_ERR_KEY, "unsupported group size");
+  if ((rc = ensure_buf(&c->d_scan, &c->scan_bytes, scan_scratch(c, (long long)outer, (long long)L, (long long)inner, slots)))) return rc;
+  return scan_level(c, d_ct, d_exp, (long long)outer, (long long)L, (long long)inner, (flags & PAI_SCAN_REVERSE) ? 1 : 0, d_out,
+                    d_exp_out, (char*)c->d_scan, slots, 0, (hipStream_t)stream);
+}
+
+// Slices of whole `outer` indices of at most SCAN_HOST_BYTES of ciphertext each (one index at least): every (o, i) row
+// lies in one slice, so the slices change no bits.
+constexpr size_t SCAN_HOST_BYTES = (size_t)1 << 30;
+
+int pai_cumsum(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t outer, size_t L, size_t inner, int flags,
+               uint32_t* ct_out, int32_t* exp_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  int rc = scan_check(c, ct, exp, outer, L, inner, flags, ct_out, exp_out, "pai_cumsum");
+  if (rc) return rc < 0 ? rc : 0;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t W = c->ct_words, row = L * inner;
+  const size_t per = std::min(outer, std::max<size_t>(SCAN_HOST_BYTES / (row * W * 4), 1));
+  DevScope ds;
+  uint32_t* din = ds.alloc<uint32_t>(per * row * W);
+  int32_t* dein = ds.alloc<int32_t>(per * row);
+  uint32_t* dout = ds.alloc<uint32_t>(per * row * W);
+  int32_t* deout = ds.alloc<int32_t>(per * row);
+  if (!din || !dein || !dout || !deout) return fail(PAI_ERR_HIP, "pai_cumsum: device allocation failed");
+  for (size_t o0 = 0; o0 < outer; o0 += per) {
+    const size_t no = std::min(per, outer - o0), n = no * row;
+    HIPCHK(hipMemcpy(din, ct + o0 * row * W, n * W * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dein, exp + o0 * row, n * 4, hipMemcpyHostToDevice));
+    if ((rc = pai_cumsum_dev(c, din, dein, no, L, inner, flags, dout, deout, nullptr))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(ct_out + o0 * row * W, dout, n * W * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(exp_out + o0 * row, deout, n * 4, hipMemcpyDeviceToHost));
+  }
   return 0;
 }
 

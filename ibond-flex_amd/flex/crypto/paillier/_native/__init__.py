@@ -36,6 +36,8 @@ PAI_OPT_OBF_CHUNK = 18
 PAI_OPT_SEGDOT_FUSED, PAI_OPT_SEGDOT_PATH = 20, 21     # 19 is not assigned
 PAI_OPT_POOL_FUSED = 22
 PAI_BIN_U8, PAI_BIN_U16 = 0, 1
+PAI_OPT_SCAN_TILE, PAI_OPT_SCAN_PATH = 23, 24
+PAI_SCAN_REVERSE = 1
 HIST_RUN = 64          # PAI_HIST_RUN: members of a histogram cell that one k_hist_acc instance sums
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
 PFB_NBASES = 33
@@ -54,6 +56,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_pack_max_slots", "pai_encrypt_packed", "pai_encrypt_packed_dev", "pai_decrypt_packed",
             "pai_decrypt_packed_dev", "pai_pack_ciphertexts", "pai_pack_ciphertexts_dev",
             "pai_segment_dot", "pai_segment_dot_dev", "pai_histogram", "pai_histogram_dev",
+            "pai_cumsum", "pai_cumsum_dev",
             "pai_pool_reserve", "pai_pool_fill", "pai_pool_fill_dev", "pai_pool_put", "pai_pool_put_dev", "pai_pool_info")
 PAI_COMM_ID_BYTES = 128
 
@@ -131,6 +134,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_segment_dot_dev.argtypes = [P, P, P, S, P, P, S, I, P, P, P, P, P]
         lib.pai_histogram.argtypes = [P, P, P, S, I, P, S, S, P, S, S, P, P, P]
         lib.pai_histogram_dev.argtypes = [P, P, P, S, I, P, S, S, P, S, S, P, P, P, P]
+        lib.pai_cumsum.argtypes = [P, P, P, S, S, S, I, P, P]
+        lib.pai_cumsum_dev.argtypes = [P, P, P, S, S, S, I, P, P, P]
         lib.pai_matmul.argtypes = [P, P, P, S, S, I, P, S, P, P]
         lib.pai_matmul_dev.argtypes = [P, P, P, S, S, I, P, S, P, P, P]
         lib.pai_comm_unique_id.argtypes = [P]
@@ -419,6 +424,20 @@ class Context:
     def segdot_path(self) -> int:
         """The path of this context's last segment_dot call: 0 = none yet, 1 = term path, 2 = fused."""
         return int(self._get_option(PAI_OPT_SEGDOT_PATH))
+
+    @property
+    def scan_tile(self) -> int:
+        """Tile length of cumsum's blocked path; 0 = automatic."""
+        return int(self._get_option(PAI_OPT_SCAN_TILE))
+
+    def set_scan_tile(self, n: int):
+        """0: automatic; n > 0: tiles of n elements at every level of the scan. Same bits for every value."""
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_SCAN_TILE, int(n)))
+
+    @property
+    def scan_path(self) -> int:
+        """The path of this context's last cumsum call: 0 = none yet, 1 = row chains, 2 = blocked scan."""
+        return int(self._get_option(PAI_OPT_SCAN_PATH))
 
     @property
     def obf_chunk(self) -> int:
@@ -850,6 +869,24 @@ class Context:
                                       _ptr(bins), F, stride, _ptr(node) if node is not None else None, int(n_nodes),
                                       int(n_bins), _ptr(out), _ptr(oe), _ptr(cnt)))
         return out, oe, cnt
+
+    def cumsum(self, ct: np.ndarray, exp: np.ndarray, outer: int, L: int, inner: int, reverse: bool = False):
+        """Prefix sums along the middle axis of the C-contiguous [outer, L, inner] array of ciphertexts (pai_cumsum;
+        reverse: suffix sums). Returns (words [outer L inner, W], exponents); entries with exponent INT32_MIN are
+        skipped, and a prefix of such entries only is ciphertext 1 with exponent INT32_MIN."""
+        ct = np.ascontiguousarray(ct, dtype=np.uint32)
+        exp = np.ascontiguousarray(exp, dtype=np.int32)
+        outer, L, inner = int(outer), int(L), int(inner)
+        if min(outer, L, inner) < 0 or outer * L * inner != exp.size:
+            raise ValueError("cumsum: outer * L * inner must be the number of ciphertexts")
+        N = exp.size
+        self._check_words(ct, exp, N)
+        self.calls["pai_cumsum"] += 1
+        out = np.empty((N, self.ct_words), dtype=np.uint32)
+        oe = np.empty(N, dtype=np.int32)
+        self._chk(self.lib.pai_cumsum(self._h, _ptr(ct), _ptr(exp), outer, L, inner, PAI_SCAN_REVERSE if reverse else 0,
+                                   _ptr(out), _ptr(oe)))
+        return out, oe
 
     def segment_dot(self, ct: np.ndarray, exp: np.ndarray, index: np.ndarray, seg_off: np.ndarray, x: np.ndarray):
         """Per-segment weighted sums: segment s = sum over t in [seg_off[s], seg_off[s+1]) of ct[index[t]] (x) x[t]

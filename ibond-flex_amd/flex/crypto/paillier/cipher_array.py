@@ -217,6 +217,22 @@ class PaillierArray(np.ndarray):
             return np.ndarray.__matmul__(np.asarray(self), b)
         return res
 
+    def cumsum(self, axis=None, dtype=None, out=None):
+        """np.cumsum / arr.cumsum: ONE pai_cumsum call when the array holds only ciphertexts of one key (the bits and
+        exponents of numpy's object loop, one __add__ per element; not obfuscated); anything else is numpy's own loop."""
+        res = cumsum_encrypted(self, axis) if dtype is None and out is None else NotImplemented
+        if res is NotImplemented:
+            return np.asarray(self).cumsum(axis=axis, dtype=dtype, out=out)
+        return res
+
+    def sum(self, axis=None, dtype=None, out=None, **kwargs):
+        """np.sum / arr.sum over one axis or over everything: ONE pai_segment_add call when the array holds only
+        ciphertexts of one key and the reduction is not empty; anything else is numpy's own reduction."""
+        res = sum_encrypted(self, axis) if dtype is None and out is None and not kwargs else NotImplemented
+        if res is NotImplemented:
+            return np.asarray(self).sum(axis=axis, dtype=dtype, out=out, **kwargs)
+        return res
+
     def pack(self, layout, max_abs):
         """Fold these ciphertexts into a PackedCiphertextBuffer (packed_buffer.pack_ciphertexts)."""
         from .packed_buffer import pack_ciphertexts
@@ -336,6 +352,59 @@ def add_encrypted(a, b):
     out, oe = ctx.add([wa, wb], [ea, eb])
     # __raw_add builds fresh, not-yet-obfuscated numbers (encrypted_number.py:180-185)
     return materialize(pk, out, oe, Ab.shape, obfuscated=False)
+
+
+def _scan_operand(a, axis):
+    """(array, public key, (outer, L, inner)) of a GPU scan or reduction of `a` along `axis` (None: flattened), or
+    None when numpy's own loop must run: no GPU, an empty array, anything but ciphertexts of one key inside, an axis
+    numpy would refuse."""
+    from . import _runtime
+    from .cipher_buffer import axis_split
+    if not _runtime.gpu_available():
+        return None
+    A, pk = _encrypted_operand(a)
+    if A is None or A.ndim == 0:
+        return None
+    if axis is None:
+        return A, pk, (1, A.size, 1)
+    if isinstance(axis, (bool, np.bool_)) or not isinstance(axis, (int, np.integer)) or not -A.ndim <= axis < A.ndim:
+        return None
+    return A, pk, axis_split(A.shape, axis)
+
+
+def cumsum_encrypted(a, axis=None, reverse: bool = False):
+    """Batched GPU cumsum of an encrypted array (np.cumsum semantics; reverse: suffix sums, the cumsum of the flipped
+    axis flipped back). NotImplemented when numpy's loop must run (_scan_operand)."""
+    from . import _runtime
+    got = _scan_operand(a, axis)
+    if got is None:
+        return NotImplemented
+    A, pk, (outer, L, inner) = got
+    words, exps, _ = pack(a if np.shape(a) == A.shape else A, pk)
+    out, oe = _runtime.context(pk).cumsum(words, exps, outer, L, inner, reverse)
+    return materialize(pk, out, oe, (A.size,) if axis is None else A.shape, obfuscated=False)
+
+
+def sum_encrypted(a, axis=None):
+    """Batched GPU sum of an encrypted array over one axis (a PaillierArray) or over everything (one
+    PaillierEncryptedNumber). NotImplemented when numpy's reduction must run (_scan_operand)."""
+    from . import _runtime
+    got = _scan_operand(a, axis)
+    if got is None:
+        return NotImplemented
+    A, pk, (outer, L, inner) = got
+    if L == 0:
+        return NotImplemented
+    words, exps, _ = pack(a if np.shape(a) == A.shape else A, pk)
+    idx = np.arange(A.size, dtype=np.int64).reshape(outer, L, inner).transpose(0, 2, 1).reshape(-1)
+    off = np.arange(outer * inner + 1, dtype=np.int64) * L
+    out, oe = _runtime.context(pk).segment_add(words, exps, idx, off)
+    if axis is None:
+        return materialize(pk, out, oe, (1,), obfuscated=False)[0]
+    ax = axis % A.ndim
+    shape = A.shape[:ax] + A.shape[ax + 1:]
+    res = materialize(pk, out, oe, shape if shape else (1,), obfuscated=False)
+    return res if shape else res[0]
 
 
 def _encrypted_like(y) -> bool:

@@ -229,6 +229,31 @@ class CiphertextBuffer(object):
         oe = np.where(cnt == 0, 0, oe).astype(np.int32)
         return self._like(out, oe, 0, shape), cnt.reshape(shape)
 
+    def cumsum(self, axis: int = -1, reverse: bool = False) -> "CiphertextBuffer":
+        """Running sums along `axis` (reverse: from the end), same shape, in ONE pai_cumsum call: element j is the
+        reference's __add__ chain over the elements up to j (np.cumsum over PaillierEncryptedNumber), at the largest
+        exponent of that prefix. An empty cell of a histogram (ciphertext 1, exponent 0) adds 0 like any other element.
+        Not obfuscated. Without a GPU the same runs on Python integers."""
+        outer, L, inner = axis_split(self.shape, axis)
+        out, oe = cumsum_words(self.public_key, self.words, self.exps, outer, L, inner, bool(reverse))
+        return self._like(out, oe)
+
+    def sum(self, axis=None) -> "CiphertextBuffer":
+        """Sum over `axis` (None: over everything, shape (1,)) in ONE pai_segment_add call over index lists built from
+        the shape; each sum is the reference's __add__ chain. An empty reduction is ciphertext 1 at exponent 0, an
+        unobfuscated encryption of 0. Without a GPU the same runs on Python integers."""
+        if axis is None:
+            outer, L, inner, shape = 1, self.size, 1, (1,)
+        else:
+            outer, L, inner = axis_split(self.shape, axis)
+            ax = axis % len(self.shape)
+            shape = self.shape[:ax] + self.shape[ax + 1:] or (1,)
+        idx = np.arange(outer * L * inner, dtype=np.int64).reshape(outer, L, inner).transpose(0, 2, 1).reshape(-1)
+        off = np.arange(outer * inner + 1, dtype=np.int64) * L
+        out, oe = segment_add_words(self.public_key, self.words, self.exps, idx, off)
+        oe = np.where(oe == EMPTY_EXP, 0, oe).astype(np.int32)
+        return self._like(out, oe, 0, shape)
+
     def pack(self, layout, max_abs):
         """Fold these ciphertexts into a PackedCiphertextBuffer (packed_buffer.pack_ciphertexts)."""
         from .packed_buffer import pack_ciphertexts
@@ -335,6 +360,67 @@ def segment_dot_words(pk, words, exps, idx, off, w):
 
 
 EMPTY_EXP = -(1 << 31)      # the exponent of an empty cell or segment (ciphertext 1)
+
+
+def axis_split(shape, axis):
+    """(outer, L, inner) of a C-contiguous array of `shape` scanned or reduced along `axis`."""
+    if isinstance(axis, (bool, np.bool_)) or not isinstance(axis, (int, np.integer)):
+        raise TypeError("axis must be an integer")
+    nd = len(shape)
+    if not -nd <= axis < nd:
+        raise ValueError(f"axis {axis} is out of bounds for an array of dimension {nd}")
+    ax = int(axis) % nd
+    return int(np.prod(shape[:ax], dtype=np.int64)), int(shape[ax]), int(np.prod(shape[ax + 1:], dtype=np.int64))
+
+
+def cumsum_words(pk, words, exps, outer: int, L: int, inner: int, reverse: bool = False):
+    """(words [outer L inner, W], exponents) of the prefix sums along the middle axis: pai_cumsum on the GPU, products of
+    Python integers without one. Entries with exponent EMPTY_EXP are skipped; a prefix of such entries only is
+    ciphertext 1 with exponent EMPTY_EXP."""
+    from . import _runtime
+    N, W = outer * L * inner, words.shape[1]
+    if N != np.asarray(exps).size:
+        raise ValueError("cumsum: outer * L * inner must be the number of ciphertexts")
+    if N and _runtime.gpu_available():
+        return _runtime.context(pk).cumsum(words, exps, outer, L, inner, reverse)
+    cts, nsq = _ints(words), pk.nsquare
+    ex = [int(e) for e in np.asarray(exps).reshape(-1)]
+    vals, oe = [1] * N, [EMPTY_EXP] * N
+    order = range(L - 1, -1, -1) if reverse else range(L)
+    for o in range(outer):
+        for i in range(inner):
+            acc, E = 1, EMPTY_EXP
+            for j in order:
+                t = (o * L + j) * inner + i
+                if ex[t] != EMPTY_EXP:
+                    if E == EMPTY_EXP:
+                        acc, E = cts[t], ex[t]
+                    elif ex[t] > E:
+                        acc, E = pow(acc, 16 ** (ex[t] - E), nsq) * cts[t] % nsq, ex[t]
+                    else:
+                        acc = acc * pow(cts[t], 16 ** (E - ex[t]), nsq) % nsq
+                vals[t], oe[t] = acc, E
+    return _runtime.ints_to_words(vals, W).reshape(N, W), np.array(oe, dtype=np.int32).reshape(N)
+
+
+def segment_add_words(pk, words, exps, idx, off):
+    """(words [nseg, W], exponents [nseg]) of the per-segment sums: pai_segment_add on the GPU, products of Python
+    integers without one. Empty segments: ciphertext 1, exponent EMPTY_EXP."""
+    from . import _runtime
+    nseg, W = off.size - 1, words.shape[1]
+    if nseg and _runtime.gpu_available():
+        return _runtime.context(pk).segment_add(words, exps, idx, off)
+    cts, nsq = _ints(words), pk.nsquare
+    vals, oe = [], []
+    for s in range(nseg):
+        mem = [int(t) for t in idx[int(off[s]):int(off[s + 1])]]
+        E = max((int(exps[t]) for t in mem), default=EMPTY_EXP)
+        acc = 1
+        for t in mem:
+            acc = acc * pow(cts[t], 16 ** (E - int(exps[t])), nsq) % nsq
+        vals.append(acc)
+        oe.append(E)
+    return _runtime.ints_to_words(vals, W).reshape(nseg, W), np.array(oe, dtype=np.int32).reshape(nseg)
 
 
 def histogram_args(N: int, bins, n_bins, node, n_nodes):

@@ -264,6 +264,23 @@ class PackedCiphertextBuffer(object):
         return (PackedCiphertextBuffer(self.public_key, out, self.layout, cells * k, shape + (k,), False, bound),
                 cnt.reshape(shape))
 
+    def cumsum(self, axis: int, reverse: bool = False) -> "PackedCiphertextBuffer":
+        """Running sums along a leading axis (reverse: from the end), every slot at once, in ONE pai_cumsum call; for
+        buffers whose last axis is exactly the slots of one ciphertext per index of the leading axes, which is what
+        histogram returns (ValueError for any other shape, and for the slot axis). The bound is this buffer's bound * the
+        length of the axis: the layout must be sized for the cumulated sums; OverflowError, before any GPU call, if it
+        passes the slot. Not obfuscated."""
+        from .cipher_buffer import axis_split, cumsum_words
+        k, C = self.layout.slots, self.words.shape[0]
+        if len(self.shape) < 2 or self.shape[-1] != k or self.count != C * k:
+            raise ValueError(f"cumsum: shape {self.shape} is not (..., {k}) with one ciphertext per index of the leading axes")
+        lead = self.shape[:-1]
+        outer, L, inner = axis_split(lead, axis)
+        bound = self.bound * L
+        self._check_bound(bound)
+        out, _ = cumsum_words(self.public_key, self.words, self._exps(), outer, L, inner, bool(reverse))
+        return self._like(out, bound)
+
     def apply_obfuscation(self) -> "PackedCiphertextBuffer":
         """Re-randomise every ciphertext in ONE pai_obfuscate call, unless the flag is already set. Returns self."""
         if self.obfuscated or self.words.shape[0] == 0:

@@ -88,6 +88,23 @@ def segment_sum(x: np.ndarray, index_lists) -> list:
     return res
 
 
+def cumsum(x: np.ndarray, axis: int = -1, reverse: bool = False) -> PaillierArray:
+    """``np.cumsum(x, axis)`` of an object array of PaillierEncryptedNumber under one key (reverse: the running sums from
+    the end of the axis) as ONE pai_cumsum call: each element is the reference's __add__ chain over its prefix, not
+    obfuscated. Without a GPU the same runs on Python integers."""
+    from .cipher_array import _encrypted_operand, materialize, pack
+    from .cipher_buffer import axis_split, cumsum_words
+    if not isinstance(x, np.ndarray):
+        raise TypeError(f"cumsum of {type(x)} not supported")
+    A, pk = _encrypted_operand(x)
+    if A is None or A.ndim == 0:
+        raise TypeError("cumsum needs a non-empty array of PaillierEncryptedNumber with one public key")
+    outer, L, inner = axis_split(A.shape, axis)
+    words, exps, _ = pack(x, pk)
+    out, oe = cumsum_words(pk, words, exps, outer, L, inner, bool(reverse))
+    return materialize(pk, out, oe, A.shape, obfuscated=False)
+
+
 def segment_dot(x: np.ndarray, index_lists, weight_lists) -> list:
     """``[sum(x[i] * w for i, w in zip(idx, ws)) for idx, ws in zip(index_lists, weight_lists)]`` (weighted per-bin sums,
     sparse gradient columns) as ONE segmented weighted sum on the GPU (pai_segment_dot), shaped like segment_sum: the

@@ -206,6 +206,12 @@ typedef struct pai_comm pai_comm;
 #define PAI_OPT_POOL_FUSED 22    /* 1 (default): pai_encrypt[_dev] with PAI_OBF_POOL runs k_pool_enc (kernels_pool.hpp: the
                                   * half-width product a + n ((b + M a) mod n)); 0: k_pool_join, the PAI_OBF_NONE
                                   * encryption and k_obf_mul, the kernels pinned to the reference. Same bits either way */
+#define PAI_OPT_SCAN_TILE 23     /* tile length of pai_cumsum[_dev]'s blocked path: 0 (default) automatic -- one tile per
+                                  * resident lane group of the chip, no tile shorter than 8 elements, and row chains when
+                                  * the rows alone fill the chip or are no longer than a tile; T > 0: tiles of T elements at
+                                  * every level of the scan (T >= L: row chains). Same bits for every value */
+#define PAI_OPT_SCAN_PATH 24     /* read-only: the path of this context's last pai_cumsum[_dev] call: 0 = none yet,
+                                  * 1 = row chains, 2 = blocked scan                                             */
 
 /* Number of visible GPUs (0 when there is none or the runtime cannot start). */
 int pai_device_count(int* count);
@@ -376,6 +382,30 @@ enum { PAI_BIN_U8 = 0, PAI_BIN_U16 = 1 };
 int pai_histogram(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int bin_dtype, const void* bins,
                   size_t F, size_t bin_stride, const int32_t* node, size_t nodes, size_t B, uint32_t* ct_out,
                   int32_t* exp_out, int64_t* count_out);
+/* Prefix sums of a ciphertext array along one axis. The array is C-contiguous [outer][L][inner] (element (o, j, i) at
+ * index (o L + j) inner + i, numpy's axis convention: no caller transposes). For every (o, i) and every j
+ *     E_j   = max over j' <= j of e_j'                               (entries with exponent INT32_MIN skipped)
+ *     out_j = prod over j' <= j of c_j'^(16^(E_j - e_j')) mod n^2     (canonical, < n^2)
+ * which equals pai_add / pai_segment_add over the members of the prefix bit for bit, with that call's exponent rule.
+ * PAI_SCAN_REVERSE scans from j = L - 1 downwards (suffix sums). An entry with exponent INT32_MIN (what
+ * pai_segment_add and pai_histogram emit for an empty segment, with ciphertext 1) is the identity: it never enters the
+ * maximum and no alignment is formed from it; a prefix of such entries only is ciphertext 1 with exponent INT32_MIN.
+ * Inputs must be < n^2, as for pai_add. The output is not re-randomised; the call needs the public key only.
+ *   outer, L or inner equal to 0: PAI_OK, nothing written. PAI_ERR_ARG before any launch: a null pointer with a
+ *   non-empty array, unknown flag bits, outer L inner at or above 2^31, an output that overlaps the input.
+ * Kernels (csrc/kernels_scan.hpp): k_scan runs one sequential chain per lane group, two Montgomery products per
+ * element on rows of one exponent. Many short rows take one chain per (o, i) row; few long rows are cut into tiles
+ * (PAI_OPT_SCAN_TILE): tile totals, a scan of the totals (recursively), then one chain per tile from its carry.
+ * PAI_OPT_SCAN_PATH reports the path. Every tiling gives the same bits.
+ * The host-buffer variant moves whole `outer` indices in slices of at most 1 GiB of ciphertext (one index at least) and
+ * never cuts L or inner, so a slice holds whole rows and the bits do not depend on the slices.
+ * The _dev variant (device pointers) takes the context lock and chains on the previous call's event like every _dev
+ * call; it never synchronises `stream` itself (no host read-back: launches only). On the blocked path the context's
+ * scratch buffer for the tiles' totals is freed and allocated again whenever a call needs more of it than any call
+ * before, and that allocation synchronises the device. */
+enum { PAI_SCAN_REVERSE = 1 };
+int pai_cumsum(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t outer, size_t L, size_t inner, int flags,
+               uint32_t* ct_out, int32_t* exp_out);
 /* Encrypted (m x K, row-major ciphertexts + exponents) times plain (K x d, row-major, dtype as above):
  * out[i][j] = sum_k ct[i][k] (x) x[k][j] with the reference's exponent alignment (bit-identical to
  * numpy's object dot over PaillierEncryptedNumber, whose sums are order independent). By default a product of
@@ -423,6 +453,8 @@ int pai_segment_dot_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp
 int pai_histogram_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int bin_dtype,
                       const void* d_bins, size_t F, size_t bin_stride, const int32_t* d_node, size_t nodes, size_t B,
                       uint32_t* d_out, int32_t* d_exp_out, int64_t* d_count_out, void* stream);
+int pai_cumsum_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t outer, size_t L, size_t inner,
+                   int flags, uint32_t* d_out, int32_t* d_exp_out, void* stream);
 
 /* Packed plaintexts: many signed fixed-point values per ciphertext (no reference counterpart; opt-in, both peers must
  * be flexpai; csrc/kernels_pack.hpp). Every packed ciphertext is an ordinary reference ciphertext
