@@ -55,6 +55,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_mm.hpp"
 #include "engine_sd.hpp"
 #include "engine_hist.hpp"
+#include "engine_shist.hpp"
 #include "engine_scan.hpp"
 #include "engine_obf.hpp"
 #include "engine_pack.hpp"
@@ -320,7 +321,17 @@ struct pai_ctx {
     std::vector<long long> cnt, index, segoff;
     std::vector<int32_t> cell_off;
     std::vector<int2> runs;
+    // pai_histogram_sparse (kernels_shist.hpp): read-backs of the checks, the default bins, and the default step's lists
+    long long nnz = 0;
+    unsigned err = 0;
+    std::vector<int32_t> zs, smem;
+    std::vector<int2> sruns;
+    std::vector<long long> sgidx, scount;
   } hist;
+  void* d_shist = nullptr;      // sparse histograms: the slot sums, the S values after them, and their exponents
+  size_t shist_bytes = 0;
+  void* d_shisterr = nullptr;   // the error bits of the CSR checks
+  size_t shisterr_bytes = 0;
   // prefix sums (kernels_scan.hpp): PAI_OPT_SCAN_TILE / PAI_OPT_SCAN_PATH
   int scan_tile = 0;            // 0: automatic tile length of the blocked path
   int scan_path = 0;            // last pai_cumsum[_dev] call: 0 none yet, 1 row chains, 2 blocked
@@ -424,6 +435,8 @@ pai_ctx::~pai_ctx() {
   if (d_histmeta) (void)hipFree(d_histmeta);
   if (d_histwork) (void)hipFree(d_histwork);
   if (d_histpart) (void)hipFree(d_histpart);
+  if (d_shist) (void)hipFree(d_shist);
+  if (d_shisterr) (void)hipFree(d_shisterr);
   if (d_scan) (void)hipFree(d_scan);
   if (d_inv) (void)hipFree(d_inv);
   if (inv_async) {
@@ -5117,15 +5130,15 @@ static int hist_check(const void* ct, const void* exp, size_t N, int bin_dtype, 
   return 0;
 }
 
-int pai_histogram_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int bin_dtype, const void* d_bins,
-                      size_t F, size_t bin_stride, const int32_t* d_node, size_t nodes, size_t B, uint32_t* d_out,
-                      int32_t* d_exp_out, int64_t* d_count_out, void* stream) {
-  if (!c) return fail(PAI_ERR_ARG, "null ctx");
-  CtxLock lk(c, (hipStream_t)stream);
-  int rc = hist_check(d_ct, d_exp, N, bin_dtype, d_bins, F, bin_stride, d_node, nodes, B, d_out, d_exp_out, "pai_histogram_dev");
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
+// The cell sums of nodes x F x B member lists over N ciphertexts. `count(d_cnt)` launches the pass that adds the members
+// per cell to the zeroed counters, `counted()` runs on the host once `st` has been synchronised for them, and
+// `scatter(f0, f1, d_cnt, d_off, d_cur, d_mem)` fills the member lists of one feature block. A cell holds at most N
+// members.
+template <typename Count, typename Counted, typename Scatter>
+static int hist_lists_dev(pai_ctx* c, const std::string& who, const uint32_t* d_ct, const int32_t* d_exp, size_t N, size_t F,
+                          size_t nodes, size_t B, Count&& count, Counted&& counted, Scatter&& scatter, uint32_t* d_out,
+                          int32_t* d_exp_out, int64_t* d_count_out, hipStream_t st) {
+  int rc = 0;
   const bool acc = hist_use_acc();
   const size_t W = c->ct_words, cells = nodes * F * B, R = hist_run_len(acc), row_bytes = acc ? 0 : R * 8;
   auto& h = c->hist;
@@ -5134,24 +5147,13 @@ int pai_histogram_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, si
   if ((rc = ensure_buf(&c->d_histmeta, &c->histmeta_bytes, o_runs))) return rc;
   unsigned long long* d_cnt = d_count_out ? (unsigned long long*)d_count_out : (unsigned long long*)c->d_histmeta;
   static_assert(sizeof(unsigned long long) == sizeof(int64_t), "count_out");
-  HistParams hp{};
-  hp.bins = d_bins;
-  hp.bin_u16 = bin_dtype == PAI_BIN_U16 ? 1 : 0;
-  hp.stride = (long long)bin_stride;
-  hp.node = d_node;
-  hp.nodes = (int)nodes;
-  hp.B = (int)B;
-  hp.N = (long long)N;
-  hp.F = (long long)F;
-  hp.count = d_cnt;
   HIPCHK(hipMemsetAsync(d_cnt, 0, cells * 8, st));
   h.cnt.assign(cells, 0);
   if (N) {
-    hp.f0 = 0;
-    hp.f1 = (long long)F;
-    HIPCHK(hist_count_launch(hp, c->cus, st));
+    if ((rc = count(d_cnt))) return rc;
     HIPCHK(hipMemcpyAsync(h.cnt.data(), d_cnt, cells * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    if ((rc = counted())) return rc;
   }
   // feature blocks: members (4 bytes each) and k_add's gather rows (8 R bytes per run) within the budget, one feature
   // at least
@@ -5168,7 +5170,7 @@ int pai_histogram_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, si
       for (size_t v = 0; v < nodes; ++v)
         for (size_t q = 0; q < B; ++q) {
           const long long n = h.cnt[(v * F + f) * B + q];
-          if (n < 0 || (size_t)n > N) return fail(PAI_ERR_HIP, "pai_histogram_dev: cell count out of range");
+          if (n < 0 || (size_t)n > N) return fail(PAI_ERR_HIP, who + ": cell count out of range");
           ent += (size_t)n;
           runs += ((size_t)n + R - 1) / R;
         }
@@ -5184,7 +5186,7 @@ int pai_histogram_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, si
     blocks.push_back(b);
     total_runs += b.runs;
   }
-  if (total_runs >= (size_t)INT32_MAX) return fail(PAI_ERR_ARG, "pai_histogram_dev: too many runs");
+  if (total_runs >= (size_t)INT32_MAX) return fail(PAI_ERR_ARG, who + ": too many runs");
   // member offsets (relative to the block's list) and runs in block order (v, f, b); the cells' partial rows
   h.cell_off.assign(cells, 0);
   h.runs.clear();
@@ -5238,16 +5240,10 @@ int pai_histogram_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, si
     HIPCHK(hipMemcpyAsync(d_off, h.cell_off.data(), cells * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_cur, 0, cells * 4, st));
     HIPCHK(hipMemcpyAsync(d_runs, h.runs.data(), total_runs * 8, hipMemcpyHostToDevice, st));
-    hp.count = d_cnt;
-    hp.cell_off = d_off;
-    hp.cursor = d_cur;
-    hp.members = d_mem;
     for (const Block& b : blocks) {
       if (!b.runs) continue;
       HIPCHK(hipMemsetAsync(d_mem, 0, b.entries * 4, st));
-      hp.f0 = (long long)b.f0;
-      hp.f1 = (long long)b.f1;
-      HIPCHK(hist_scatter_launch(hp, c->cus, st));
+      HIPCHK(scatter(b.f0, b.f1, d_cnt, d_off, d_cur, d_mem));
       if (acc) {
         HistAccParams ap{};
         ap.cts = d_ct;
@@ -5278,7 +5274,45 @@ int pai_histogram_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, si
   }
   // the partials of cell s are rows index[segoff[s] .. segoff[s + 1]); an empty cell has none (ciphertext 1, INT32_MIN)
   return pai_segment_add_dev(c, part, pexp, total_runs, (const int64_t*)h.index.data(), (const int64_t*)h.segoff.data(), cells, d_out,
-                             d_exp_out, stream);
+                             d_exp_out, (void*)st);
+}
+
+int pai_histogram_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int bin_dtype, const void* d_bins,
+                      size_t F, size_t bin_stride, const int32_t* d_node, size_t nodes, size_t B, uint32_t* d_out,
+                      int32_t* d_exp_out, int64_t* d_count_out, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  int rc = hist_check(d_ct, d_exp, N, bin_dtype, d_bins, F, bin_stride, d_node, nodes, B, d_out, d_exp_out, "pai_histogram_dev");
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  HistParams hp{};
+  hp.bins = d_bins;
+  hp.bin_u16 = bin_dtype == PAI_BIN_U16 ? 1 : 0;
+  hp.stride = (long long)bin_stride;
+  hp.node = d_node;
+  hp.nodes = (int)nodes;
+  hp.B = (int)B;
+  hp.N = (long long)N;
+  hp.F = (long long)F;
+  auto count = [&](unsigned long long* d_cnt) -> int {
+    hp.count = d_cnt;
+    hp.f0 = 0;
+    hp.f1 = (long long)F;
+    HIPCHK(hist_count_launch(hp, c->cus, st));
+    return 0;
+  };
+  auto scatter = [&](size_t f0, size_t f1, unsigned long long* d_cnt, const int32_t* d_off, unsigned* d_cur, int32_t* d_mem) {
+    hp.count = d_cnt;
+    hp.cell_off = d_off;
+    hp.cursor = d_cur;
+    hp.members = d_mem;
+    hp.f0 = (long long)f0;
+    hp.f1 = (long long)f1;
+    return hist_scatter_launch(hp, c->cus, st);
+  };
+  return hist_lists_dev(c, "pai_histogram_dev", d_ct, d_exp, N, F, nodes, B, count, [] { return 0; }, scatter, d_out, d_exp_out,
+                        d_count_out, st);
 }
 
 int pai_histogram(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, int bin_dtype, const void* bins, size_t F,
@@ -5337,6 +5371,262 @@ int pai_histogram(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, 
   }
   HIPCHK(hipMemcpy(ct_out, dout, cells * W * 4, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(exp_out, dexo, cells * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ------------------------------------------------------------------ sparse histograms (kernels_shist.hpp)
+// The bin matrix is CSR. Step one (shist_slots_dev) is the histogram above over the STORED entries: every (node,
+// feature) has B + 1 slots (the bins, and one for stored missing values), entries at the feature's default bin are
+// skipped, and the pseudo feature F lists all samples of every node, so that its slot 0 sums to T_v. The member lists
+// go through hist_lists_dev, so runs, feature blocks and the closing segmented add are the dense call's. Step two
+// (shist_finish_dev) works on the slot sums alone: S_{v,f} is one k_hist_acc run over the pair's non-empty slots but the
+// default one, the S values are inverted by the batch inversion of pai_mul, and ONE 2-way gather k_add writes every
+// cell of the output: (slot, -) for the other cells, (T_v, inv S) for a default cell, (T_v, -) where nothing is
+// stored beside it, (-, -) for an empty cell. The slot sums and T_v are exact residues at their largest exponent, so the bits
+// of step two depend on nothing in step one but the matrix; the host variant combines its chunks' slot sums first.
+static size_t shist_slots(size_t nodes, size_t F, size_t B) { return nodes * (F + 1) * (B + 1); }
+
+static int shist_check(const void* ct, const void* exp, size_t N, const void* indptr, int bin_dtype, size_t F, const void* default_bin,
+                       const int32_t* node, size_t nodes, size_t B, const void* ct_out, const void* exp_out, const char* who) {
+  const std::string w(who);
+  if ((N && (!ct || !exp)) || !indptr || !default_bin || !ct_out || !exp_out) return fail(PAI_ERR_ARG, w + ": null pointer");
+  if (bin_dtype != PAI_BIN_U8 && bin_dtype != PAI_BIN_U16) return fail(PAI_ERR_ARG, w + ": bin_dtype must be PAI_BIN_U8 or PAI_BIN_U16");
+  if (F == 0) return fail(PAI_ERR_ARG, w + ": F must be at least 1");
+  if (B == 0 || B > (bin_dtype == PAI_BIN_U8 ? (size_t)256 : (size_t)65536)) return fail(PAI_ERR_ARG, w + ": B out of range for the bin type");
+  if (nodes == 0 || (!node && nodes != 1)) return fail(PAI_ERR_ARG, w + ": nodes must be >= 1, and 1 without node ids");
+  if (nodes > HIST_MAX_CELLS || F > HIST_MAX_CELLS || nodes * F > HIST_MAX_CELLS || nodes * F * B > HIST_MAX_CELLS)
+    return fail(PAI_ERR_ARG, w + ": more than 2^24 cells");
+  if (N >= ((size_t)1 << 31)) return fail(PAI_ERR_ARG, w + ": N must be below 2^31");
+  return 0;
+}
+
+// d_sct / d_sexp [shist_slots]: the slot sums; their member counts stay in c->hist.cnt
+static int shist_slots_dev(pai_ctx* c, const char* who, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_indptr,
+                           const int32_t* d_indices, int bin_dtype, const void* d_data, size_t F, const int32_t* d_default,
+                           const int32_t* d_node, size_t nodes, size_t B, uint32_t* d_sct, int32_t* d_sexp, hipStream_t st) {
+  const std::string w(who);
+  auto& h = c->hist;
+  int rc = ensure_buf(&c->d_shisterr, &c->shisterr_bytes, 16);
+  if (rc) return rc;
+  unsigned* d_err = (unsigned*)c->d_shisterr;
+  HIPCHK(hipMemsetAsync(d_err, 0, 4, st));
+  static_assert(sizeof(long long) == sizeof(int64_t), "indptr");
+  HIPCHK(shist_indptr_launch((const long long*)d_indptr, (long long)N, d_err, c->cus, st));
+  HIPCHK(hipMemcpyAsync(&h.nnz, d_indptr + N, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&h.err, d_err, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (h.err) return fail(PAI_ERR_ARG, w + ": indptr must start at 0 and must not decrease");
+  if (h.nnz < 0 || h.nnz >= (1ll << 31)) return fail(PAI_ERR_ARG, w + ": nnz must be below 2^31");
+  if (h.nnz && (!d_indices || !d_data)) return fail(PAI_ERR_ARG, w + ": null pointer");
+  SHistParams sp{};
+  sp.indptr = (const long long*)d_indptr;
+  sp.indices = d_indices;
+  sp.data = d_data;
+  sp.bin_u16 = bin_dtype == PAI_BIN_U16 ? 1 : 0;
+  sp.default_bin = d_default;
+  sp.node = d_node;
+  sp.nodes = (int)nodes;
+  sp.B = (int)B;
+  sp.N = (long long)N;
+  sp.F = (long long)F;
+  sp.nnz = h.nnz;
+  sp.err = d_err;
+  auto count = [&](unsigned long long* d_cnt) -> int {
+    sp.count = d_cnt;
+    sp.f0 = 0;
+    sp.f1 = (long long)F + 1;
+    HIPCHK(shist_count_launch(sp, c->cus, st));
+    HIPCHK(hipMemcpyAsync(&h.err, d_err, 4, hipMemcpyDeviceToHost, st));
+    return 0;
+  };
+  auto counted = [&]() -> int {
+    if (h.err & SHIST_ERR_INDEX) return fail(PAI_ERR_ARG, w + ": index outside [0, F)");
+    if (h.err & SHIST_ERR_ORDER) return fail(PAI_ERR_ARG, w + ": the indices of a row must be strictly increasing");
+    return 0;
+  };
+  auto scatter = [&](size_t f0, size_t f1, unsigned long long* d_cnt, const int32_t* d_off, unsigned* d_cur, int32_t* d_mem) {
+    sp.count = d_cnt;
+    sp.cell_off = d_off;
+    sp.cursor = d_cur;
+    sp.members = d_mem;
+    sp.f0 = (long long)f0;
+    sp.f1 = (long long)f1;
+    return shist_scatter_launch(sp, c->cus, st);
+  };
+  return hist_lists_dev(c, w, d_ct, d_exp, N, F + 1, nodes, B + 1, count, counted, scatter, d_sct, d_sexp, nullptr, st);
+}
+
+// d_s / d_se hold the slot sums and room for nodes F more rows (the S values). cnt: members per slot, zs: default bins
+// (both host memory).
+static int shist_finish_dev(pai_ctx* c, const char* who, uint32_t* d_s, int32_t* d_se, const long long* cnt, const int32_t* zs, size_t F,
+                            size_t nodes, size_t B, uint32_t* d_out, int32_t* d_exp_out, int64_t* d_count_out, hipStream_t st) {
+  const size_t F1 = F + 1, B1 = B + 1, slots = shist_slots(nodes, F, B), cells = nodes * F * B, W = c->ct_words;
+  auto& h = c->hist;
+  h.sgidx.assign(cells * 2, -1ll);
+  h.scount.assign(cells, 0);
+  h.smem.clear();
+  h.sruns.clear();
+  for (size_t v = 0; v < nodes; ++v) {
+    const size_t total = (v * F1 + F) * B1;
+    for (size_t f = 0; f < F; ++f) {
+      const size_t base = (v * F1 + f) * B1, cell0 = (v * F + f) * B;
+      const bool has = zs[f] >= 0 && (size_t)zs[f] < B;
+      const size_t z = has ? (size_t)zs[f] : B1;
+      for (size_t b = 0; b < B; ++b) {
+        if (b == z) continue;
+        h.scount[cell0 + b] = cnt[base + b];
+        if (cnt[base + b]) h.sgidx[2 * (cell0 + b)] = (long long)(base + b);
+      }
+      if (!has) continue;
+      const size_t first = h.smem.size();
+      long long stored = 0;
+      for (size_t q = 0; q < B1; ++q)
+        if (q != z && cnt[base + q]) {
+          stored += cnt[base + q];
+          h.smem.push_back((int32_t)(base + q));
+        }
+      const long long rest = cnt[total] - stored;
+      if (rest < 0) return fail(PAI_ERR_ARG, std::string(who) + ": a node holds more stored entries of a feature than samples");
+      h.scount[cell0 + z] = rest;
+      if (rest == 0 || stored == 0) h.smem.resize(first);        // an empty default cell, or T_v itself: no S
+      if (rest == 0) continue;
+      h.sgidx[2 * (cell0 + z)] = (long long)total;
+      if (stored) {
+        h.sgidx[2 * (cell0 + z) + 1] = (long long)(slots + h.sruns.size());
+        h.sruns.push_back(make_int2((int)first, (int)(h.smem.size() - first)));
+      }
+    }
+  }
+  const size_t pairs = h.sruns.size(), o_runs = align16(h.smem.size() * 4), o_g = align16(o_runs + pairs * 8);
+  int rc = ensure_buf(&c->d_histwork, &c->histwork_bytes, o_g + cells * 16);
+  if (rc) return rc;
+  int32_t* d_mem = (int32_t*)c->d_histwork;
+  int2* d_runs = (int2*)((char*)c->d_histwork + o_runs);
+  long long* d_g = (long long*)((char*)c->d_histwork + o_g);
+  HIPCHK(hipMemcpyAsync(d_g, h.sgidx.data(), cells * 16, hipMemcpyHostToDevice, st));
+  if (pairs) {
+    HIPCHK(hipMemcpyAsync(d_mem, h.smem.data(), h.smem.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_runs, h.sruns.data(), pairs * 8, hipMemcpyHostToDevice, st));
+    HistAccParams ap{};
+    ap.cts = d_s;
+    ap.exps = d_se;
+    ap.members = d_mem;
+    ap.runs = d_runs;
+    ap.nruns = (long long)pairs;
+    ap.out = d_s + slots * W;
+    ap.out_exp = d_se + slots;
+    ap.N = c->d_N;
+    ap.RS = c->d_RS;
+    ap.mprime = c->mprime_N;
+    ap.ct_words = c->ct_words;
+    HIPCHK(hist_acc_launch(c->tpi_e, ap, c->cus, st));
+    if ((rc = batch_invert(c, d_s + slots * W, nullptr, (long long)pairs, st))) return rc;
+  }
+  if ((rc = run_add(c, add_params(d_s, d_se, 2, (long long)cells, d_out, d_exp_out, d_g), st))) return rc;
+  if (d_count_out) HIPCHK(hipMemcpyAsync(d_count_out, h.scount.data(), cells * 8, hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+int pai_histogram_sparse_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_indptr,
+                             const int32_t* d_indices, int bin_dtype, const void* d_data, size_t F, const int32_t* d_default_bin,
+                             const int32_t* d_node, size_t nodes, size_t B, uint32_t* d_out, int32_t* d_exp_out,
+                             int64_t* d_count_out, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  const char* who = "pai_histogram_sparse_dev";
+  int rc = shist_check(d_ct, d_exp, N, d_indptr, bin_dtype, F, d_default_bin, d_node, nodes, B, d_out, d_exp_out, who);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t W = c->ct_words, rows = shist_slots(nodes, F, B) + nodes * F, o_exp = align16(rows * W * 4);
+  if ((rc = ensure_buf(&c->d_shist, &c->shist_bytes, o_exp + rows * 4))) return rc;
+  uint32_t* d_s = (uint32_t*)c->d_shist;
+  int32_t* d_se = (int32_t*)((char*)c->d_shist + o_exp);
+  c->hist.zs.assign(F, 0);
+  HIPCHK(hipMemcpyAsync(c->hist.zs.data(), d_default_bin, F * 4, hipMemcpyDeviceToHost, st));   // (read after the next synchronisation)
+  if ((rc = shist_slots_dev(c, who, d_ct, d_exp, N, d_indptr, d_indices, bin_dtype, d_data, F, d_default_bin, d_node, nodes, B, d_s,
+                            d_se, st)))
+    return rc;
+  return shist_finish_dev(c, who, d_s, d_se, c->hist.cnt.data(), c->hist.zs.data(), F, nodes, B, d_out, d_exp_out, d_count_out, st);
+}
+
+int pai_histogram_sparse(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, const int64_t* indptr, const int32_t* indices,
+                         int bin_dtype, const void* data, size_t F, const int32_t* default_bin, const int32_t* node, size_t nodes,
+                         size_t B, uint32_t* ct_out, int32_t* exp_out, int64_t* count_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  const char* who = "pai_histogram_sparse";
+  int rc = shist_check(ct, exp, N, indptr, bin_dtype, F, default_bin, node, nodes, B, ct_out, exp_out, who);
+  if (rc) return rc;
+  // (the offsets cut host arrays below, so they are checked here; the indices are checked on the device)
+  if (indptr[0] != 0) return fail(PAI_ERR_ARG, std::string(who) + ": indptr must start at 0 and must not decrease");
+  for (size_t i = 0; i < N; ++i)
+    if (indptr[i + 1] < indptr[i]) return fail(PAI_ERR_ARG, std::string(who) + ": indptr must start at 0 and must not decrease");
+  if (indptr[N] >= (1ll << 31)) return fail(PAI_ERR_ARG, std::string(who) + ": nnz must be below 2^31");
+  if (indptr[N] && (!indices || !data)) return fail(PAI_ERR_ARG, std::string(who) + ": null pointer");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t W = c->ct_words, slots = shist_slots(nodes, F, B), cells = nodes * F * B, rows = slots + nodes * F,
+               bsz = bin_dtype == PAI_BIN_U16 ? 2 : 1;
+  // chunks of samples as in pai_histogram; their slot sums [chunk][slots] are the operands of one k-way add
+  size_t chunk = HIST_HOST_CHUNK;
+  if (const char* e = xcheck_env("FLEXPAI_HIST_CHUNK")) {           // test build: chunks at small shapes
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    if (v > 0) chunk = (size_t)v;
+  }
+  const size_t kmax = std::max<size_t>(HIST_HOST_PART_BYTES / (slots * W * 4), 1);
+  if ((N + chunk - 1) / chunk > kmax) chunk = (N + kmax - 1) / kmax;
+  const size_t k = std::max<size_t>((N + chunk - 1) / chunk, 1), nc = std::min(chunk, std::max<size_t>(N, 1));
+  size_t ne = 0;
+  for (size_t i0 = 0; i0 < N; i0 += chunk) ne = std::max(ne, (size_t)(indptr[std::min(N, i0 + chunk)] - indptr[i0]));
+  DevScope ds;
+  uint32_t* dct = ds.alloc<uint32_t>(nc * W);
+  int32_t* dexp = ds.alloc<int32_t>(nc);
+  int64_t* dptr = ds.alloc<int64_t>(nc + 1);
+  int32_t* dind = ds.alloc<int32_t>(ne);
+  uint8_t* ddata = ds.alloc<uint8_t>(ne * bsz);
+  int32_t* ddef = ds.alloc<int32_t>(F);
+  int32_t* dnode = node ? ds.alloc<int32_t>(nc) : nullptr;
+  // (k == 1: the chunk's slot sums are the finish step's buffer, with the S rows after them)
+  uint32_t* dpart = ds.alloc<uint32_t>(k > 1 ? k * slots * W : rows * W);
+  int32_t* dpexp = ds.alloc<int32_t>(k > 1 ? k * slots : rows);
+  uint32_t* dsum = k > 1 ? ds.alloc<uint32_t>(rows * W) : dpart;
+  int32_t* dsexp = k > 1 ? ds.alloc<int32_t>(rows) : dpexp;
+  uint32_t* dout = ds.alloc<uint32_t>(cells * W);
+  int32_t* dexo = ds.alloc<int32_t>(cells);
+  int64_t* dcnt = ds.alloc<int64_t>(cells);
+  if (!dct || !dexp || !dptr || !dind || !ddata || !ddef || (node && !dnode) || !dpart || !dpexp || !dsum || !dsexp || !dout || !dexo ||
+      !dcnt)
+    return fail(PAI_ERR_HIP, std::string(who) + ": device allocation failed");
+  HIPCHK(hipMemcpy(ddef, default_bin, F * 4, hipMemcpyHostToDevice));
+  std::vector<long long> cnt(slots, 0);
+  std::vector<int64_t> ptr(nc + 1);
+  for (size_t q = 0; q < k; ++q) {
+    const size_t i0 = q * chunk, n = N ? std::min(chunk, N - i0) : 0;
+    const int64_t e0 = indptr[i0];
+    const size_t m = (size_t)(indptr[i0 + n] - e0);
+    for (size_t i = 0; i <= n; ++i) ptr[i] = indptr[i0 + i] - e0;
+    HIPCHK(hipMemcpy(dptr, ptr.data(), (n + 1) * 8, hipMemcpyHostToDevice));
+    if (n) {
+      HIPCHK(hipMemcpy(dct, ct + i0 * W, n * W * 4, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(dexp, exp + i0, n * 4, hipMemcpyHostToDevice));
+      if (node) HIPCHK(hipMemcpy(dnode, node + i0, n * 4, hipMemcpyHostToDevice));
+    }
+    if (m) {
+      HIPCHK(hipMemcpy(dind, indices + e0, m * 4, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(ddata, (const char*)data + (size_t)e0 * bsz, m * bsz, hipMemcpyHostToDevice));
+    }
+    if ((rc = shist_slots_dev(c, who, dct, dexp, n, dptr, dind, bin_dtype, ddata, F, ddef, dnode, nodes, B, dpart + q * slots * W,
+                              dpexp + q * slots, nullptr)))
+      return rc;
+    HIPCHK(hipDeviceSynchronize());
+    for (size_t s = 0; s < slots; ++s) cnt[s] += c->hist.cnt[s];
+  }
+  if (k > 1 && (rc = add_dev(c, dpart, dpexp, (int)k, (long long)slots, dsum, dsexp, nullptr))) return rc;
+  if ((rc = shist_finish_dev(c, who, dsum, dsexp, cnt.data(), default_bin, F, nodes, B, dout, dexo, dcnt, nullptr))) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(ct_out, dout, cells * W * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(exp_out, dexo, cells * 4, hipMemcpyDeviceToHost));
+  if (count_out) HIPCHK(hipMemcpy(count_out, dcnt, cells * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 

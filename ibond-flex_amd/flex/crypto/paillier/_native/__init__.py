@@ -56,6 +56,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_pack_max_slots", "pai_encrypt_packed", "pai_encrypt_packed_dev", "pai_decrypt_packed",
             "pai_decrypt_packed_dev", "pai_pack_ciphertexts", "pai_pack_ciphertexts_dev",
             "pai_segment_dot", "pai_segment_dot_dev", "pai_histogram", "pai_histogram_dev",
+            "pai_histogram_sparse", "pai_histogram_sparse_dev",
             "pai_cumsum", "pai_cumsum_dev",
             "pai_pool_reserve", "pai_pool_fill", "pai_pool_fill_dev", "pai_pool_put", "pai_pool_put_dev", "pai_pool_info")
 PAI_COMM_ID_BYTES = 128
@@ -134,6 +135,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_segment_dot_dev.argtypes = [P, P, P, S, P, P, S, I, P, P, P, P, P]
         lib.pai_histogram.argtypes = [P, P, P, S, I, P, S, S, P, S, S, P, P, P]
         lib.pai_histogram_dev.argtypes = [P, P, P, S, I, P, S, S, P, S, S, P, P, P, P]
+        lib.pai_histogram_sparse.argtypes = [P, P, P, S, P, P, I, P, S, P, P, S, S, P, P, P]
+        lib.pai_histogram_sparse_dev.argtypes = [P, P, P, S, P, P, I, P, S, P, P, S, S, P, P, P, P]
         lib.pai_cumsum.argtypes = [P, P, P, S, S, S, I, P, P]
         lib.pai_cumsum_dev.argtypes = [P, P, P, S, S, S, I, P, P, P]
         lib.pai_matmul.argtypes = [P, P, P, S, S, I, P, S, P, P]
@@ -868,6 +871,41 @@ class Context:
         self._chk(self.lib.pai_histogram(self._h, _ptr(ct), _ptr(exp), N, PAI_BIN_U16 if isz == 2 else PAI_BIN_U8,
                                       _ptr(bins), F, stride, _ptr(node) if node is not None else None, int(n_nodes),
                                       int(n_bins), _ptr(out), _ptr(oe), _ptr(cnt)))
+        return out, oe, cnt
+
+    def histogram_sparse(self, ct: np.ndarray, exp: np.ndarray, indptr: np.ndarray, indices: np.ndarray, data: np.ndarray,
+                         n_features: int, default_bin: np.ndarray, n_bins: int, node=None, n_nodes: int = 1):
+        """histogram over a CSR matrix of bin ids (pai_histogram_sparse, one call): indptr [N + 1], indices (features,
+        strictly increasing inside a row) and data (uint8 / uint16 bin ids) of the stored entries, default_bin [F] the
+        bin of every entry that is not stored. Returns (words [n_nodes F n_bins, W], exponents, counts int64) laid out
+        like histogram; the default cells are T_v - S_{v,f} (include/flexpai.h). The arguments are the checked ones of
+        cipher_buffer.histogram_sparse_args."""
+        ct = np.ascontiguousarray(ct, dtype=np.uint32)
+        exp = np.ascontiguousarray(exp, dtype=np.int32)
+        N = exp.size
+        self._check_words(ct, exp, N)
+        if data.dtype not in (np.uint8, np.uint16):
+            raise ValueError("histogram: the stored bin ids must be uint8 or uint16")
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        data = np.ascontiguousarray(data)
+        default_bin = np.ascontiguousarray(default_bin, dtype=np.int32)
+        F = int(n_features)
+        if indptr.shape != (N + 1,) or indices.shape != data.shape or indices.ndim != 1 or default_bin.shape != (F,):
+            raise ValueError("histogram: malformed CSR operand")
+        if node is not None:
+            node = np.ascontiguousarray(node, dtype=np.int32)
+            if node.shape != (N,):
+                raise ValueError("histogram: one node id per ciphertext")
+        cells = int(n_nodes) * F * int(n_bins)
+        self.calls["pai_histogram_sparse"] += 1
+        out = np.empty((max(cells, 0), self.ct_words), dtype=np.uint32)
+        oe = np.empty(max(cells, 0), dtype=np.int32)
+        cnt = np.empty(max(cells, 0), dtype=np.int64)
+        self._chk(self.lib.pai_histogram_sparse(self._h, _ptr(ct), _ptr(exp), N, _ptr(indptr), _ptr(indices),
+                                             PAI_BIN_U16 if data.dtype.itemsize == 2 else PAI_BIN_U8, _ptr(data), F,
+                                             _ptr(default_bin), _ptr(node) if node is not None else None, int(n_nodes),
+                                             int(n_bins), _ptr(out), _ptr(oe), _ptr(cnt)))
         return out, oe, cnt
 
     def cumsum(self, ct: np.ndarray, exp: np.ndarray, outer: int, L: int, inner: int, reverse: bool = False):

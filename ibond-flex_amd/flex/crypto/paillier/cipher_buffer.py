@@ -217,13 +217,24 @@ class CiphertextBuffer(object):
 
     __matmul__ = dot
 
-    def histogram(self, bins, n_bins: int, node=None, n_nodes: int = 1):
+    def histogram(self, bins, n_bins: int, node=None, n_nodes: int = 1, default_bin=0):
         """Per-cell sums of these N ciphertexts (flat order) over the bin ids bins [N, F] (uint8 / uint16) and an optional
         node id per sample: (CiphertextBuffer of shape (n_nodes, F, n_bins), int64 counts of that shape), cell
         [v, f, b] = the sum of the samples with node == v and bins[:, f] == b, in ONE pai_histogram call with no index
         list. A node id outside [0, n_nodes) and a bin id >= n_bins put the sample in no cell (of that feature). Each
         sum is the reference's __add__ chain over the members; an empty cell is ciphertext 1 at exponent 0, an
-        unobfuscated encryption of 0. Without a GPU the same runs on Python integers."""
+        unobfuscated encryption of 0. Without a GPU the same runs on Python integers.
+        Sparse bins (anything that offers .tocsr(); never densified, never re-routed to the dense call) take ONE
+        pai_histogram_sparse call whose cost follows the stored entries: an entry that is not stored has bin
+        default_bin (a scalar or one per feature, out of range: in no cell), and the default cell [v, f, default_bin[f]]
+        is T_v - S: the node's total minus the feature's stored entries off the default bin, at the node's largest
+        exponent (the dense call's plaintext; its bits too wherever a node's exponents are uniform)."""
+        csr = sparse_csr(bins)
+        if csr is not None:
+            *args, shape = histogram_sparse_args(self.size, csr, n_bins, node, n_nodes, default_bin)
+            out, oe, cnt = histogram_sparse_words(self.public_key, self.words, self.exps, *args, shape)
+            oe = np.where(cnt == 0, 0, oe).astype(np.int32)
+            return self._like(out, oe, 0, shape), cnt.reshape(shape)
         b, nd, shape = histogram_args(self.size, bins, n_bins, node, n_nodes)
         out, oe, cnt = histogram_words(self.public_key, self.words, self.exps, b, int(n_bins), nd, int(n_nodes))
         oe = np.where(cnt == 0, 0, oe).astype(np.int32)
@@ -488,6 +499,147 @@ def histogram_words(pk, words, exps, bins, n_bins: int, node, n_nodes: int):
         s = int(cell[i, f])
         acc[s] = acc[s] * pow(cts[i], 16 ** (int(E[s]) - int(exps[i])), nsq) % nsq
     return _runtime.ints_to_words(acc, W).reshape(cells, W), E.astype(np.int32), cnt
+
+
+def sparse_csr(b):
+    """(indptr, indices, data, shape) of a 2-D sparse matrix in canonical CSR form, for any object that offers .tocsr()
+    (duck typing: scipy is not imported here); None for everything else. Duplicates are summed and the indices sorted
+    where the object offers sum_duplicates() / sort_indices(), on a copy when .tocsr() returned the operand itself."""
+    if isinstance(b, np.ndarray) or not hasattr(b, "tocsr"):
+        return None
+    c = b.tocsr()
+    if c is b and hasattr(c, "copy"):
+        c = c.copy()
+    for name in ("sum_duplicates", "sort_indices"):
+        fn = getattr(c, name, None)
+        if callable(fn):
+            fn()
+    shape = tuple(int(v) for v in c.shape)
+    if len(shape) != 2:
+        raise ValueError(f"histogram: sparse bins of shape {shape} are not a matrix")
+    indptr = np.asarray(c.indptr).reshape(-1)
+    indices = np.asarray(c.indices).reshape(-1)
+    data = np.asarray(c.data).reshape(-1)
+    if (indptr.size != shape[0] + 1 or indices.size != data.size or indptr.dtype.kind not in "iu"
+            or (indices.size and indices.dtype.kind not in "iu")):
+        raise ValueError("histogram: malformed CSR operand")
+    return indptr.astype(np.int64), indices.astype(np.int64), data, shape
+
+
+def histogram_sparse_args(N: int, csr, n_bins, node, n_nodes, default_bin):
+    """Checked (indptr int64 [N + 1], indices int32 [nnz], data uint8 / uint16 [nnz], default bins int32 [F] with -1 for
+    "in no cell", node int32 [N] or None, (n_nodes, F, n_bins)) of a histogram over the CSR bins of sparse_csr. Stored
+    ids are cast to uint8 below 256 bins and to uint16 from there; an id >= n_bins (a missing value) becomes n_bins."""
+    indptr, indices, data, (rows, F) = csr
+    if rows != N or F == 0:
+        raise ValueError(f"histogram: bins must have shape ({N}, F) with F >= 1, not {(rows, F)}")
+    if isinstance(n_bins, (bool, np.bool_)) or not isinstance(n_bins, (int, np.integer)):
+        raise TypeError("histogram: n_bins must be an integer")
+    B = int(n_bins)
+    if not 1 <= B <= 65536:
+        raise ValueError("histogram: n_bins must be in 1 .. 65536")
+    # (the dense rules for node and n_nodes, and the cell limit)
+    _, node, shape = histogram_args(N, np.zeros((N, 1), dtype=np.uint16), 1, node, n_nodes)
+    if shape[0] * F * B > 1 << 24:
+        raise ValueError("histogram: more than 2^24 cells")
+    if indptr[0] != 0 or np.any(np.diff(indptr) < 0) or indptr[-1] != indices.size:
+        raise ValueError("histogram: indptr must start at 0, must not decrease and must end at the stored entries")
+    if indices.size >= 1 << 31:
+        raise ValueError("histogram: bins must hold fewer than 2^31 stored entries")
+    if indices.size and (indices.min() < 0 or indices.max() >= F):
+        raise IndexError(f"histogram: feature index out of range for {F} features")
+    if indices.size > 1:
+        inner = np.ones(indices.size - 1, dtype=bool)
+        ends = indptr[1:-1]
+        inner[ends[(ends > 0) & (ends < indices.size)] - 1] = False        # pairs that straddle two rows
+        if np.any((np.diff(indices) <= 0) & inner):
+            raise ValueError("histogram: the feature indices of a row must be strictly increasing (sorted, no duplicates)")
+    if data.dtype.kind == "f":
+        if not np.all(np.isfinite(data)) or np.any(data != np.floor(data)):
+            raise ValueError("histogram: stored bin ids must be integers")
+    elif data.dtype.kind not in "iub":
+        raise TypeError(f"histogram: unsupported bin dtype {data.dtype}")
+    if data.size and data.min() < 0:
+        raise ValueError("histogram: stored bin ids must not be negative")
+    if B == 65536 and data.size and data.max() > 65535:
+        raise ValueError("histogram: with 65536 bins no id is left for a missing value")
+    ids = np.minimum(data, B).astype(np.uint8 if B < 256 else np.uint16)
+    z = np.asarray(default_bin)
+    if z.dtype.kind not in "iu" or z.ndim > 1 or (z.ndim == 1 and z.size != F):
+        raise ValueError(f"histogram: default_bin must be an integer or {F} integers")
+    z = np.broadcast_to(z.astype(np.int64), (F,))
+    zs = np.where((z >= 0) & (z < B), z, -1).astype(np.int32)
+    return indptr, indices.astype(np.int32), ids, zs, node, (shape[0], F, B)
+
+
+def histogram_sparse_counts(indptr, indices, data, zs, node, shape):
+    """(counts int64 [cells], stored mask, node per stored entry, row per stored entry): the members of every cell of the
+    sparse histogram, default cells included (count(v) minus the stored non-default entries of (v, f)); the mask selects
+    the stored entries that enter a slot (valid node, not at the default bin)."""
+    nodes, F, B = shape
+    N = indptr.size - 1
+    v = np.zeros(N, dtype=np.int64) if node is None else node.astype(np.int64)
+    okv = (v >= 0) & (v < nodes)
+    rows = np.repeat(np.arange(N, dtype=np.int64), np.diff(indptr))
+    f = indices.astype(np.int64)
+    b = data.astype(np.int64)
+    sel = okv[rows] & ~((b < B) & (b == zs[f]))
+    vr = v[rows]
+    cell = (vr * F + f) * B + b
+    cnt = np.bincount(cell[sel & (b < B)], minlength=nodes * F * B).astype(np.int64).reshape(nodes, F, B)
+    stored = np.bincount((vr * F + f)[sel], minlength=nodes * F).astype(np.int64).reshape(nodes, F)
+    cv = np.bincount(v[okv], minlength=nodes).astype(np.int64)
+    fz = np.flatnonzero(zs >= 0)
+    cnt[:, fz, zs[fz]] = cv[:, None] - stored[:, fz]
+    return cnt.reshape(-1), sel, vr, rows
+
+
+def histogram_sparse_words(pk, words, exps, indptr, indices, data, zs, node, shape):
+    """(words [cells, W], exponents [cells], counts int64 [cells]) of the sparse histogram over checked arguments:
+    pai_histogram_sparse on the GPU, Python integers without one. A cell off the default bin is the product over its
+    stored members; a default cell is T_v * invert(S_{v,f})^(16^(E_T - E_S)) at the node's exponent E_T, T_v itself where
+    nothing else is stored, and empty (ciphertext 1, EMPTY_EXP) where its count is 0."""
+    from . import _runtime
+    nodes, F, B = shape
+    if _runtime.gpu_available():
+        return _runtime.context(pk).histogram_sparse(words, exps, indptr, indices, data, F, zs, B, node, nodes)
+    W, cells = words.shape[1], nodes * F * B
+    cnt, sel, vr, rows = histogram_sparse_counts(indptr, indices, data, zs, node, shape)
+    cts, nsq = _ints(words), pk.nsquare
+    ex = [int(e) for e in np.asarray(exps).reshape(-1)]
+
+    def fold(members):
+        E = max((ex[i] for i in members), default=EMPTY_EXP)
+        acc = 1
+        for i in members:
+            acc = acc * pow(cts[i], 16 ** (E - ex[i]), nsq) % nsq
+        return acc, E
+
+    in_cell, in_rest = {}, {}
+    for t in np.flatnonzero(sel).tolist():
+        v, f, b, i = int(vr[t]), int(indices[t]), int(data[t]), int(rows[t])
+        if b < B:
+            in_cell.setdefault((v * F + f) * B + b, []).append(i)
+        in_rest.setdefault(v * F + f, []).append(i)
+    v_of = np.zeros(len(ex), dtype=np.int64) if node is None else node.astype(np.int64)
+    totals = [fold(np.flatnonzero(v_of == v).tolist()) for v in range(nodes)]
+    acc, oe = [1] * cells, [EMPTY_EXP] * cells
+    for s, members in in_cell.items():
+        acc[s], oe[s] = fold(members)
+    for v in range(nodes):
+        for f in np.flatnonzero(zs >= 0).tolist():
+            s = (v * F + f) * B + int(zs[f])
+            if cnt[s] == 0:
+                continue
+            (T, ET), rest = totals[v], in_rest.get(v * F + f)
+            if rest:
+                S, ES = fold(rest)
+                try:
+                    T = T * pow(pow(S, -1, nsq), 16 ** (ET - ES), nsq) % nsq
+                except ValueError as e:
+                    raise ZeroDivisionError("invert() no inverse exists") from e
+            acc[s], oe[s] = T, ET
+    return _runtime.ints_to_words(acc, W).reshape(cells, W), np.array(oe, dtype=np.int32), cnt
 
 
 def _plain(y, N: int) -> np.ndarray:

@@ -243,17 +243,31 @@ class PackedCiphertextBuffer(object):
 
     __rmul__ = __mul__
 
-    def histogram(self, bins, n_bins: int, node=None, n_nodes: int = 1):
+    def histogram(self, bins, n_bins: int, node=None, n_nodes: int = 1, default_bin=0):
         """Histogram of samples encrypted as packed ciphertexts, ONE ciphertext per sample (count == samples * slots:
         g and h of a sample in two slots): (PackedCiphertextBuffer of shape (n_nodes, F, n_bins, slots) with this layout,
         int64 counts of shape (n_nodes, F, n_bins)) from one pai_histogram call, every slot summed per cell at once. The
         bound is this buffer's bound * counts.max(); the counts are taken on the host first, so that OverflowError is
-        raised before any GPU call if it passes the slot. Empty cells decode as 0 in every slot."""
-        from .cipher_buffer import histogram_args, histogram_cells, histogram_words
+        raised before any GPU call if it passes the slot. Empty cells decode as 0 in every slot.
+        Sparse bins (anything that offers .tocsr()) take one pai_histogram_sparse call with default_bin as in
+        CiphertextBuffer.histogram; a packed buffer's exponents are uniform, so the bits are the dense call's."""
+        from .cipher_buffer import (histogram_args, histogram_cells, histogram_sparse_args, histogram_sparse_counts,
+                                    histogram_sparse_words, histogram_words, sparse_csr)
         k, N = self.layout.slots, self.words.shape[0]
         if self.count != N * k:
             raise ValueError(f"histogram: {self.count} values do not fill {N} ciphertexts of {k} slots (one ciphertext "
                              "per sample)")
+        csr = sparse_csr(bins)
+        if csr is not None:
+            # (a default cell is a true subset sum, T_v minus the stored rest, so counts.max() bounds it like any cell)
+            *args, shape = histogram_sparse_args(N, csr, n_bins, node, n_nodes, default_bin)
+            cells = shape[0] * shape[1] * shape[2]
+            cnt = histogram_sparse_counts(*args, shape)[0]
+            bound = self.bound * (int(cnt.max()) if cnt.size else 0)
+            self._check_bound(bound)
+            out, _, _ = histogram_sparse_words(self.public_key, self.words, self._exps(), *args, shape)
+            return (PackedCiphertextBuffer(self.public_key, out, self.layout, cells * k, shape + (k,), False, bound),
+                    cnt.reshape(shape))
         b, nd, shape = histogram_args(N, bins, n_bins, node, n_nodes)
         cells = shape[0] * shape[1] * shape[2]
         cell = histogram_cells(b, shape[2], nd, shape[0])

@@ -191,35 +191,47 @@ def _histogram_operand(x, who: str):
     return pk, words, exps
 
 
-def histogram(x, bins, n_bins, node=None, n_nodes=1):
+def _histogram_cells(pk, words, exps, bins, n_bins, node, n_nodes, default_bin):
+    """(words, exponents, counts, shape) of the histogram's cells: sparse bins (anything that offers .tocsr()) through
+    pai_histogram_sparse, a numpy matrix through pai_histogram."""
+    from .cipher_buffer import histogram_args, histogram_sparse_args, histogram_sparse_words, histogram_words, sparse_csr
+    csr = sparse_csr(bins)
+    if csr is not None:
+        *args, shape = histogram_sparse_args(exps.size, csr, n_bins, node, n_nodes, default_bin)
+        return histogram_sparse_words(pk, words, exps, *args, shape) + (shape,)
+    b, nd, shape = histogram_args(exps.size, bins, n_bins, node, n_nodes)
+    return histogram_words(pk, words, exps, b, shape[2], nd, shape[0]) + (shape,)
+
+
+def histogram(x, bins, n_bins, node=None, n_nodes=1, default_bin=0):
     """Per-cell sums of the encrypted vector x (flat order) over the bin ids bins [N, F] (uint8 / uint16) and an optional
     node id per sample, all features at once: (PaillierArray of shape (n_nodes, F, n_bins), int64 counts of that shape)
     from ONE pai_histogram call, with no index list built (IV_FFS over every feature of a party, the (node, feature, bin)
     sums of gradient boosting). Cell [v, f, b] is the pure ``+`` reduction over the samples with node == v and
     bins[:, f] == b, without the ``0 +`` of Python's sum; a node id outside [0, n_nodes) and a bin id >= n_bins put the
     sample in no cell (of that feature). An empty cell is ciphertext 1 at exponent 0, an unobfuscated encryption of 0.
-    Without a GPU the same runs on Python integers."""
+    Without a GPU the same runs on Python integers.
+    Sparse bins (anything that offers .tocsr()) take ONE pai_histogram_sparse call over the stored entries; every entry
+    that is not stored has bin default_bin (a scalar or one per feature), and the default cell is the node's total minus
+    the feature's other stored entries (``T - S`` of the reference's operators, CiphertextBuffer.histogram)."""
     from .cipher_array import materialize
-    from .cipher_buffer import histogram_args, histogram_words
     pk, words, exps = _histogram_operand(x, "histogram")
-    b, nd, shape = histogram_args(exps.size, bins, n_bins, node, n_nodes)
-    out, oe, cnt = histogram_words(pk, words, exps, b, shape[2], nd, shape[0])
+    out, oe, cnt, shape = _histogram_cells(pk, words, exps, bins, n_bins, node, n_nodes, default_bin)
     oe = np.where(cnt == 0, 0, oe).astype(np.int32)
     return materialize(pk, out, oe, shape, obfuscated=False), cnt.reshape(shape)
 
 
-def histogram_packed(x, bins, n_bins, layout, max_abs, node=None, n_nodes=1):
+def histogram_packed(x, bins, n_bins, layout, max_abs, node=None, n_nodes=1, default_bin=0):
     """The cell sums of histogram as ONE PackedCiphertextBuffer of shape (n_nodes, F, n_bins): one pai_histogram call,
     then one pai_pack_ciphertexts call that folds layout.slots cell sums into each ciphertext; returns (buffer, counts).
     `x` holds integer-valued ciphertexts at the layout's exponent with |value| <= max_abs (the caller's assertion); the
     buffer's bound is counts.max() * ceil(max_abs * 16^exponent), OverflowError before the fold if it passes the slot.
-    Empty cells decode as 0. Without a GPU the same runs on Python integers (small arrays only)."""
-    from .cipher_buffer import histogram_args, histogram_words
+    Empty cells decode as 0. Without a GPU the same runs on Python integers (small arrays only). Sparse bins and
+    default_bin as in histogram; a default cell is a subset sum like any other, so the bound rule is the same."""
     from .packed_buffer import _fold, _slot_bound
     pk, words, exps = _histogram_operand(x, "histogram_packed")
-    b, nd, shape = histogram_args(exps.size, bins, n_bins, node, n_nodes)
     _slot_bound(layout, max_abs, 1)                         # a single value already has to fit
-    out, oe, cnt = histogram_words(pk, words, exps, b, shape[2], nd, shape[0])
+    out, oe, cnt, shape = _histogram_cells(pk, words, exps, bins, n_bins, node, n_nodes, default_bin)
     bound = _slot_bound(layout, max_abs, int(cnt.max()) if cnt.size else 0)
     return _fold(pk, out, np.ascontiguousarray(oe, dtype=np.int32), layout, bound, shape), cnt.reshape(shape)
 

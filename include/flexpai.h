@@ -382,6 +382,35 @@ enum { PAI_BIN_U8 = 0, PAI_BIN_U16 = 1 };
 int pai_histogram(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int bin_dtype, const void* bins,
                   size_t F, size_t bin_stride, const int32_t* node, size_t nodes, size_t B, uint32_t* ct_out,
                   int32_t* exp_out, int64_t* count_out);
+/* pai_histogram over a sparse bin matrix, at a cost that follows the stored entries. The matrix is CSR: indptr holds
+ * N + 1 offsets that start at 0 and never decrease, indices the feature of every stored entry (inside [0, F), strictly
+ * increasing inside a row), data its bin id (PAI_BIN_U8 / PAI_BIN_U16). Every (i, f) that is not stored has bin
+ * default_bin[f]; a default_bin[f] outside [0, B) puts the unstored entries of that feature in no cell. A stored bin id
+ * >= B is a missing value, in no cell. node, nodes, B, the cell index (v F + f) B + b, the treatment of node ids outside
+ * [0, nodes), the empty cell (ciphertext 1, INT32_MIN) and count_out are those of pai_histogram. N F is not limited.
+ *   With z = default_bin[f]: a cell (v, f, b), b != z, holds exactly what pai_histogram gives on the densified matrix.
+ *   The default cell (v, f, z) is T_v - S_{v,f}: T_v the sum of all samples of node v (pai_segment_add, once per
+ *   call), S_{v,f} the sum of the stored entries of (v, f) whose bin is not z, stored missing values included
+ *   (pai_segment_add), and `-` the ciphertext difference T_v * invert(S)^(16^(E_T - E_S)) mod n^2 of pai_mul by -1 and
+ *   pai_add, bit for bit. Its exponent is E_T, the node's largest, and its ciphertext is the dense cell's raised to
+ *   16^(E_T - E_cell): the same plaintext, and THE SAME BITS AS pai_histogram WHENEVER THE EXPONENTS OF A NODE ARE
+ *   UNIFORM (int64 labels, fixed-exponent g / h, every packed buffer). Where nothing but default entries is stored for
+ *   (v, f) the cell is T_v's bits and nothing is inverted; where count(v) equals the stored non-default entries it is
+ *   the empty cell. count_out of a default cell is count(v) minus the stored non-default entries of (v, f). An S without
+ *   inverse mod n^2 ends the call with PAI_ERR_NOINV. The output is not re-randomised; the call needs the public key
+ *   only. Runs, feature blocks and the host variant's chunks change no bit, the default cells included: the
+ *   subtraction happens once, on the combined slot sums.
+ *   PAI_ERR_ARG before any ciphertext work: a null pointer, F = 0, B = 0 or B above the type's range, nodes = 0, nodes F B
+ *   above 2^24, N or nnz at or above 2^31, an indptr that decreases or does not start at 0, an index outside [0, F), a row
+ *   whose indices are not strictly increasing (the last two are found on the device by the counting pass).
+ * Kernels (csrc/kernels_shist.hpp): the counting and the scattering pass run over tiles of stored entries, with the
+ * tile's touched slots in an LDS hash table; the member lists then take pai_histogram's path (k_hist_acc, segmented
+ * add). The _dev variant (device pointers for everything) synchronises `stream` to read nnz, to read the counts, per
+ * level of the segmented add and for the batch inversion. */
+int pai_histogram_sparse(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, const int64_t* indptr,
+                         const int32_t* indices, int bin_dtype, const void* data, size_t F, const int32_t* default_bin,
+                         const int32_t* node, size_t nodes, size_t B, uint32_t* ct_out, int32_t* exp_out,
+                         int64_t* count_out);
 /* Prefix sums of a ciphertext array along one axis. The array is C-contiguous [outer][L][inner] (element (o, j, i) at
  * index (o L + j) inner + i, numpy's axis convention: no caller transposes). For every (o, i) and every j
  *     E_j   = max over j' <= j of e_j'                               (entries with exponent INT32_MIN skipped)
@@ -453,6 +482,10 @@ int pai_segment_dot_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp
 int pai_histogram_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int bin_dtype,
                       const void* d_bins, size_t F, size_t bin_stride, const int32_t* d_node, size_t nodes, size_t B,
                       uint32_t* d_out, int32_t* d_exp_out, int64_t* d_count_out, void* stream);
+int pai_histogram_sparse_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_indptr,
+                             const int32_t* d_indices, int bin_dtype, const void* d_data, size_t F,
+                             const int32_t* d_default_bin, const int32_t* d_node, size_t nodes, size_t B,
+                             uint32_t* d_out, int32_t* d_exp_out, int64_t* d_count_out, void* stream);
 int pai_cumsum_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t outer, size_t L, size_t inner,
                    int flags, uint32_t* d_out, int32_t* d_exp_out, void* stream);
 
