@@ -59,6 +59,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_scan.hpp"
 #include "engine_obf.hpp"
 #include "engine_pack.hpp"
+#include "engine_res.hpp"
 #include "engine_pool.hpp"
 #include "engine_crtw.hpp"
 #include "engine_pe1.hpp"
@@ -256,6 +257,9 @@ struct pai_ctx {
   size_t mul_bytes = 0;
   void* d_seg = nullptr;        // segmented sums: gather rows and the partial sums of each level
   size_t seg_bytes = 0;
+  void* d_take = nullptr;       // pai_take_dev's row index; pai_check_below_dev's result word
+  size_t take_bytes = 0;
+  uint32_t* d_nsq32 = nullptr;  // n^2 in 32-bit words (pai_check_below_dev), uploaded at its first call
   void* d_plain = nullptr;      // ciphertext + plaintext: the two k_add operands and their exponents
   size_t plain_bytes = 0;
   // re-randomisation (pai_obfuscate_dev): the zero plaintexts, scratch exponents and statuses of the encryption that
@@ -449,6 +453,7 @@ pai_ctx::~pai_ctx() {
   if (pool.rows) (void)hipFree(pool.rows);
   if (pool.d_rho) (void)hipFree(pool.d_rho);
   if (d_seg) (void)hipFree(d_seg);
+  if (d_take) (void)hipFree(d_take);
   if (d_addplan) (void)hipFree(d_addplan);
 }
 
@@ -6374,6 +6379,64 @@ int pai_pack_ciphertexts(pai_ctx* c, const uint32_t* ct, const int32_t* exp, siz
   HIPCHK(hipMemcpyAsync(ct_out, dout, C * W * 4, hipMemcpyDeviceToHost, sc));
   if (status_out) HIPCHK(hipMemcpyAsync(status_out, dst, N * 4, hipMemcpyDeviceToHost, sc));
   HIPCHK(hipStreamSynchronize(sc));
+  return 0;
+}
+
+// ------------------------------------------------------------------ device-resident buffers (engine_res.hip)
+namespace fpai {
+hipError_t shared_dev_malloc(void** p, size_t bytes) { return dev_malloc(p, bytes); }
+void shared_par_copy(void* dst, const void* src, size_t bytes) { par_copy(dst, src, bytes); }
+}  // namespace fpai
+
+// Gather of rows by a host index (kernels_res.hpp k_take). Every argument is checked before the first launch, so no
+// index formed from data addresses outside the input.
+int pai_take_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* index, size_t M,
+                 uint32_t* d_ct_out, int32_t* d_exp_out, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (M == 0) return 0;
+  if (!index || !d_ct_out || !d_exp_out || (N > 0 && (!d_ct || !d_exp)))
+    return fail(PAI_ERR_ARG, "pai_take_dev: null pointer");
+  if (N >= ((size_t)1 << 40) || M >= ((size_t)1 << 40)) return fail(PAI_ERR_ARG, "pai_take_dev: too many rows");
+  for (size_t j = 0; j < M; ++j)
+    if (index[j] < -1 || index[j] >= (int64_t)N) return fail(PAI_ERR_ARG, "pai_take_dev: index out of range");
+  const size_t W = c->ct_words;
+  if (ranges_overlap(d_ct, N * W * 4, d_ct_out, M * W * 4) || ranges_overlap(d_exp, N * 4, d_exp_out, M * 4) ||
+      ranges_overlap(d_ct, N * W * 4, d_exp_out, M * 4) || ranges_overlap(d_exp, N * 4, d_ct_out, M * W * 4) ||
+      ranges_overlap(d_ct_out, M * W * 4, d_exp_out, M * 4))
+    return fail(PAI_ERR_ARG, "pai_take_dev: the output overlaps the input");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  int rc = ensure_buf(&c->d_take, &c->take_bytes, std::max<size_t>(M * 8, 16));
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(c->d_take, index, M * 8, hipMemcpyHostToDevice, st));
+  TakeParams p{d_ct, d_exp, (const long long*)c->d_take, (long long)M, (int)W, d_ct_out, d_exp_out};
+  HIPCHK(take_launch(p, c->cus, st));
+  HIPCHK(hipStreamSynchronize(st));   // the index is the caller's host memory, and d_take serves the next call
+  return 0;
+}
+
+// The wire-ingest range check on the device (k_check_below): one read-back of one word.
+int pai_check_below_dev(pai_ctx* c, const uint32_t* d_ct, size_t N, int64_t* first_bad, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (!first_bad) return fail(PAI_ERR_ARG, "pai_check_below_dev: null pointer");
+  *first_bad = -1;
+  if (N == 0) return 0;
+  if (!d_ct) return fail(PAI_ERR_ARG, "pai_check_below_dev: null pointer");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (!c->d_nsq32 && (rc = upload(c, c->N.words(c->ct_words), &c->d_nsq32))) return rc;
+  if ((rc = ensure_buf(&c->d_take, &c->take_bytes, 16))) return rc;
+  unsigned long long* d_first = (unsigned long long*)c->d_take;
+  HIPCHK(hipMemsetAsync(d_first, 0xFF, 8, st));
+  CheckBelowParams p{d_ct, (long long)N, c->ct_words, c->d_nsq32, d_first};
+  HIPCHK(check_below_launch(p, c->cus, st));
+  unsigned long long first = 0;
+  HIPCHK(hipMemcpyAsync(&first, d_first, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (first != ~0ull) *first_bad = (int64_t)first;
   return 0;
 }
 

@@ -58,7 +58,10 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_segment_dot", "pai_segment_dot_dev", "pai_histogram", "pai_histogram_dev",
             "pai_histogram_sparse", "pai_histogram_sparse_dev",
             "pai_cumsum", "pai_cumsum_dev",
-            "pai_pool_reserve", "pai_pool_fill", "pai_pool_fill_dev", "pai_pool_put", "pai_pool_put_dev", "pai_pool_info")
+            "pai_pool_reserve", "pai_pool_fill", "pai_pool_fill_dev", "pai_pool_put", "pai_pool_put_dev", "pai_pool_info",
+            "pai_dev_alloc", "pai_dev_free", "pai_dev_upload", "pai_dev_download", "pai_dev_copy", "pai_dev_io_stats",
+            "pai_dev_release_staging", "pai_take_dev", "pai_check_below_dev")
+RESIDENT = EXPORTED[-9:]      # device-resident buffers (include/flexpai.h)
 PAI_COMM_ID_BYTES = 128
 
 _lib = None
@@ -154,13 +157,34 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_prime_test.argtypes = [I, I, P, S, S, P, S, P]
         lib.pai_debug_prime_sieve.argtypes = [I, P, S, ctypes.c_uint32, P, S, P]
         lib.pai_release_table_cache.restype = None
+        # (a library built from an earlier commit, loaded next to this one by the A/B tools, has no resident buffers)
+        resident = hasattr(lib, "pai_dev_alloc")
+        if resident:
+            lib.pai_dev_alloc.argtypes = [I, S, ctypes.POINTER(ctypes.c_void_p)]
+            lib.pai_dev_free.argtypes = [I, P]
+            lib.pai_dev_upload.argtypes = [I, P, P, S]
+            lib.pai_dev_download.argtypes = [I, P, P, S]
+            lib.pai_dev_copy.argtypes = [I, P, P, S]
+            lib.pai_dev_io_stats.argtypes = [P, P]
+            lib.pai_dev_release_staging.argtypes = []
+            lib.pai_take_dev.argtypes = [P, P, P, S, P, S, P, P, P]
+            lib.pai_check_below_dev.argtypes = [P, P, S, P, P]
         for name in EXPORTED:
+            if not resident and name in RESIDENT:
+                continue
             if name not in ("pai_ctx_destroy", "pai_last_error", "pai_comm_destroy", "pai_release_table_cache"):
                 getattr(lib, name).restype = ctypes.c_int
         _libs[path] = lib
         if path == LIB_PATH:
             _lib = lib
         return lib
+
+
+def release_staging() -> None:
+    """Give the pinned staging slots, copy streams and events of the device-buffer transfers back now
+    (pai_dev_release_staging: up to 128 MiB of pinned host memory per device; the next transfer makes them again)."""
+    lib = load_library()
+    _check(lib.pai_dev_release_staging(), lib)
 
 
 def release_table_cache() -> None:
@@ -262,6 +286,91 @@ def device_mem_info(device: int = 0):
     return fr.value, tot.value
 
 
+class DeviceMem:
+    """A block of device memory of the library (pai_dev_alloc; include/flexpai.h, "Device-resident ciphertext
+    buffers"): owned by the device, not by a context. free() -- and the finaliser -- wait for the device's queued work
+    before the block goes back. DeviceMem.wrap(ptr, nbytes, device, owner) names memory somebody else owns (a torch
+    tensor's data_ptr()): it keeps `owner` alive and never frees."""
+    __slots__ = ("ptr", "nbytes", "device", "owner", "_lib")
+
+    def __init__(self, nbytes: int, device: int = 0, lib=None):
+        self._lib = lib or load_library()
+        self.nbytes, self.device, self.owner = int(nbytes), int(device), None
+        p = ctypes.c_void_p()
+        _check(self._lib.pai_dev_alloc(self.device, self.nbytes, ctypes.byref(p)), self._lib)
+        global _runtime_started
+        _runtime_started = True
+        self.ptr = p.value or 0
+
+    @classmethod
+    def wrap(cls, ptr: int, nbytes: int, device: int = 0, owner=None) -> "DeviceMem":
+        m = object.__new__(cls)
+        m._lib, m.ptr, m.nbytes, m.device, m.owner = None, int(ptr), int(nbytes), int(device), owner
+        return m
+
+    def at(self, offset: int) -> int:
+        return self.ptr + int(offset)
+
+    def upload(self, a: np.ndarray, offset: int = 0) -> "DeviceMem":
+        """Host array -> this block at byte `offset` (pai_dev_upload: pinned staging, complete on return)."""
+        a = np.ascontiguousarray(a)
+        if offset < 0 or offset + a.nbytes > self.nbytes:
+            raise ValueError("upload: the array does not fit the device block")
+        lib = self._lib or load_library()
+        if a.nbytes:
+            _check(lib.pai_dev_upload(self.device, self.ptr + offset, _ptr(a), a.nbytes), lib)
+        return self
+
+    def download(self, dtype, count: int, offset: int = 0) -> np.ndarray:
+        """`count` elements of `dtype` from byte `offset` (pai_dev_download; waits for the device's queued work)."""
+        out = np.empty(int(count), dtype=dtype)
+        if offset < 0 or offset + out.nbytes > self.nbytes:
+            raise ValueError("download: the range lies outside the device block")
+        lib = self._lib or load_library()
+        if out.nbytes:
+            _check(lib.pai_dev_download(self.device, _ptr(out), self.ptr + offset, out.nbytes), lib)
+        return out
+
+    def copy_from(self, src: "DeviceMem", nbytes: int, offset: int = 0, src_offset: int = 0) -> "DeviceMem":
+        """Device-to-device copy (pai_dev_copy) of `nbytes` from src at src_offset to this block at offset."""
+        if min(offset, src_offset, nbytes) < 0 or offset + nbytes > self.nbytes or src_offset + nbytes > src.nbytes:
+            raise ValueError("copy_from: the range lies outside a device block")
+        if src.device != self.device:
+            raise ValueError("copy_from: the blocks are on different devices")
+        lib = self._lib or load_library()
+        if nbytes:
+            _check(lib.pai_dev_copy(self.device, self.ptr + offset, src.ptr + src_offset, int(nbytes)), lib)
+        return self
+
+    def free(self) -> None:
+        if self._lib is not None and self.ptr:
+            lib, p = self._lib, self.ptr
+            self.ptr = 0
+            _check(lib.pai_dev_free(self.device, p), lib)
+        self.ptr, self.owner = 0, None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:   # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def device_upload(a: np.ndarray, device: int = 0) -> DeviceMem:
+    """A fresh device block holding the host array `a`."""
+    a = np.ascontiguousarray(a)
+    return DeviceMem(a.nbytes, device).upload(a)
+
+
+def dev_io_stats(lib=None) -> Tuple[int, int]:
+    """(host-to-device, device-to-host) bytes moved by pai_dev_upload / pai_dev_download in this process (per loaded
+    build of the library)."""
+    lib = lib or load_library()
+    up, down = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(lib.pai_dev_io_stats(ctypes.byref(up), ctypes.byref(down)), lib)
+    return int(up.value), int(down.value)
+
+
 class Comm:
     """RCCL communicator of the C ABI's shard all-gather (pai_comm_*): one per rank, one process per GPU.
     Rank 0 makes the id (Comm.unique_id()) and passes it to the others over any channel."""
@@ -326,6 +435,7 @@ class Context:
         """lib: another build of the C ABI (load_library(XCHECK_LIB_PATH) in the cross-check tests)."""
         self.lib = lib or load_library()
         self.n = n
+        self.device = int(device)
         nbytes = (n.bit_length() + 7) // 8
         buf = int_to_le(n, nbytes)
         h = ctypes.c_void_p()
@@ -590,6 +700,24 @@ class Context:
         if ct.dtype != np.uint32 or ct.shape != (N, self.ct_words) or exp.shape != (N,):
             raise ValueError(f"ciphertext buffer shape {ct.shape} / exponents {exp.shape} do not match "
                              f"({N}, {self.ct_words})")
+
+    # ----------------------------------------------------------------- device-pointer ops (device_buffer.py)
+    def dev_call(self, name: str, *args) -> None:
+        """The *_dev entry point `name` on device pointers (ints, DeviceMem.at()), on the null stream; asynchronous as
+        include/flexpai.h states for that entry point. The callers (device_buffer.py) own the shapes."""
+        self.calls[name] += 1
+        self._chk(getattr(self.lib, name)(self._h, *args, None))
+
+    def take_dev(self, d_ct: int, d_exp: int, N: int, index: np.ndarray, d_ct_out: int, d_exp_out: int) -> None:
+        """pai_take_dev: out[j] = in[index[j]] (host int64 index; -1: ciphertext 1, exponent INT32_MIN)."""
+        index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+        self.dev_call("pai_take_dev", d_ct, d_exp, int(N), _ptr(index), index.size, d_ct_out, d_exp_out)
+
+    def check_below_dev(self, d_ct: int, N: int) -> int:
+        """pai_check_below_dev: the smallest i with ct[i] >= n^2, or -1."""
+        first = ctypes.c_int64(-1)
+        self.dev_call("pai_check_below_dev", d_ct, int(N), ctypes.byref(first))
+        return int(first.value)
 
     # ----------------------------------------------------------------- host-buffer ops
     def encrypt(self, x: np.ndarray, exp_mode: int = PAI_EXP_AUTO, fixed_exp: int = 0,

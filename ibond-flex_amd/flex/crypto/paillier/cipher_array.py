@@ -642,8 +642,8 @@ def to_wire(arr, be_secure: bool = False) -> bytes:
     bulk format. be_secure=True first re-randomises, in place and in one GPU call, every element that is not yet
     obfuscated (the array form of ``ciphertext(be_secure=True)``, encrypted_number.py:50-56), so every shipped flag
     is 1; the default ships the ciphertexts as they are."""
-    from .cipher_buffer import CiphertextBuffer
-    if isinstance(arr, CiphertextBuffer):
+    from .cipher_buffer import BufferOps
+    if isinstance(arr, BufferOps):                      # a CiphertextBuffer or a DeviceCiphertextBuffer
         return arr.to_wire(be_secure)
     A, pk = _encrypted_operand(arr)
     if A is None:
@@ -674,11 +674,15 @@ def _rows_below(words: np.ndarray, limit: int) -> bool:
     return True
 
 
-def from_wire(buf, public_key=None, lazy: bool = False):
+def from_wire(buf, public_key=None, lazy: bool = False, device: bool = False):
     """Inverse of to_wire. `public_key` (optional) must match the key in the buffer (ValueError
     otherwise, like encrypted_number.py:169-170); without it a PaillierPublicKey is rebuilt from n.
     lazy=True returns a CiphertextBuffer (cipher_buffer.py): the validated words and exponents, no
-    Python object per element."""
+    Python object per element. lazy=True, device=True returns a DeviceCiphertextBuffer (device_buffer.py): the words
+    go to the GPU in one upload, straight from `buf`, and c < n^2 is checked there (the same ValueError);
+    RuntimeError without a GPU."""
+    if device and not lazy:
+        raise ValueError("from_wire: device=True needs lazy=True")
     from .keypair import PaillierPublicKey
     mv = memoryview(buf).cast("B")
     bad = ValueError("corrupted ciphertext array")
@@ -701,11 +705,20 @@ def from_wire(buf, public_key=None, lazy: bool = False):
         raise ValueError("corrupted ciphertext array (length mismatch)")
     exps = np.frombuffer(mv, "<i4", N, o).astype(np.int32); o += 4 * N
     obf = np.frombuffer(mv, np.uint8, N, o).copy(); o += N
-    words = np.frombuffer(mv, "<u4", N * W, o).reshape(N, W).copy(); o += 4 * N * W
+    words = np.frombuffer(mv, "<u4", N * W, o).reshape(N, W); o += 4 * N * W
     if public_key is None:
         public_key = PaillierPublicKey(n)
     elif public_key.n != n:
         raise ValueError("ciphertext array was encrypted under a different public key")
+    if device:
+        from . import _runtime
+        from .cipher_buffer import need_gpu
+        from .device_buffer import DeviceCiphertextBuffer, upload_checked
+        need_gpu()
+        dw = upload_checked(public_key, words, _runtime.context(public_key).device,
+                            "corrupted ciphertext array (ciphertext >= n^2)")
+        return DeviceCiphertextBuffer(public_key, dw, exps, obf, shape)
+    words = words.copy()
     if not _rows_below(words, public_key.nsquare):
         raise ValueError("corrupted ciphertext array (ciphertext >= n^2)")
     if lazy:

@@ -15,7 +15,9 @@ as numpy arrays, and runs the array operators straight on the GPU:
 
 Results are bit-identical to the per-object operators (same kernels as PaillierArray's). Conversions:
 CiphertextBuffer.from_array(PaillierArray or object ndarray), .to_array() -> PaillierArray,
-PaillierEncryptor.encrypt_to_buffer(ndarray).
+PaillierEncryptor.encrypt_to_buffer(ndarray). buf[key], buf.take, buf.T and concatenate select like numpy.
+.to_device() gives a DeviceCiphertextBuffer (device_buffer.py): the same operators with the words kept on the GPU
+between calls.
 """
 from __future__ import annotations
 
@@ -26,7 +28,127 @@ import numpy as np
 from .encrypted_number import PaillierEncryptedNumber
 
 
-class CiphertextBuffer(object):
+def need_gpu() -> None:
+    from . import _runtime
+    if not _runtime.gpu_available():
+        raise RuntimeError("CiphertextBuffer operators need a GPU (use .to_array() for the host operators)")
+
+
+def _on_device(x) -> bool:
+    from .device_buffer import DeviceCiphertextBuffer
+    return isinstance(x, DeviceCiphertextBuffer)
+
+
+class BufferOps(object):
+    """What CiphertextBuffer and DeviceCiphertextBuffer (device_buffer.py) share: the operators that are written in
+    terms of other operators, and indexing. A subclass provides public_key, shape, size, _coerce, _add_plain, __mul__,
+    segment_dot, _dense_dot and _gather."""
+    __slots__ = ()
+
+    def __len__(self) -> int:
+        return self.shape[0] if self.shape else 1
+
+    def _broadcast(self, number) -> "CiphertextBuffer":
+        return CiphertextBuffer.from_array(np.full(self.shape, number, dtype=object))
+
+    def __add__(self, other):
+        if _on_device(other) and not _on_device(self):
+            return NotImplemented                               # other.__radd__: the sum stays on the device
+        b = self._coerce(other)
+        if b is not None:
+            return add_buffers([self, b])
+        if isinstance(other, PaillierEncryptedNumber):
+            return add_buffers([self, self._coerce(self._broadcast(other))])
+        return self._add_plain(other)
+
+    __radd__ = __add__
+
+    def __sub__(self, other):
+        # self + (other * -1), encrypted_number.py:74-75: an encrypted operand is scaled by -1 on the GPU
+        # (k_mul with the batch inversion) and added by k_add; a plain one is negated and added as plain
+        if _on_device(other) and not _on_device(self):
+            return NotImplemented                               # other.__rsub__
+        if isinstance(other, PaillierEncryptedNumber):
+            other = self._broadcast(other)
+        b = self._coerce(other)
+        if b is not None:
+            return add_buffers([self, b * -1])
+        return self._add_plain(_plain(other, self.size) * -1)
+
+    def __rsub__(self, other):
+        if isinstance(other, PaillierEncryptedNumber):
+            other = self._broadcast(other)
+        b = self._coerce(other)
+        if b is not None:
+            return add_buffers([b, self * -1])
+        return (self * -1)._add_plain(other)                    # other + (self * -1), encrypted_number.py:77-78
+
+    def __rmul__(self, y):
+        return self * y
+
+    def __truediv__(self, s):
+        return self * (1 / s)
+
+    def _dot_sparse(self, csc):
+        indptr, indices, data, (K, d) = csc
+        if len(self.shape) not in (1, 2) or K != self.shape[-1]:
+            raise ValueError(f"dot: shapes {self.shape} and {(K, d)} not aligned")
+        m = self.shape[0] if len(self.shape) == 2 else 1
+        idx, off, w = sparse_segments(indptr, indices, data, m, K, d)
+        out = self.segment_dot(idx, off, w)
+        return out.reshape((m, d) if len(self.shape) == 2 else (d,))
+
+    def dot(self, b):
+        """(K,) or (m, K) encrypted @ (K,) or (K, d) plain, numpy semantics (he_otp_lr_ft1/train.py:160). A sparse
+        (K, d) matrix (anything that offers .tocsc()) runs as segment_dot over its stored entries, explicit zeros
+        included: columns are the segments, row i of an (m, K) buffer offsets the indices by i K."""
+        csc = sparse_csc(b)
+        if csc is not None:
+            return self._dot_sparse(csc)
+        x = np.asarray(b)
+        if len(self.shape) not in (1, 2) or x.ndim not in (1, 2) or x.shape[0] != self.shape[-1]:
+            raise ValueError(f"dot: shapes {self.shape} and {x.shape} not aligned")
+        from .cipher_array import _plain_array
+        xs = _plain_array(x)
+        if xs is None:
+            raise TypeError(f"dot: unsupported operand dtype {x.dtype}")
+        m = self.shape[0] if len(self.shape) == 2 else 1
+        d = x.shape[1] if x.ndim == 2 else 1
+        shape = tuple(([m] if len(self.shape) == 2 else []) + ([d] if x.ndim == 2 else []))
+        return self._dense_dot(m, np.ascontiguousarray(xs).reshape(-1), d, shape if shape else (1,))
+
+    def __matmul__(self, b):
+        return self.dot(b)
+
+    # ---------------------------------------------------------------- indexing (numpy semantics)
+    def _positions(self) -> np.ndarray:
+        return np.arange(self.size, dtype=np.int64).reshape(self.shape)
+
+    def _select(self, idx) -> "CiphertextBuffer":
+        idx = np.asarray(idx, dtype=np.int64)
+        return self._gather(np.ascontiguousarray(idx).reshape(-1), idx.shape)
+
+    def __getitem__(self, key):
+        """buf[key] with numpy's rules (ints, slices, integer arrays, boolean masks, ... and None): the elements that
+        np.arange(size).reshape(shape)[key] names, in that shape. One selected element is a buffer of shape (), not a
+        scalar. The obfuscation flags travel with their elements."""
+        return self._select(self._positions()[key])
+
+    def take(self, indices, axis=None):
+        """np.take(array, indices, axis) over the ciphertexts."""
+        return self._select(np.take(self._positions(), indices, axis=axis))
+
+    def transpose(self, *axes):
+        """np.transpose over the ciphertexts (a copy: both buffer classes keep their elements C-contiguous)."""
+        axes = axes[0] if len(axes) == 1 and (axes[0] is None or isinstance(axes[0], (tuple, list))) else (axes or None)
+        return self._select(np.transpose(self._positions(), axes))
+
+    @property
+    def T(self):
+        return self.transpose()
+
+
+class CiphertextBuffer(BufferOps):
     __slots__ = ("public_key", "words", "exps", "obfuscated", "shape")
 
     def __init__(self, public_key, words: np.ndarray, exps: np.ndarray, obfuscated=None, shape=None):
@@ -96,16 +218,12 @@ class CiphertextBuffer(object):
     def size(self) -> int:
         return self.exps.size
 
-    def __len__(self) -> int:
-        return self.shape[0] if self.shape else 1
-
     def __repr__(self) -> str:
         return f"CiphertextBuffer(shape={self.shape}, key_bits={self.public_key.n.bit_length()})"
 
     def _ctx(self):
         from . import _runtime
-        if not _runtime.gpu_available():
-            raise RuntimeError("CiphertextBuffer operators need a GPU (use .to_array() for the host operators)")
+        need_gpu()
         return _runtime.context(self.public_key)
 
     def _like(self, words, exps, obfuscated=0, shape=None) -> "CiphertextBuffer":
@@ -125,31 +243,6 @@ class CiphertextBuffer(object):
         return b
 
     # ---------------------------------------------------------------- operators (GPU)
-    def __add__(self, other):
-        b = self._coerce(other)
-        if b is not None:
-            return add_buffers([self, b])
-        if isinstance(other, PaillierEncryptedNumber):
-            return add_buffers([self, CiphertextBuffer.from_array(np.full(self.shape, other, dtype=object))])
-        return self._add_plain(other)
-
-    __radd__ = __add__
-
-    def __sub__(self, other):
-        # self + (other * -1), encrypted_number.py:74-75: an encrypted operand is scaled by -1 on the GPU
-        # (k_mul with the batch inversion) and added by k_add; a plain one is negated and added as plain
-        if isinstance(other, PaillierEncryptedNumber):
-            other = CiphertextBuffer.from_array(np.full(self.shape, other, dtype=object))
-        b = self._coerce(other)
-        if b is not None:
-            return add_buffers([self, b * -1])
-        return self._add_plain(_plain(other, self.size) * -1)
-
-    def __rsub__(self, other):
-        if isinstance(other, PaillierEncryptedNumber):
-            return CiphertextBuffer.from_array(np.full(self.shape, other, dtype=object)) - self
-        return (self * -1)._add_plain(other)                    # other + (self * -1), encrypted_number.py:77-78
-
     def _add_plain(self, y):
         x = _plain(y, self.size)
         out, oe, st = self._ctx().add_plain(self.words, self.exps, x)
@@ -172,11 +265,6 @@ class CiphertextBuffer(object):
         out, oe, _ = self._ctx().mul(self.words, self.exps, _plain(y, self.size))
         return self._like(out, oe)
 
-    __rmul__ = __mul__
-
-    def __truediv__(self, s):
-        return self * (1 / s)
-
     def segment_dot(self, index, seg_off, weights) -> "CiphertextBuffer":
         """Segmented weighted sums, shape (nseg,): out[s] = sum over t in [seg_off[s], seg_off[s+1]) of
         self[index[t]] * weights[t] (flat indices; pai_segment_dot, one call). Each term is the reference's __mul__, each
@@ -186,36 +274,17 @@ class CiphertextBuffer(object):
         out, oe = segment_dot_words(self.public_key, self.words, self.exps, idx, off, w)
         return self._like(out, oe, 0, (off.size - 1,))
 
-    def _dot_sparse(self, csc):
-        indptr, indices, data, (K, d) = csc
-        if len(self.shape) not in (1, 2) or K != self.shape[-1]:
-            raise ValueError(f"dot: shapes {self.shape} and {(K, d)} not aligned")
-        m = self.shape[0] if len(self.shape) == 2 else 1
-        idx, off, w = sparse_segments(indptr, indices, data, m, K, d)
-        out = self.segment_dot(idx, off, w)
-        return out.reshape((m, d) if len(self.shape) == 2 else (d,))
+    def _dense_dot(self, m: int, xs: np.ndarray, d: int, shape):
+        out, oe = self._ctx().matmul(self.words, self.exps, m, self.shape[-1], xs, d)
+        return self._like(out, oe, 0, shape)
 
-    def dot(self, b):
-        """(K,) or (m, K) encrypted @ (K,) or (K, d) plain, numpy semantics (he_otp_lr_ft1/train.py:160). A sparse
-        (K, d) matrix (anything that offers .tocsc()) runs as segment_dot over its stored entries, explicit zeros
-        included: columns are the segments, row i of an (m, K) buffer offsets the indices by i K."""
-        csc = sparse_csc(b)
-        if csc is not None:
-            return self._dot_sparse(csc)
-        x = np.asarray(b)
-        if len(self.shape) not in (1, 2) or x.ndim not in (1, 2) or x.shape[0] != self.shape[-1]:
-            raise ValueError(f"dot: shapes {self.shape} and {x.shape} not aligned")
-        from .cipher_array import _plain_array
-        xs = _plain_array(x)
-        if xs is None:
-            raise TypeError(f"dot: unsupported operand dtype {x.dtype}")
-        m = self.shape[0] if len(self.shape) == 2 else 1
-        d = x.shape[1] if x.ndim == 2 else 1
-        out, oe = self._ctx().matmul(self.words, self.exps, m, self.shape[-1], np.ascontiguousarray(xs).reshape(-1), d)
-        shape = tuple(([m] if len(self.shape) == 2 else []) + ([d] if x.ndim == 2 else []))
-        return self._like(out, oe, 0, shape if shape else (1,))
+    def _gather(self, idx: np.ndarray, shape):
+        return CiphertextBuffer(self.public_key, self.words[idx], self.exps[idx], self.obfuscated[idx], shape)
 
-    __matmul__ = dot
+    def to_device(self):
+        """The same ciphertexts as a DeviceCiphertextBuffer (device_buffer.py): one upload; RuntimeError without a GPU."""
+        from .device_buffer import DeviceCiphertextBuffer
+        return DeviceCiphertextBuffer.from_host(self)
 
     def histogram(self, bins, n_bins: int, node=None, n_nodes: int = 1, default_bin=0):
         """Per-cell sums of these N ciphertexts (flat order) over the bin ids bins [N, F] (uint8 / uint16) and an optional
@@ -278,6 +347,9 @@ def add_buffers(bufs: Sequence[CiphertextBuffer]) -> CiphertextBuffer:
     bufs = list(bufs)
     if not bufs:
         raise ValueError("add_buffers needs at least one buffer")
+    if any(_on_device(b) for b in bufs):       # one device buffer keeps the sum on the device
+        from .device_buffer import add_device_buffers
+        return add_device_buffers(bufs)
     a = bufs[0]
     for b in bufs[1:]:
         a._coerce(b)
@@ -285,6 +357,26 @@ def add_buffers(bufs: Sequence[CiphertextBuffer]) -> CiphertextBuffer:
         return a
     out, oe = a._ctx().add([b.words for b in bufs], [b.exps for b in bufs])
     return a._like(out, oe)
+
+
+def concatenate(bufs: Sequence[CiphertextBuffer], axis: int = 0):
+    """np.concatenate over buffers of one key: a CiphertextBuffer, or a DeviceCiphertextBuffer when any operand is one
+    (device-to-device copies and one pai_take_dev; host operands are uploaded for the call)."""
+    bufs = list(bufs)
+    if not bufs:
+        raise ValueError("need at least one buffer to concatenate")
+    for b in bufs[1:]:
+        if b.public_key != bufs[0].public_key:
+            raise ValueError("add two numbers have different public key!")
+    starts = np.cumsum([0] + [b.size for b in bufs[:-1]])
+    idx = np.concatenate([b._positions() + int(o) for b, o in zip(bufs, starts)], axis=axis)
+    if any(_on_device(b) for b in bufs):
+        from .device_buffer import stack_device_buffers
+        return stack_device_buffers(bufs)._select(idx)
+    a = bufs[0]
+    flat = CiphertextBuffer(a.public_key, np.concatenate([b.words for b in bufs]), np.concatenate([b.exps for b in bufs]),
+                            np.concatenate([b.obfuscated for b in bufs]))
+    return flat._select(idx)
 
 
 def sparse_csc(b):
@@ -373,6 +465,16 @@ def segment_dot_words(pk, words, exps, idx, off, w):
 EMPTY_EXP = -(1 << 31)      # the exponent of an empty cell or segment (ciphertext 1)
 
 
+def _device_words(words) -> bool:
+    """True for a device holder (device_buffer.DeviceWords) in the place of numpy words: histogram_words,
+    histogram_sparse_words and cumsum_words then run the *_dev entry points and return (DeviceWords, exponents as a
+    device block[, counts on the host]), which is how both buffer classes and the packed buffer stay resident."""
+    if isinstance(words, np.ndarray):
+        return False
+    from .device_buffer import DeviceWords
+    return isinstance(words, DeviceWords)
+
+
 def axis_split(shape, axis):
     """(outer, L, inner) of a C-contiguous array of `shape` scanned or reduced along `axis`."""
     if isinstance(axis, (bool, np.bool_)) or not isinstance(axis, (int, np.integer)):
@@ -389,6 +491,9 @@ def cumsum_words(pk, words, exps, outer: int, L: int, inner: int, reverse: bool 
     Python integers without one. Entries with exponent EMPTY_EXP are skipped; a prefix of such entries only is
     ciphertext 1 with exponent EMPTY_EXP."""
     from . import _runtime
+    if _device_words(words):
+        from . import device_buffer
+        return device_buffer.cumsum_dev(pk, words, exps, outer, L, inner, reverse)
     N, W = outer * L * inner, words.shape[1]
     if N != np.asarray(exps).size:
         raise ValueError("cumsum: outer * L * inner must be the number of ciphertexts")
@@ -484,6 +589,9 @@ def histogram_words(pk, words, exps, bins, n_bins: int, node, n_nodes: int):
     """(words [cells, W], exponents [cells], counts int64 [cells]) of the histogram over checked arguments: pai_histogram
     on the GPU, products of Python integers without one. Empty cells: ciphertext 1, exponent EMPTY_EXP."""
     from . import _runtime
+    if _device_words(words):
+        from . import device_buffer
+        return device_buffer.histogram_dev(pk, words, exps, bins, n_bins, node, n_nodes)
     if _runtime.gpu_available():
         return _runtime.context(pk).histogram(words, exps, bins, n_bins, node, n_nodes)
     W = words.shape[1]
@@ -601,6 +709,9 @@ def histogram_sparse_words(pk, words, exps, indptr, indices, data, zs, node, sha
     nothing else is stored, and empty (ciphertext 1, EMPTY_EXP) where its count is 0."""
     from . import _runtime
     nodes, F, B = shape
+    if _device_words(words):
+        from . import device_buffer
+        return device_buffer.histogram_sparse_dev(pk, words, exps, indptr, indices, data, zs, node, shape)
     if _runtime.gpu_available():
         return _runtime.context(pk).histogram_sparse(words, exps, indptr, indices, data, F, zs, B, node, nodes)
     W, cells = words.shape[1], nodes * F * B

@@ -66,10 +66,17 @@ class PaillierDecryptor(object):
         words, exps, _ = pack(encrypted_number_numpy, self.pub_key)
         return self._decrypt_words(words, exps, s)
 
-    def _decrypt_words(self, words: np.ndarray, exps: np.ndarray, s) -> np.ndarray:
+    def _decrypt_words(self, words, exps, s) -> np.ndarray:
+        """words: numpy [N, W], or a device holder (device_buffer.DeviceWords) with the exponents as a device block: then
+        pai_decrypt_dev runs where the words are, and only values and statuses come back."""
         from . import _native, _runtime
-        ctx = _runtime.context(self.pub_key, self.priv_key)
-        val, mant, st, _ = ctx.decrypt(words, exps)
+        if isinstance(words, np.ndarray):
+            ctx = _runtime.context(self.pub_key, self.priv_key)
+            run = lambda want_raw=False: ctx.decrypt(words, exps, want_raw=want_raw)          # noqa: E731
+        else:
+            from .device_buffer import decrypt_dev
+            run = lambda want_raw=False: decrypt_dev(self.pub_key, self.priv_key, words, exps, want_raw)   # noqa: E731
+        val, mant, st, _ = run()
         if np.all(st == _native.EL_OK):
             return val.reshape(s)
         for code, exc, msg in ((_native.EL_OVERFLOW, OverflowError, 'Overflow detected in decode number'),
@@ -78,16 +85,17 @@ class PaillierDecryptor(object):
                 raise exc(msg)
         raw = None
         if np.any(st == _native.EL_INT_BIG):
-            _, _, _, raw_words = ctx.decrypt(words, exps, want_raw=True)
+            _, _, _, raw_words = run(True)
             raw = _runtime.words_to_ints(raw_words)
+        ex = exps if isinstance(exps, np.ndarray) else exps.download(np.int32, st.size)
         values = []
-        for i in range(exps.size):
+        for i in range(ex.size):
             if st[i] == _native.EL_OK:
                 values.append(float(val[i]))
             elif st[i] == _native.EL_INT:
                 values.append(int(mant[i]))
             else:   # exact integer too wide for int64: decode the exact plaintext
-                values.append(FixedPointNumber(raw[i], int(exps[i]), self.pub_key.n, self.pub_key.max_int).decode())
+                values.append(FixedPointNumber(raw[i], int(ex[i]), self.pub_key.n, self.pub_key.max_int).decode())
         return np.array(values).reshape(s)
 
     def _decrypt_packed(self, buf) -> np.ndarray:
@@ -100,7 +108,12 @@ class PaillierDecryptor(object):
         e = buf.layout.exponent
         if buf.count == 0:
             return np.zeros(buf.shape, dtype=np.int64 if e == 0 else np.float64)
-        if _runtime.gpu_available():
+        if buf.resident:
+            from .device_buffer import decrypt_packed_dev
+            val, mant, st = decrypt_packed_dev(self.pub_key, self.priv_key, buf.words, buf.layout, buf.count)
+            if np.any(st == _native.EL_OVERFLOW):
+                raise OverflowError('Overflow detected in decode number')
+        elif _runtime.gpu_available():
             val, mant, st = _runtime.context(self.pub_key, self.priv_key).decrypt_packed(buf.words, buf.layout, buf.count)
             if np.any(st == _native.EL_OVERFLOW):
                 raise OverflowError('Overflow detected in decode number')
@@ -110,11 +123,19 @@ class PaillierDecryptor(object):
         return (mant if e == 0 else val).reshape(buf.shape)
 
     def decrypt(self, encrypted_number):
-        """decryptor.py:114-127 (plus CiphertextBuffer, cipher_buffer.py, and PackedCiphertextBuffer)"""
+        """decryptor.py:114-127 (plus CiphertextBuffer, cipher_buffer.py, DeviceCiphertextBuffer, device_buffer.py, and
+        PackedCiphertextBuffer, host or resident)"""
         from .cipher_buffer import CiphertextBuffer
+        from .device_buffer import DeviceCiphertextBuffer
         from .packed_buffer import PackedCiphertextBuffer
         if isinstance(encrypted_number, PackedCiphertextBuffer):
             return self._decrypt_packed(encrypted_number)
+        if isinstance(encrypted_number, DeviceCiphertextBuffer):
+            if encrypted_number.public_key != self.pub_key:
+                raise ValueError("encrypted_number was encrypted against a different key!")
+            if encrypted_number.size == 0:
+                return np.array([]).reshape(encrypted_number.shape)
+            return self._decrypt_words(encrypted_number.words, encrypted_number._ex, encrypted_number.shape)
         if isinstance(encrypted_number, CiphertextBuffer):
             if encrypted_number.public_key != self.pub_key:
                 raise ValueError("encrypted_number was encrypted against a different key!")

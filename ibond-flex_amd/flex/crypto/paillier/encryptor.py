@@ -108,10 +108,12 @@ class PaillierEncryptor(object):
             out = PaillierArray(objs.reshape(s))
         return out
 
-    def encrypt_to_buffer(self, values: np.ndarray, precision: int = None):
+    def encrypt_to_buffer(self, values: np.ndarray, precision: int = None, device: bool = False):
         """Encrypt an array into a CiphertextBuffer (cipher_buffer.py): the device words, exponents and
         obfuscation flags, no PaillierEncryptedNumber per element. Same ciphertext distribution as
-        encrypt(values); for callers that ship (to_wire) or sum ciphertexts without touching them."""
+        encrypt(values); for callers that ship (to_wire) or sum ciphertexts without touching them.
+        device=True: a DeviceCiphertextBuffer (device_buffer.py) -- the ciphertexts stay where pai_encrypt_dev wrote
+        them, and only the plaintexts and the statuses cross PCIe. RuntimeError without a GPU."""
         from . import _native, _runtime, obfuscator_pool
         from .cipher_buffer import CiphertextBuffer
         values = np.asarray(values)
@@ -122,6 +124,15 @@ class PaillierEncryptor(object):
         exp_mode, fixed_exp = _native.PAI_EXP_AUTO, 0
         if precision is not None:
             exp_mode, fixed_exp = _native.PAI_EXP_FIXED, math.floor(math.log(precision, FixedPointNumber.BASE))
+        if device:
+            from .device_buffer import DeviceCiphertextBuffer, encrypt_dev
+            words, ex, st = encrypt_dev(self.pub_key, x, exp_mode, fixed_exp)
+            for i in np.nonzero(st != _native.EL_OK)[0].tolist():
+                # beyond the device's 64-bit fixed-point range: the host encoder (raises like the reference)
+                e = self._encrypt(values.reshape(-1)[i], precision)
+                words.mem.upload(_runtime.ints_to_words([e.ciphertext(False)], words.shape[1])[0], i * words.shape[1] * 4)
+                ex.upload(np.array([e.exponent], dtype=np.int32), i * 4)
+            return DeviceCiphertextBuffer(self.pub_key, words, ex, 1, s)
         ctx = _runtime.context(self.pub_key)
         with obfuscator_pool.lock:           # obfuscators prepared ahead of time, when they cover the whole array
             pooled = obfuscator_pool.device_pool(self.pub_key, x.size)

@@ -154,6 +154,14 @@ def _gpu() -> bool:
     return _runtime.gpu_available()
 
 
+def _resident(words) -> bool:
+    """True when the words are a device holder (device_buffer.DeviceWords), not a numpy array."""
+    if isinstance(words, np.ndarray):
+        return False
+    from .device_buffer import DeviceWords
+    return isinstance(words, DeviceWords)
+
+
 def host_raw_decrypt(c: int, priv_key) -> int:
     """decryptor.py:33-63 on Python integers: the raw plaintext in [0, n)."""
     p, q = priv_key.p, priv_key.q
@@ -164,7 +172,9 @@ def host_raw_decrypt(c: int, priv_key) -> int:
 
 class PackedCiphertextBuffer(object):
     """C = ceil(count / slots) packed ciphertexts: words [C, W], the layout, the number of values and their shape, one
-    obfuscation flag for the buffer, and the exact slot bound."""
+    obfuscation flag for the buffer, and the exact slot bound. to_device() gives the same buffer with its words resident
+    on the GPU (device_buffer.DeviceWords in the place of the numpy words): the operators then run the *_dev entry
+    points and return resident buffers; layout and bound bookkeeping are the same, checked before any GPU call."""
     __slots__ = ("public_key", "words", "layout", "count", "shape", "obfuscated", "bound")
 
     def __init__(self, public_key, words: np.ndarray, layout: PackedLayout, count: int, shape=None,
@@ -173,10 +183,11 @@ class PackedCiphertextBuffer(object):
         W = (2 * nb + 31) // 32
         if not isinstance(layout, PackedLayout) or layout.key_bits != nb:
             raise ValueError("layout does not belong to a key of this size")
-        words = np.ascontiguousarray(words, dtype=np.uint32)
+        if not _resident(words):
+            words = np.ascontiguousarray(words, dtype=np.uint32)
         count = int(count)
         C = -(-count // layout.slots)
-        if words.shape != (C, W):
+        if tuple(words.shape) != (C, W):
             raise ValueError(f"ciphertext words {words.shape} do not match ({C}, {W}) for {count} values")
         self.public_key, self.words, self.layout, self.count = public_key, words, layout, count
         self.shape = tuple(int(v) for v in shape) if shape is not None else (count,)
@@ -188,7 +199,27 @@ class PackedCiphertextBuffer(object):
             raise OverflowError(f"slot bound {self.bound} exceeds 2^(slot_bits - 1) - 1")
 
     def __repr__(self):
-        return f"PackedCiphertextBuffer(shape={self.shape}, {self.layout!r}, bound={self.bound})"
+        where = ", resident" if self.resident else ""
+        return f"PackedCiphertextBuffer(shape={self.shape}, {self.layout!r}, bound={self.bound}{where})"
+
+    @property
+    def resident(self) -> bool:
+        return _resident(self.words)
+
+    def to_device(self) -> "PackedCiphertextBuffer":
+        """The same buffer with its words on the GPU (one upload; RuntimeError without a GPU)."""
+        if self.resident:
+            return self
+        from . import _runtime
+        from .cipher_buffer import need_gpu
+        from .device_buffer import DeviceWords
+        need_gpu()
+        return self._like(DeviceWords.from_host(self.words, _runtime.context(self.public_key).device), self.bound,
+                          self.obfuscated)
+
+    def to_host(self) -> "PackedCiphertextBuffer":
+        """The same buffer with numpy words (one download)."""
+        return self._like(self.words.to_host(), self.bound, self.obfuscated) if self.resident else self
 
     @property
     def size(self) -> int:
@@ -232,7 +263,10 @@ class PackedCiphertextBuffer(object):
             raise OverflowError("scalar must be below 2^63 in magnitude")
         bound = self.bound * abs(s)
         self._check_bound(bound)
-        if _gpu():
+        if self.resident:
+            from .device_buffer import mul_dev
+            out, _, _ = mul_dev(self.public_key, self.words, self._exps(), np.array([s], dtype=np.int64))
+        elif _gpu():
             from . import _runtime
             out, _, _ = _runtime.context(self.public_key).mul(self.words, self._exps(), np.array([s], dtype=np.int64))
         else:
@@ -257,24 +291,30 @@ class PackedCiphertextBuffer(object):
         if self.count != N * k:
             raise ValueError(f"histogram: {self.count} values do not fill {N} ciphertexts of {k} slots (one ciphertext "
                              "per sample)")
+        # A resident buffer whose bound times ALL its samples fits the slot cannot overflow whatever the cells are: that
+        # check replaces the host-side count (22 ms for 262 144 x 16 bin ids, more than the kernels), and the counts the
+        # device returns give the same exact bound afterwards. Every other case counts on the host first, as before.
+        safe = self.resident and self.bound * N <= self.layout.slot_max
         csr = sparse_csr(bins)
         if csr is not None:
             # (a default cell is a true subset sum, T_v minus the stored rest, so counts.max() bounds it like any cell)
             *args, shape = histogram_sparse_args(N, csr, n_bins, node, n_nodes, default_bin)
             cells = shape[0] * shape[1] * shape[2]
-            cnt = histogram_sparse_counts(*args, shape)[0]
-            bound = self.bound * (int(cnt.max()) if cnt.size else 0)
-            self._check_bound(bound)
-            out, _, _ = histogram_sparse_words(self.public_key, self.words, self._exps(), *args, shape)
-            return (PackedCiphertextBuffer(self.public_key, out, self.layout, cells * k, shape + (k,), False, bound),
-                    cnt.reshape(shape))
-        b, nd, shape = histogram_args(N, bins, n_bins, node, n_nodes)
-        cells = shape[0] * shape[1] * shape[2]
-        cell = histogram_cells(b, shape[2], nd, shape[0])
-        cnt = np.bincount(cell[cell >= 0], minlength=cells).astype(np.int64)
+            if not safe:
+                cnt = histogram_sparse_counts(*args, shape)[0]
+                self._check_bound(self.bound * (int(cnt.max()) if cnt.size else 0))
+            out, _, dev_cnt = histogram_sparse_words(self.public_key, self.words, self._exps(), *args, shape)
+        else:
+            b, nd, shape = histogram_args(N, bins, n_bins, node, n_nodes)
+            cells = shape[0] * shape[1] * shape[2]
+            if not safe:
+                cell = histogram_cells(b, shape[2], nd, shape[0])
+                cnt = np.bincount(cell[cell >= 0], minlength=cells).astype(np.int64)
+                self._check_bound(self.bound * (int(cnt.max()) if cnt.size else 0))
+            out, _, dev_cnt = histogram_words(self.public_key, self.words, self._exps(), b, shape[2], nd, shape[0])
+        if safe:
+            cnt = dev_cnt
         bound = self.bound * (int(cnt.max()) if cnt.size else 0)
-        self._check_bound(bound)
-        out, _, _ = histogram_words(self.public_key, self.words, self._exps(), b, shape[2], nd, shape[0])
         return (PackedCiphertextBuffer(self.public_key, out, self.layout, cells * k, shape + (k,), False, bound),
                 cnt.reshape(shape))
 
@@ -300,7 +340,10 @@ class PackedCiphertextBuffer(object):
         if self.obfuscated or self.words.shape[0] == 0:
             self.obfuscated = True
             return self
-        if _gpu():
+        if self.resident:
+            from .device_buffer import obfuscate_dev
+            self.words = obfuscate_dev(self.public_key, self.words)
+        elif _gpu():
             from .obfuscator import apply_obfuscation_array
             self.words = apply_obfuscation_array(self.words, self.public_key)
         else:
@@ -325,13 +368,33 @@ class PackedCiphertextBuffer(object):
                          np.asarray(self.layout.as_tuple(), dtype="<i4").tobytes(), np.uint64(self.count).tobytes(),
                          np.uint32(len(self.shape)).tobytes(), np.asarray(self.shape, dtype="<i8").tobytes(),
                          np.uint32(bb).tobytes(), self.bound.to_bytes(bb, "little"),
-                         bytes([1 if self.obfuscated else 0]), np.ascontiguousarray(self.words, dtype="<u4").tobytes()])
+                         bytes([1 if self.obfuscated else 0]),
+                         np.ascontiguousarray(self.words.to_host() if self.resident else self.words, dtype="<u4").tobytes()])
+
+    def take(self, indices, axis: int = 0) -> "PackedCiphertextBuffer":
+        """np.take along a leading axis, for buffers whose last axis is exactly the slots of one ciphertext per index of
+        the leading axes (what histogram returns); the slot axis cannot be indexed. One pai_take_dev on a resident
+        buffer."""
+        from .cipher_buffer import axis_split
+        k, C = self.layout.slots, self.words.shape[0]
+        if len(self.shape) < 2 or self.shape[-1] != k or self.count != C * k:
+            raise ValueError(f"take: shape {self.shape} is not (..., {k}) with one ciphertext per index of the leading axes")
+        lead = self.shape[:-1]
+        axis_split(lead, axis)                                                  # (the axis rules; the slot axis is out)
+        idx = np.take(np.arange(C, dtype=np.int64).reshape(lead), indices, axis=axis)
+        if self.resident:
+            from .device_buffer import take_dev
+            words, _ = take_dev(self.public_key, self.words, self._exps(), idx.reshape(-1))
+        else:
+            words = self.words[idx.reshape(-1)]
+        return PackedCiphertextBuffer(self.public_key, words, self.layout, idx.size * k, idx.shape + (k,), self.obfuscated,
+                                      self.bound)
 
     @classmethod
-    def from_wire(cls, buf, public_key=None) -> "PackedCiphertextBuffer":
+    def from_wire(cls, buf, public_key=None, device: bool = False) -> "PackedCiphertextBuffer":
         """Inverse of to_wire. `public_key` (optional) must match the key in the buffer. ValueError for anything
         malformed: a wrong length or W, an invalid layout, a count above C * slots, a bound above the slot, a word row
-        >= n^2."""
+        >= n^2. device=True: a resident buffer; the words are uploaded once and range-checked on the GPU."""
         from .cipher_array import _rows_below
         from .keypair import PaillierPublicKey
         mv = memoryview(buf).cast("B")
@@ -384,6 +447,14 @@ class PackedCiphertextBuffer(object):
             raise ValueError("corrupted packed ciphertext buffer (count does not match the ciphertexts)")
         if bound > layout.slot_max:
             raise ValueError("corrupted packed ciphertext buffer (bound above the slot)")
+        if device:
+            from . import _runtime
+            from .cipher_buffer import need_gpu
+            from .device_buffer import upload_checked
+            need_gpu()
+            words = upload_checked(public_key, take("<u4", C * W).reshape(C, W), _runtime.context(public_key).device,
+                                   "corrupted packed ciphertext buffer (ciphertext >= n^2)")
+            return cls(public_key, words, layout, count, shape, bool(flags & 1), bound)
         words = take("<u4", C * W).reshape(C, W).copy()
         if C and not _rows_below(words, public_key.nsquare):
             raise ValueError("corrupted packed ciphertext buffer (ciphertext >= n^2)")
@@ -405,7 +476,10 @@ def add_packed(bufs: Sequence[PackedCiphertextBuffer]) -> PackedCiphertextBuffer
     a._check_bound(bound)
     if len(bufs) == 1:
         return a
-    if _gpu():
+    if any(b.resident for b in bufs):          # one resident operand keeps the sum on the device
+        from .device_buffer import add_dev
+        out, _ = add_dev(a.public_key, [b.to_device().words for b in bufs], [a._exps()] * len(bufs))
+    elif _gpu():
         from . import _runtime
         out, _ = _runtime.context(a.public_key).add([b.words for b in bufs], [a._exps()] * len(bufs))
     else:
@@ -460,11 +534,15 @@ def _slot_bound(layout: PackedLayout, max_abs, terms: int = 1) -> int:
 
 
 def _fold(pub_key, words, exps, layout: PackedLayout, bound: int, shape) -> "PackedCiphertextBuffer":
-    """One pai_pack_ciphertexts call over words [N, W] / exps [N] (Python integers without a GPU)."""
+    """One pai_pack_ciphertexts call over words [N, W] / exps [N] (Python integers without a GPU); resident words
+    (device_buffer.DeviceWords) fold on the device into a resident buffer."""
     if not isinstance(layout, PackedLayout) or layout.key_bits != pub_key.n.bit_length():
         raise ValueError("layout does not belong to a key of this size")
     W = (2 * pub_key.n.bit_length() + 31) // 32
-    if exps.size == 0:
+    if _resident(words):
+        from .device_buffer import pack_dev
+        out, st = pack_dev(pub_key, words, exps, layout)
+    elif exps.size == 0:
         out, st = np.zeros((0, W), dtype=np.uint32), np.zeros(0, dtype=np.int32)
     elif _gpu():
         from . import _runtime
@@ -489,7 +567,8 @@ def pack_ciphertexts(src, layout: PackedLayout, max_abs) -> "PackedCiphertextBuf
     0 <= 4 (layout.exponent - exponent) < slot_bits (ValueError names the first index that does not). The result is not
     re-randomised (obfuscated=False): to_wire(be_secure=True) does that."""
     from .cipher_buffer import CiphertextBuffer
-    if isinstance(src, CiphertextBuffer):
+    from .device_buffer import DeviceCiphertextBuffer
+    if isinstance(src, (CiphertextBuffer, DeviceCiphertextBuffer)):
         pk, words, exps, shape = src.public_key, src.words, src.exps, src.shape
     elif isinstance(src, np.ndarray) and src.dtype == object:
         from .cipher_array import _encrypted_operand, pack

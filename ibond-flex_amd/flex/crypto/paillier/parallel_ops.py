@@ -94,6 +94,8 @@ def cumsum(x: np.ndarray, axis: int = -1, reverse: bool = False) -> PaillierArra
     obfuscated. Without a GPU the same runs on Python integers."""
     from .cipher_array import _encrypted_operand, materialize, pack
     from .cipher_buffer import axis_split, cumsum_words
+    if _on_device(x):
+        return x.cumsum(axis, reverse)                      # a device buffer in, a device buffer out
     if not isinstance(x, np.ndarray):
         raise TypeError(f"cumsum of {type(x)} not supported")
     A, pk = _encrypted_operand(x)
@@ -179,11 +181,18 @@ def segment_sum_packed(x, index_lists, layout, max_abs):
     return _fold(pk, out, np.ascontiguousarray(oe, dtype=np.int32), layout, bound, (len(lists),))
 
 
+def _on_device(x) -> bool:
+    from .device_buffer import DeviceCiphertextBuffer
+    return isinstance(x, DeviceCiphertextBuffer)
+
+
 def _histogram_operand(x, who: str):
     from .cipher_array import _encrypted_operand, pack
     from .cipher_buffer import CiphertextBuffer
     if isinstance(x, CiphertextBuffer):
         return x.public_key, x.words, x.exps
+    if _on_device(x):
+        return x.public_key, x.words, x._ex                 # device holders: the cells stay on the device
     A, pk = _encrypted_operand(x)
     if A is None:
         raise TypeError(f"{who} needs a non-empty array of PaillierEncryptedNumber with one public key")
@@ -197,9 +206,9 @@ def _histogram_cells(pk, words, exps, bins, n_bins, node, n_nodes, default_bin):
     from .cipher_buffer import histogram_args, histogram_sparse_args, histogram_sparse_words, histogram_words, sparse_csr
     csr = sparse_csr(bins)
     if csr is not None:
-        *args, shape = histogram_sparse_args(exps.size, csr, n_bins, node, n_nodes, default_bin)
+        *args, shape = histogram_sparse_args(words.shape[0], csr, n_bins, node, n_nodes, default_bin)
         return histogram_sparse_words(pk, words, exps, *args, shape) + (shape,)
-    b, nd, shape = histogram_args(exps.size, bins, n_bins, node, n_nodes)
+    b, nd, shape = histogram_args(words.shape[0], bins, n_bins, node, n_nodes)
     return histogram_words(pk, words, exps, b, shape[2], nd, shape[0]) + (shape,)
 
 
@@ -215,6 +224,8 @@ def histogram(x, bins, n_bins, node=None, n_nodes=1, default_bin=0):
     that is not stored has bin default_bin (a scalar or one per feature), and the default cell is the node's total minus
     the feature's other stored entries (``T - S`` of the reference's operators, CiphertextBuffer.histogram)."""
     from .cipher_array import materialize
+    if _on_device(x):
+        return x.histogram(bins, n_bins, node=node, n_nodes=n_nodes, default_bin=default_bin)
     pk, words, exps = _histogram_operand(x, "histogram")
     out, oe, cnt, shape = _histogram_cells(pk, words, exps, bins, n_bins, node, n_nodes, default_bin)
     oe = np.where(cnt == 0, 0, oe).astype(np.int32)
@@ -224,6 +235,7 @@ def histogram(x, bins, n_bins, node=None, n_nodes=1, default_bin=0):
 def histogram_packed(x, bins, n_bins, layout, max_abs, node=None, n_nodes=1, default_bin=0):
     """The cell sums of histogram as ONE PackedCiphertextBuffer of shape (n_nodes, F, n_bins): one pai_histogram call,
     then one pai_pack_ciphertexts call that folds layout.slots cell sums into each ciphertext; returns (buffer, counts).
+    A DeviceCiphertextBuffer gives a resident packed buffer (histogram and cumsum return device buffers for one too).
     `x` holds integer-valued ciphertexts at the layout's exponent with |value| <= max_abs (the caller's assertion); the
     buffer's bound is counts.max() * ceil(max_abs * 16^exponent), OverflowError before the fold if it passes the slot.
     Empty cells decode as 0. Without a GPU the same runs on Python integers (small arrays only). Sparse bins and
@@ -233,6 +245,8 @@ def histogram_packed(x, bins, n_bins, layout, max_abs, node=None, n_nodes=1, def
     _slot_bound(layout, max_abs, 1)                         # a single value already has to fit
     out, oe, cnt, shape = _histogram_cells(pk, words, exps, bins, n_bins, node, n_nodes, default_bin)
     bound = _slot_bound(layout, max_abs, int(cnt.max()) if cnt.size else 0)
+    if _on_device(x):
+        oe = oe.download(np.int32, cnt.size)                # exponents only: the cells fold where they are
     return _fold(pk, out, np.ascontiguousarray(oe, dtype=np.int32), layout, bound, shape), cnt.reshape(shape)
 
 

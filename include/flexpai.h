@@ -489,6 +489,53 @@ int pai_histogram_sparse_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* 
 int pai_cumsum_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t outer, size_t L, size_t inner,
                    int flags, uint32_t* d_out, int32_t* d_exp_out, void* stream);
 
+/* Device-resident ciphertext buffers (csrc/engine_res.hip, kernels_res.hpp; no reference counterpart): memory for
+ * the *_dev entry points that a caller without a HIP runtime of its own (the Python layer, which never imports torch)
+ * can hold across calls, so that a chain of calls moves no ciphertext word over PCIe.
+ *
+ * Ownership: the blocks belong to a DEVICE, not to a context. A block outlives every context that wrote it and may be
+ *   passed to any context on the same device. Nothing frees a block but pai_dev_free.
+ *   pai_dev_alloc     `bytes` of device memory (at least 16), from the allocator of the call buffers: when the device
+ *                     is full, released table memory (pai_release_table_cache) goes back to the driver first.
+ *   pai_dev_free      A FREE THAT SYNCHRONISES: it waits for all work queued on the device (hipDeviceSynchronize) and
+ *                     then frees, so dropping a block while kernels that read it are still queued is safe, on whatever
+ *                     stream they were queued. Null is PAI_OK.
+ *   pai_dev_upload    host -> device, pai_dev_download: device -> host. Complete on return. Each first waits for the
+ *                     work queued on the device, so a download sees the result of every *_dev call made before it and
+ *                     an upload never overwrites a block that a queued kernel still reads. They go through two pinned
+ *                     staging slots of at most 64 MiB per device: the host threads (at most 16) fill or drain one slot
+ *                     while the other crosses PCIe, the pattern of pai_add / pai_decrypt. Calls are serialised by one
+ *                     mutex; a call that fails waits for its copies in flight before it returns. In the test build
+ *                     $FLEXPAI_RES_SLOT (bytes) shrinks the slot.
+ *   pai_dev_copy      device -> device, queued on the NULL stream and not waited for: ordered with *_dev calls made on
+ *                     the null stream (the Python layer's), and complete before any pai_dev_free, pai_dev_upload or
+ *                     pai_dev_download that follows, since those wait for the device.
+ *   pai_dev_release_staging  gives the copy streams, events and pinned slots (up to 128 MiB of pinned host memory per
+ *                     device) back now; the next transfer makes them again. Otherwise they live as long as the process.
+ *   pai_dev_io_stats  process-wide bytes moved by pai_dev_upload and by pai_dev_download since the process started
+ *                     (each nullable).
+ *
+ * pai_take_dev: out[j] = in[index[j]], words and exponents (kernels_res.hpp k_take). index holds M entries and is a
+ *   HOST array, as in pai_segment_add_dev; an entry lies in [0, N) and may repeat, or is -1, which writes the identity
+ *   the API uses for an empty segment: ciphertext 1, exponent INT32_MIN. PAI_ERR_ARG before any launch, with the output
+ *   untouched: any other index value, a null pointer with M > 0, an output that overlaps the input. M = 0 is PAI_OK. Rows
+ *   move as 16-byte vectors when ct_words is a multiple of 4 and both bases are 16-byte aligned, word by word otherwise
+ *   (a 1035-bit key has 65 words). Takes the context lock and chains on the previous call's event like every _dev call;
+ *   synchronises `stream` once, after the launch (the index is caller memory).
+ * pai_check_below_dev: *first_bad = the smallest i with ct[i] >= n^2, or -1 (k_check_below: compared from the top limb;
+ *   one read-back of one word; synchronises `stream`). The range check of a received ciphertext array, done where the
+ *   array already is. */
+int pai_dev_alloc(int device, size_t bytes, void** d_out);
+int pai_dev_free(int device, void* d);
+int pai_dev_upload(int device, void* d_dst, const void* src, size_t bytes);
+int pai_dev_download(int device, void* dst, const void* d_src, size_t bytes);
+int pai_dev_copy(int device, void* d_dst, const void* d_src, size_t bytes);
+int pai_dev_io_stats(uint64_t* h2d_bytes, uint64_t* d2h_bytes);
+int pai_dev_release_staging(void);
+int pai_take_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* index, size_t M,
+                 uint32_t* d_ct_out, int32_t* d_exp_out, void* stream);
+int pai_check_below_dev(pai_ctx* ctx, const uint32_t* d_ct, size_t N, int64_t* first_bad, void* stream);
+
 /* Packed plaintexts: many signed fixed-point values per ciphertext (no reference counterpart; opt-in, both peers must
  * be flexpai; csrc/kernels_pack.hpp). Every packed ciphertext is an ordinary reference ciphertext
  * raw_encrypt(M mod n, pk, r), so pai_add, pai_mul by an integer and pai_obfuscate act on all slots at once.
