@@ -44,7 +44,7 @@ inline EncryptRoute encrypt_route(const pai_route_facts& f, int obf_mode, long l
   } else {
     if (rng && f.pfb_enabled && f.pfb_supported && rt.sampler == PAI_SAMPLER_NONE) rt.sampler = PAI_SAMPLER_PUBLIC;
     if (n <= f.crtw_max && f.pew_ok) rt.chain = PAI_CHAIN_PE_ROWS;
-    else if (f.pe_ok && f.ct_words == 128) rt.chain = PAI_CHAIN_PE;   // 1537..2048-bit n: 64-word pairs
+    else if (f.pe_ok && f.ct_words == 128) rt.chain = PAI_CHAIN_PE;   // 2033..2048-bit n: k_pe_fin writes 64-word pairs
     else if (f.pe1_ok) rt.chain = PAI_CHAIN_PE1;
     else if (f.pe4_ok && !f.has_priv) rt.chain = PAI_CHAIN_PE4;
   }

@@ -2684,7 +2684,9 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
 // ------------------------------------------------------------------ public-key fixed bases (kernels_pfb.hpp)
 // A party without the private key samples r = g_0^e_0 g_1^e_1 ... g_32^e_32 mod n from 33 bases it drew itself
 // (g_0 with Jacobi symbol -1) and exponents from the element's ChaCha20 stream (e_0: nb + 64 bits, e_j: 96 bits),
-// and gets r^n mod n^2 as a product of table rows (distribution argument, break-even).
+// and gets r^n mod n^2 as a product of table rows (distribution argument, break-even). The rows and
+// k_pe_fin's output are 64-word pairs, so of setup_pe's 1537..2048 bits only the keys of 128 ciphertext words (n of
+// 2033..2048 bits) qualify, as for k_pe_* in encrypt_route.hpp.
 static bool pfb_supported(const pai_ctx* c) {
   return c->pe_ok && c->ct_words == 2 * PFB_PW && (size_t)c->nb + 24 <= (size_t)LB * PFB_S;
 }
@@ -2824,7 +2826,7 @@ static int pfb_upload(pai_ctx* c, int W, int K0, int KS, RowScratch& sc, uint4**
 static int ensure_pfb(pai_ctx* c) {
   if (c->pfb_state == pai_ctx::FB_READY) return 1;
   if (c->pfb_state == pai_ctx::FB_UNAVAILABLE) return 0;
-  if (!pfb_supported(c)) return pfb_unavailable(c, "the public fixed-base kernels need a 1537..2048-bit n");
+  if (!pfb_supported(c)) return pfb_unavailable(c, "the public fixed-base kernels need an n of 2033..2048 bits (128 ciphertext words)");
   const int W = pfb_choose_window(c);
   if (!W) return pfb_unavailable(c, "tables do not fit the device memory budget");
   SetupTrace tr_all("ensure_pfb");

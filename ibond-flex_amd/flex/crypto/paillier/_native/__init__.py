@@ -619,7 +619,8 @@ class Context:
     @property
     def pair_paths(self) -> int:
         """Bit 0: decryption, bit 1: CRT encryption stage B on p-adic pairs (kernels_pair.hpp); bit 2: public-key
-        encryption on pairs (n of at most 1024 bits and of 1537..2048 bits; n of 2049..4096 bits on pair groups,
+        encryption on pairs (n of at most 1024 bits and of 1537..2048 bits -- of the latter only keys of 128 ciphertext
+        words, 2033..2048 bits, run k_pe_*, the others k_encrypt; n of 2049..4096 bits on pair groups,
         kernels_pe4.hpp, while the context holds no private key); bit 3: a 2049..4096-bit key holder's encryption above the
         rows runs the split-pair CRT (kernels_crt4.hpp)."""
         return int(self._get_option(PAI_OPT_PAIR))

@@ -153,7 +153,9 @@ typedef struct pai_comm pai_comm;
                                     2049..4096 bits and its encryption above the rows (more than PAI_OPT_ROWS_MAX and
                                     more than PAI_OPT_CRT4_MIN elements, explicit r or device RNG without resident
                                     fixed-base tables) runs the split-pair CRT (kernels_crt4.hpp). A key holder's
-                                    bit 2 stays 0. The whole order: csrc/encrypt_route.hpp                     */
+                                    bit 2 stays 0 at 2049..4096 bits. Bit 2 says the constants are set up: of the
+                                    1537..2048-bit keys only those of 128 ciphertext words (n of 2033..2048 bits)
+                                    run k_pe_*, the others k_encrypt. The whole order: csrc/encrypt_route.hpp  */
 #define PAI_OPT_PUBLIC_FB 10     /* 1 (default): PAI_OBF_RNG encryption WITHOUT the private key (2048-bit n) samples
                                   * r^n through the public fixed bases (kernels_pfb.hpp) once the break-even count
                                   * is reached (pai_ctx_public_fb_policy); get: 1 when the path is enabled and not
