@@ -620,6 +620,16 @@ static bool build_lane_program(const HBig& e, std::vector<uint32_t>& prog) {
   return loaded;
 }
 
+// Stage A's exponent, other mod (p_h - 1). Primes that lie close to one another, or to powers of two in the ratio
+// 2^k (the two largest primes below 2^517; 2^518 - 917 and 2^517 - 489, which leave 63), give a residue too short for
+// an op list (build_lane_program wants a chain of more than one window). Such a residue is lifted by p_h - 1, which
+// changes no result: x^(p_h - 1) = 1 mod p_h for every unit, and a multiple of p_h stays 0 (it would not at residue 0).
+static HBig stage_a_exponent(const HBig& other, const HBig& ph) {
+  const HBig pm1 = sub(ph, HBig(1));
+  const HBig ea = mod(other, pm1);
+  return ea.bits() < 64 ? add(ea, pm1) : ea;
+}
+
 // K_t: for each table entry t, the sum over the chain's multiplies by it of 2^(squares after that multiply)
 static std::vector<HBig> chain_weights(const HBig& ph, const std::vector<uint16_t>& sched) {
   std::vector<HBig> K(LANE_NTILE, HBig(0));
@@ -1946,7 +1956,7 @@ static int setup_rows4096(pai_ctx* c, const HBig& p, const HBig& q) {
     const HBig& ph = primes[h];
     const HBig& m2 = sq[h];
     std::vector<uint32_t> pa, pb, pd;
-    if (!build_lane_program(mod(primes[1 - h], sub(ph, HBig(1))), pa) || !build_lane_program(ph, pb) ||
+    if (!build_lane_program(stage_a_exponent(primes[1 - h], ph), pa) || !build_lane_program(ph, pb) ||
         !build_lane_program(sub(ph, HBig(1)), pd))
       return 0;
     const HBig coef = inv_mod(sq[1 - h], m2);
@@ -2044,7 +2054,7 @@ static int setup_crt(pai_ctx* c, const HBig& p, const HBig& q) {
     const HBig& ph = primes[h];
     const HBig& other = primes[1 - h];
     // stage A: (r mod p_h)^(other mod (p_h - 1)) mod p_h
-    HBig ea = mod(other, sub(ph, HBig(1)));
+    HBig ea = stage_a_exponent(other, ph);
     std::vector<uint32_t> pa, pbp;
     if (!build_lane_program(ea, pa) || !build_lane_program(ph, pbp)) return 0;
     std::vector<uint32_t> ck;

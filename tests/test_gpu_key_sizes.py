@@ -20,6 +20,12 @@ it on an MI355X (test_key_map asserts it from the inequalities written out in _e
   K2072 (1036/1036) 74/148 3  2   8/4     no    9    no    k_crt4_*                    k_dec4_*, k_decrypt<4>    k_sgp<74>
   K3072 (1536/1536) 74/148 3  2   8/4     no    9    no    as K2072                    as K2072                  k_sgp<74>
   K4096 (golden)   74/148  4  2   8/4     no    9    no    as K2072                    as K2072                  k_sgs<74>
+  K1034T (517/517) 19/37   4  3   2/2     yes   3    yes   as K1034                    as K1034                  refused
+  K2048T (1024/1024) 37/74 4  2   4/2     yes   7    yes   as K2048                    as K2048                  k_fbs<37>
+
+  K1034T and K2048T are top-heavy: their primes are the two largest below 2^517 and below 2^1024, so p_h and p_h^2 lie
+  within a hair of the power of two above them, where K1034 and K2048 meet the pair kernels' bounds (2 pb + 2 = 28 * 37,
+  28 * 37 = pb + 12) with primes whose top bits are random.
 
   sa/sb   limbs of p_h and of p_h^2: the first of (19, 37), (37, 74) with 28 sa >= pb + 2 and 28 sb >= 2 pb + 2 (pb <= 517,
           pb <= 1034); no pair for pb >= 1035, where setup_fbg / setup_rows4096 / setup_crt4 take 74/148 if tpi_e = 8
@@ -65,8 +71,10 @@ SPECS = {"K512": None, "K768": (768, 384, 384, 1), "K1024": None, "K1034": (1034
          "K1035": (1035, 518, 517, 1), "K1036": (1036, 518, 518, 1), "K1536": (1536, 768, 768, 1), "K2048": None,
          "K2050": (2050, 1025, 1025, 1), "K2071": (2071, 1036, 1035, 1), "K2072": (2072, 1036, 1036, 1),
          "K3072": (3072, 1536, 1536, 2), "K4096": None,
+         "K1034T": "top-heavy", "K2048T": "top-heavy",                        # the two largest primes below 2^517, 2^1024
          "P1537": (1537, 769, 769, 1), "P1792": (1792, 896, 896, 1)}          # public-only contexts (part 5)
-BITS = {"K512": 512, "K1024": 1024, "K2048": 2048, "K4096": 4096, **{k: v[0] for k, v in SPECS.items() if v}}
+BITS = {"K512": 512, "K1024": 1024, "K2048": 2048, "K4096": 4096, "K1034T": 1034, "K2048T": 2048,
+        **{k: v[0] for k, v in SPECS.items() if isinstance(v, tuple)}}
 HOLDERS = [k for k in SPECS if k.startswith("K")]
 PUBLIC = ["K512", "K768", "K1024", "K1035", "K1536", "P1537", "P1792", "K2048"]
 # What the library reported on the GPU, per key: (sa, sb), crt_available, pair_paths, lane_decrypt, sampler accepted.
@@ -77,7 +85,8 @@ REPORTED = {"K512": ((19, 37), True, 7, True, False), "K768": ((19, 37), True, 7
             "K1536": ((37, 74), True, 3, True, False), "K2048": ((37, 74), True, 7, True, True),
             "K2050": ((37, 74), False, 0, False, False), "K2071": (None, False, 0, False, False),
             "K2072": ((74, 148), False, 9, False, True), "K3072": ((74, 148), False, 9, False, True),
-            "K4096": ((74, 148), False, 9, False, True)}
+            "K4096": ((74, 148), False, 9, False, True),
+            "K1034T": ((19, 37), True, 3, True, False), "K2048T": ((37, 74), True, 7, True, True)}
 
 
 def _native():
@@ -90,6 +99,9 @@ def _make_key(name, golden):
         k = next(e for e in golden["keygen"] if e["nb"] == 512 and e["seed"] == 99)
     elif SPECS[name] is None:
         k = golden["keys"][name[1:]]
+    elif SPECS[name] == "top-heavy":
+        from test_gpu_ops_sizes import _make_key as make      # p and q stepped down from the power of two
+        return make(name, golden)
     else:
         nb, pb, qb, seed = SPECS[name]
         while True:                                  # step the seed until n has exactly nb bits
@@ -213,14 +225,16 @@ def test_key_map(K, name):
     assert (e["limbs"], e["crt_available"], e["pair_paths"], e["lane_decrypt"], e["sampler"]) == REPORTED[name]
     # the seams the table rests on
     nb, pb = e["nb"], max(key.p.bit_length(), key.q.bit_length())
-    if name == "K1034":
+    if name in ("K1034", "K1034T"):
         assert 2 * pb + 2 == LB * 37 and (e["tpi_d"], e["kd"]) == (2, 3)
     if name == "K1035":
         assert 2 * nb + 2 == 2 * LB * LANE and e["tpi_e"] == 2 and e["limbs"] == (37, 74)
     if name == "K1036":
         assert e["tpi_e"] == 4
-    if name == "K2048":
+    if name in ("K2048", "K2048T"):
         assert LB * 37 == pb + 12
+    if name in ("K1034T", "K2048T"):                 # top-heavy: p_h^2 within 2^-500 of the power of two above it
+        assert all(h.bit_length() == pb and (1 << 2 * pb) - h * h < 1 << (2 * pb - 500) for h in (key.p, key.q))
     if name == "K2050":
         assert e["limbs"] == (37, 74) and LB * 37 < pb + 12
     if name == "K2071":

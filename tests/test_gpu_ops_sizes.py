@@ -39,7 +39,27 @@ def _native():
     return _native
 
 
+def _prime_below(x):
+    """The largest prime below x, stepping down with the oracle's Miller-Rabin."""
+    x -= 1
+    while not O._is_probable_prime(x):
+        x -= 1
+    return x
+
+
+# Top-heavy keys: name -> (bits of n, bits below which p is the largest prime, the same for q). Equal bounds: q is the
+# largest prime below p. n = p q lies just under 2^nb, so n^2 (or p^2) sits within a hair of the power of two above it.
+TOP_HEAVY = {"K1034T": (1034, 517, 517), "K1035T": (1035, 518, 517), "K2048T": (2048, 1024, 1024),
+             "K2071T": (2071, 1036, 1035)}
+
+
 def _make_key(name, golden):
+    if name in TOP_HEAVY:
+        nb, pb, qb = TOP_HEAVY[name]
+        p = _prime_below(1 << pb)
+        q = _prime_below(p if qb == pb else 1 << qb)
+        assert (p * q).bit_length() == nb
+        return O.Key(p * q, p, q)
     if name == "K512":
         k = next(e for e in golden["keygen"] if e["nb"] == 512 and e["seed"] == 99)
         return O.Key(int(k["n"], 16), int(k["p"], 16), int(k["q"], 16))

@@ -26,13 +26,9 @@ def _key(golden, nb):
 
 
 def _key1035():
-    """A 1035-bit modulus (ct_words 65), found as tests/test_gpu_ops_sizes.py finds its K1035."""
-    seed = 1
-    while True:
-        p, q = O.getprimeover(518, seed=seed), O.getprimeover(517, seed=seed + 1000)
-        if p != q and (p * q).bit_length() == 1035:
-            return O.Key(p * q, p, q)
-        seed += 1
+    """A 1035-bit modulus (ct_words 65): the K1035 of tests/test_gpu_ops_sizes.py."""
+    from test_gpu_ops_sizes import _make_key
+    return _make_key("K1035", None)
 
 
 def _pk(key):
