@@ -59,6 +59,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_scan.hpp"
 #include "engine_obf.hpp"
 #include "engine_pack.hpp"
+#include "engine_foldw.hpp"
 #include "engine_res.hpp"
 #include "engine_pool.hpp"
 #include "engine_crtw.hpp"
@@ -339,6 +340,10 @@ struct pai_ctx {
   // prefix sums (kernels_scan.hpp): PAI_OPT_SCAN_TILE / PAI_OPT_SCAN_PATH
   int scan_tile = 0;            // 0: automatic tile length of the blocked path
   int scan_path = 0;            // last pai_cumsum[_dev] call: 0 none yet, 1 row chains, 2 blocked
+  // folds (kernels_pack.hpp k_pack_fold, kernels_foldw.hpp k_pack_fold_w): PAI_OPT_FOLD_ROWS / PAI_OPT_FOLD_PATH
+  int fold_rows = 1;            // 1 automatic (fold_rows_max), 0 never rows, 2 rows wherever a row kernel exists
+  int fold_path = 0;            // last pai_pack_ciphertexts[_dev] / pai_repack[_dev] call: 0 none yet, 1 groups, 2 rows
+  long long fold_call_n = 0;    // outputs of the host-buffer fold in progress (its chunks share one choice), else 0
   void* d_scan = nullptr;       // the blocked path's tile totals and their scans, all levels
   size_t scan_bytes = 0;
   void* d_inv = nullptr;        // batch-inversion prefix products and segment products
@@ -2294,6 +2299,10 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       if (value < 0) return fail(PAI_ERR_ARG, "PAI_OPT_SCAN_TILE must be >= 0");
       c->scan_tile = value;
       return 0;
+    case PAI_OPT_FOLD_ROWS:
+      if (value < 0 || value > 2) return fail(PAI_ERR_ARG, "PAI_OPT_FOLD_ROWS must be 0, 1 or 2");
+      c->fold_rows = value;
+      return 0;
     case PAI_OPT_OBF_CHUNK:
       if (value < 64) return fail(PAI_ERR_ARG, "PAI_OPT_OBF_CHUNK must be >= 64");
       c->obf_chunk = value;
@@ -2337,6 +2346,8 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_POOL_FUSED: *value = c->pool.fused ? 1 : 0; return 0;
     case PAI_OPT_SCAN_TILE: *value = c->scan_tile; return 0;
     case PAI_OPT_SCAN_PATH: *value = c->scan_path; return 0;
+    case PAI_OPT_FOLD_ROWS: *value = c->fold_rows; return 0;
+    case PAI_OPT_FOLD_PATH: *value = c->fold_path; return 0;
     case PAI_OPT_OBF_CHUNK: *value = c->obf_chunk; return 0;
     case PAI_OPT_STAGE_TIMING: *value = c->timing ? 1 : 0; return 0;
     case PAI_OPT_LANE_DECRYPT: *value = (c->dec_lane_ok && c->dec_lane_enabled) ? 1 : 0; return 0;
@@ -4086,7 +4097,74 @@ int pai_decrypt_packed_dev(pai_ctx* c, const uint32_t* d_ct, const pai_pack_layo
   return 0;
 }
 
-// One k_pack_fold over the ceil(N / slots) outputs: no scratch, no inversion, nothing read back.
+// Largest output count that the automatic choice (PAI_OPT_FOLD_ROWS = 1) sends to the rows: the measured crossings of
+// tools/fold_ab.py (include/flexpai.h), per size of n^2 in limbs.
+static long long fold_rows_max(int k) {
+  return k == 74 ? PAI_FOLD_ROWS_MAX_1024 : k == 148 ? PAI_FOLD_ROWS_MAX_2048 : k == 296 ? PAI_FOLD_ROWS_MAX_4096 : 0;
+}
+
+// A host-buffer fold decides rows or groups once, by the outputs of the whole call: its chunks run one after the other
+// on one stream, so a call above the threshold gains nothing from chunks that happen to lie below it.
+struct FoldCall {
+  pai_ctx* c;
+  FoldCall(pai_ctx* ctx, size_t outputs) : c(ctx) { c->fold_call_n = (long long)outputs; }
+  ~FoldCall() { c->fold_call_n = 0; }
+};
+
+// One fold over p.n outputs: k_pack_fold_w on 16-lane rows for calls of few outputs, k_pack_fold on lane groups
+// otherwise. No scratch, no inversion, nothing read back; the constants are filled here.
+static int fold_run(pai_ctx* c, PackFoldParams& p, hipStream_t st) {
+  p.N = c->d_N;
+  p.R2 = c->d_R2;
+  p.oneR = c->d_oneR;
+  p.mprime = c->mprime_N;
+  p.ct_words = c->ct_words;
+  const long long total = c->fold_call_n ? c->fold_call_n : p.n;
+  const bool rows = foldw_has(c->S_e) && (c->fold_rows == 2 || (c->fold_rows == 1 && total <= fold_rows_max(c->S_e)));
+  if (rows) {
+    HIPCHK(foldw_launch(c->S_e, p, st));
+    c->fold_path = 2;
+    return 0;
+  }
+  int occ = 1;
+  if (fold_occupancy(c->tpi_e, &occ)) return fail(PAI_ERR_KEY, "unsupported group size");
+  const int gpb = BLOCK / c->tpi_e;
+  const int grid = (int)std::max<long long>(1, std::min<long long>((p.n + gpb - 1) / gpb, (long long)occ * c->cus));
+  HIPCHK(fold_launch(c->tpi_e, p, grid, st));
+  c->fold_path = 1;
+  return 0;
+}
+
+// Packed ciphertexts folded into wider ones (include/flexpai.h pai_repack): k_pack_fold's walk with the stride s sb and
+// no exponents. Every argument is checked before the launch.
+int pai_repack_dev(pai_ctx* c, const uint32_t* d_ct, size_t N, const pai_pack_layout* in_layout, int group,
+                   uint32_t* d_out, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  PackLayout lay;
+  int rc = pack_layout(c, in_layout, &lay);
+  if (rc) return rc;
+  if (group < 1 || (long long)lay.k * group > (c->nb - 2) / lay.sb)
+    return fail(PAI_ERR_ARG, "pai_repack: slots * group must be in [slots, (key_bits - 2) / slot_bits]");
+  if (N == 0) return 0;
+  if (!d_ct || !d_out) return fail(PAI_ERR_ARG, "pai_repack_dev: bad arguments");
+  const size_t W = c->ct_words, C = (N + group - 1) / group;
+  if (d_out < d_ct + N * W && d_ct < d_out + C * W)
+    return fail(PAI_ERR_ARG, "pai_repack_dev: d_out must not overlap d_ct");
+  HIPCHK(hipSetDevice(c->device));
+  PackFoldParams p{};
+  p.ct = d_ct;
+  p.exp = nullptr;
+  p.nvals = (long long)N;
+  p.lay = PackLayout{lay.sb, lay.vb, lay.fexp, group};
+  p.stride = lay.k * lay.sb;
+  p.out = d_out;
+  p.status = nullptr;
+  p.n = (long long)C;
+  return fold_run(c, p, (hipStream_t)stream);
+}
+
+// One fold over the ceil(N / slots) outputs.
 int pai_pack_ciphertexts_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N,
                              const pai_pack_layout* layout, uint32_t* d_out, int32_t* d_status, void* stream) {
   if (!c) return fail(PAI_ERR_ARG, "null ctx");
@@ -4100,25 +4178,16 @@ int pai_pack_ciphertexts_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_
   if (d_out < d_ct + N * W && d_ct < d_out + C * W)
     return fail(PAI_ERR_ARG, "pai_pack_ciphertexts_dev: d_out must not overlap d_ct");
   HIPCHK(hipSetDevice(c->device));
-  int occ = 1;
-  if (fold_occupancy(c->tpi_e, &occ)) return fail(PAI_ERR_KEY, "unsupported group size");
-  const int gpb = BLOCK / c->tpi_e;
   PackFoldParams p{};
   p.ct = d_ct;
   p.exp = d_exp;
   p.nvals = (long long)N;
   p.lay = lay;
+  p.stride = lay.sb;
   p.out = d_out;
   p.status = d_status;
   p.n = (long long)C;
-  p.N = c->d_N;
-  p.R2 = c->d_R2;
-  p.oneR = c->d_oneR;
-  p.mprime = c->mprime_N;
-  p.ct_words = c->ct_words;
-  const int grid = (int)std::max<long long>(1, std::min<long long>((p.n + gpb - 1) / gpb, (long long)occ * c->cus));
-  HIPCHK(fold_launch(c->tpi_e, p, grid, (hipStream_t)stream));
-  return 0;
+  return fold_run(c, p, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ host-buffer entry points
@@ -6375,6 +6444,7 @@ int pai_pack_ciphertexts(pai_ctx* c, const uint32_t* ct, const int32_t* exp, siz
   int32_t* dst = cv.take<int32_t>(N);
   hipStream_t sc = c->s_comp, sy = c->s_copy;
   HostCall hc(c);
+  FoldCall fc(c, C);
   HIPCHK(hipMemcpyAsync(dexp, exp, N * 4, hipMemcpyHostToDevice, sc));
   for (int i = 0; i < nch; ++i) {
     const size_t off = (size_t)i * CH, n = std::min(CH, C - off), v0 = off * K, nv = std::min(n * K, N - v0);
@@ -6390,6 +6460,47 @@ int pai_pack_ciphertexts(pai_ctx* c, const uint32_t* ct, const int32_t* exp, siz
   }
   HIPCHK(hipMemcpyAsync(ct_out, dout, C * W * 4, hipMemcpyDeviceToHost, sc));
   if (status_out) HIPCHK(hipMemcpyAsync(status_out, dst, N * 4, hipMemcpyDeviceToHost, sc));
+  HIPCHK(hipStreamSynchronize(sc));
+  return 0;
+}
+
+// Chunks of whole outputs (multiples of `group` inputs), as pai_pack_ciphertexts: the inputs of chunk i + 1 go up through
+// the pinned slots while chunk i folds; the outputs come down at the end.
+int pai_repack(pai_ctx* c, const uint32_t* ct, size_t N, const pai_pack_layout* in_layout, int group, uint32_t* ct_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  PackLayout lay;
+  int rc = pack_layout(c, in_layout, &lay);
+  if (rc) return rc;
+  if (group < 1 || (long long)lay.k * group > (c->nb - 2) / lay.sb)
+    return fail(PAI_ERR_ARG, "pai_repack: slots * group must be in [slots, (key_bits - 2) / slot_bits]");
+  if (N == 0) return 0;
+  if (!ct || !ct_out) return fail(PAI_ERR_ARG, "pai_repack: null buffer");
+  const size_t W = c->ct_words, K = (size_t)group, C = (N + K - 1) / K;
+  if (ranges_overlap(ct, N * W * 4, ct_out, C * W * 4)) return fail(PAI_ERR_ARG, "pai_repack: ct_out must not overlap ct");
+  HIPCHK(hipSetDevice(c->device));
+  size_t CH;
+  int nch;
+  if ((rc = host_pipe(c, C, carve_bytes({N * W * 4, C * W * 4}), K * W * 4, &CH, &nch))) return rc;
+  Carve cv{(char*)c->d_hostio};
+  uint32_t* dct = cv.take<uint32_t>(N * W);
+  uint32_t* dout = cv.take<uint32_t>(C * W);
+  hipStream_t sc = c->s_comp, sy = c->s_copy;
+  HostCall hc(c);
+  FoldCall fc(c, C);
+  for (int i = 0; i < nch; ++i) {
+    const size_t off = (size_t)i * CH, n = std::min(CH, C - off), v0 = off * K, nv = std::min(n * K, N - v0);
+    if (i >= 2) HIPCHK(hipEventSynchronize(c->hev[i - 2]));   // the slot's previous upload is done
+    par_copy(c->h_pin[i & 1], ct + v0 * W, nv * W * 4);
+    HIPCHK(hipMemcpyAsync(dct + v0 * W, c->h_pin[i & 1], nv * W * 4, hipMemcpyHostToDevice, sy));
+    HIPCHK(hipEventRecord(c->hev[i], sy));
+    HIPCHK(hipStreamWaitEvent(sc, c->hev[i], 0));
+    if ((rc = pai_repack_dev(c, dct + v0 * W, nv, in_layout, group, dout + off * W, sc))) {
+      (void)hipStreamSynchronize(sc);
+      return rc;
+    }
+  }
+  HIPCHK(hipMemcpyAsync(ct_out, dout, C * W * 4, hipMemcpyDeviceToHost, sc));
   HIPCHK(hipStreamSynchronize(sc));
   return 0;
 }

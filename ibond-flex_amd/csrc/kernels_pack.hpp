@@ -184,11 +184,15 @@ __global__ __launch_bounds__(BLOCK, 2) void k_pack_mul(PackMulParams p) {
 // the others multiply by 1 (R in the Montgomery domain). Nothing is squared before the wave's first injection, so the
 // top slot costs its own 4 D squarings and a ragged output starts at its own top slot. Per slot: sb squarings, one
 // product by R^2 that takes c_j into the Montgomery domain, one product into acc.
+// pai_repack is the same walk over PACKED inputs: slot j of an output is a whole input ciphertext of s slots, so the
+// distance between two slots is stride = s sb bits (not bounded by 64 like sb), there are no exponents (exp is null:
+// every D_j = 0) and lay.k counts the inputs per output.
 struct PackFoldParams {
-  const uint32_t* ct;     // [nvals][ct_words] ordinary ciphertexts
-  const int32_t* exp;     // [nvals]; PAD_EXP: the ciphertext 1 of an empty segment
+  const uint32_t* ct;     // [nvals][ct_words] ciphertexts
+  const int32_t* exp;     // [nvals]; PAD_EXP: the ciphertext 1 of an empty segment; null: every shift is 0
   long long nvals;
   PackLayout lay;
+  int stride;             // bits between neighbouring slots of an output: lay.sb, or s sb for pai_repack
   uint32_t* out;          // [n][ct_words]
   int32_t* status;        // [nvals], nullable
   long long n;            // outputs: ceil(nvals / k)
@@ -203,6 +207,7 @@ struct PackFoldParams {
 __device__ __forceinline__ int fold_shift(const PackFoldParams& p, long long ci, int j, bool record) {
   const long long i = ci * p.lay.k + j;
   if (i >= p.nvals) return -1;
+  if (!p.exp) return 0;
   const int32_t e = p.exp[i];
   int st = ST_OK, d4 = -1;
   if (e != PAD_EXP) {
@@ -226,7 +231,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_pack_fold(PackFoldParams p) {
   uint32_t* park = smem + (GPB + gib) * S;            // second slot of the group: acc during an injection
   uint32_t m[L];
   load_limbs_g<TPI>(p.N, m, tig);
-  const int sb = p.lay.sb, k = p.lay.k;
+  const int sb = p.stride, k = p.lay.k;
 
   for (long long base = (long long)blockIdx.x * GPB; base < p.n; base += (long long)gridDim.x * GPB) {
     const long long inst = base + gib;

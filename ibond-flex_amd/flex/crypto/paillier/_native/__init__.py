@@ -37,6 +37,7 @@ PAI_OPT_SEGDOT_FUSED, PAI_OPT_SEGDOT_PATH = 20, 21     # 19 is not assigned
 PAI_OPT_POOL_FUSED = 22
 PAI_BIN_U8, PAI_BIN_U16 = 0, 1
 PAI_OPT_SCAN_TILE, PAI_OPT_SCAN_PATH = 23, 24
+PAI_OPT_FOLD_ROWS, PAI_OPT_FOLD_PATH = 25, 26
 PAI_SCAN_REVERSE = 1
 HIST_RUN = 64          # PAI_HIST_RUN: members of a histogram cell that one k_hist_acc instance sums
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
@@ -54,7 +55,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_next_prime", "pai_prime_last_times", "pai_prime_test", "pai_debug_prime_sieve",
             "pai_obfuscate", "pai_obfuscate_dev",
             "pai_pack_max_slots", "pai_encrypt_packed", "pai_encrypt_packed_dev", "pai_decrypt_packed",
-            "pai_decrypt_packed_dev", "pai_pack_ciphertexts", "pai_pack_ciphertexts_dev",
+            "pai_decrypt_packed_dev", "pai_pack_ciphertexts", "pai_pack_ciphertexts_dev", "pai_repack", "pai_repack_dev",
             "pai_segment_dot", "pai_segment_dot_dev", "pai_histogram", "pai_histogram_dev",
             "pai_histogram_sparse", "pai_histogram_sparse_dev",
             "pai_cumsum", "pai_cumsum_dev",
@@ -128,6 +129,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_decrypt_packed_dev.argtypes = [P, P, P, S, P, P, P, P]
         lib.pai_pack_ciphertexts.argtypes = [P, P, P, S, P, P, P]
         lib.pai_pack_ciphertexts_dev.argtypes = [P, P, P, S, P, P, P, P]
+        lib.pai_repack.argtypes = [P, P, S, P, I, P]
+        lib.pai_repack_dev.argtypes = [P, P, S, P, I, P, P]
         lib.pai_mul.argtypes = [P, P, P, S, I, P, S, P, P, P]
         lib.pai_mul_dev.argtypes = [P, P, P, S, I, P, S, P, P, P, P]
         lib.pai_add_plain.argtypes = [P, P, P, S, I, P, S, P, P, P]
@@ -553,6 +556,20 @@ class Context:
         return int(self._get_option(PAI_OPT_SCAN_PATH))
 
     @property
+    def fold_rows(self) -> int:
+        """pack_ciphertexts / repack on 16-lane rows: 1 = automatic (calls of few outputs), 0 = never, 2 = always."""
+        return int(self._get_option(PAI_OPT_FOLD_ROWS))
+
+    def set_fold_rows(self, mode: int):
+        """0: lane groups only; 1: automatic; 2: rows wherever a row kernel exists. Same bits for every value."""
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_FOLD_ROWS, int(mode)))
+
+    @property
+    def fold_path(self) -> int:
+        """The path of this context's last pack_ciphertexts or repack call: 0 = none yet, 1 = lane groups, 2 = rows."""
+        return int(self._get_option(PAI_OPT_FOLD_PATH))
+
+    @property
     def obf_chunk(self) -> int:
         """Elements per slice of an in-place pai_obfuscate_dev (default 262 144)."""
         return int(self._get_option(PAI_OPT_OBF_CHUNK))
@@ -900,6 +917,18 @@ class Context:
         self.calls["pai_pack_ciphertexts"] += 1
         self._chk(self.lib.pai_pack_ciphertexts(self._h, _ptr(ct), _ptr(exp), N, ctypes.byref(lay), _ptr(out), _ptr(st)))
         return out, st
+
+    def repack(self, ct: np.ndarray, layout, group: int) -> np.ndarray:
+        """pai_repack: fold the N packed ciphertexts ct [N, ct_words] under `layout`, `group` at a time, into
+        ceil(N / group) ciphertexts of layout.slots * group slots. Returns words [C, ct_words]."""
+        ct = np.ascontiguousarray(ct, dtype=np.uint32)
+        if ct.ndim != 2 or ct.shape[1] != self.ct_words:
+            raise ValueError(f"ciphertext buffer shape {ct.shape} does not match (N, {self.ct_words})")
+        lay, group, N = pack_layout(layout), int(group), ct.shape[0]
+        out = np.empty((-(-N // group) if group > 0 else 0, self.ct_words), dtype=np.uint32)
+        self.calls["pai_repack"] += 1
+        self._chk(self.lib.pai_repack(self._h, _ptr(ct), N, ctypes.byref(lay), group, _ptr(out)))
+        return out
 
     def add(self, cts: Sequence[np.ndarray], exps: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
         k = len(cts)

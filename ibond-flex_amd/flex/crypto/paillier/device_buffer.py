@@ -276,6 +276,17 @@ def pack_dev(pk, words: DeviceWords, exps, layout):
     return out, st.download(np.int32, N)
 
 
+def repack_dev(pk, words: DeviceWords, layout, group: int) -> DeviceWords:
+    """pai_repack_dev: packed words [N, W] under `layout`, `group` at a time -> [ceil(N / group), W]."""
+    (N, W), dev = words.shape, words.device
+    ctx = context_on(pk, dev)
+    lay, group = _native.pack_layout(layout), int(group)
+    out = DeviceWords.empty(-(-N // group), W, dev)
+    if N:
+        ctx.dev_call("pai_repack_dev", words.ptr, N, ctypes.byref(lay), group, out.ptr)
+    return out
+
+
 def decrypt_dev(pk, private_key, words: DeviceWords, exps, want_raw: bool = False):
     """pai_decrypt_dev: (val float64, mant int64, statuses, raw words or None) on the host; no ciphertext word comes
     back."""

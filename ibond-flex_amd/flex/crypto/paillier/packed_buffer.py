@@ -290,7 +290,12 @@ class PackedCiphertextBuffer(object):
         k, N = self.layout.slots, self.words.shape[0]
         if self.count != N * k:
             raise ValueError(f"histogram: {self.count} values do not fill {N} ciphertexts of {k} slots (one ciphertext "
-                             "per sample)")
+                             "per sample; a buffer after repack() no longer has one)")
+        # After repack() a ciphertext holds several whole rows of the last axis (k = slots of a row * g), and count can be
+        # a multiple of k again (300 samples of 2 slots at g = 10: 30 ciphertexts of 20): each would mix g samples.
+        if len(self.shape) >= 2 and self.shape[-1] != k and self.shape[-1] > 0 and k % self.shape[-1] == 0:
+            raise ValueError(f"histogram: a ciphertext of {k} slots spans {k // self.shape[-1]} rows of shape {self.shape}: "
+                             "one ciphertext per sample is needed (repack() goes after histogram)")
         # A resident buffer whose bound times ALL its samples fits the slot cannot overflow whatever the cells are: that
         # check replaces the host-side count (22 ms for 262 144 x 16 bin ids, more than the kernels), and the counts the
         # device returns give the same exact bound afterwards. Every other case counts on the host first, as before.
@@ -327,13 +332,46 @@ class PackedCiphertextBuffer(object):
         from .cipher_buffer import axis_split, cumsum_words
         k, C = self.layout.slots, self.words.shape[0]
         if len(self.shape) < 2 or self.shape[-1] != k or self.count != C * k:
-            raise ValueError(f"cumsum: shape {self.shape} is not (..., {k}) with one ciphertext per index of the leading axes")
+            raise ValueError(f"cumsum: shape {self.shape} is not (..., {k}) with one ciphertext per index of the leading axes "
+                             "(repack() goes after cumsum)")
         lead = self.shape[:-1]
         outer, L, inner = axis_split(lead, axis)
         bound = self.bound * L
         self._check_bound(bound)
         out, _ = cumsum_words(self.public_key, self.words, self._exps(), outer, L, inner, bool(reverse))
         return self._like(out, bound)
+
+    def repack(self, slots: Optional[int] = None) -> "PackedCiphertextBuffer":
+        """The same values in fewer, fuller ciphertexts (SecureBoost+'s cipher compression): `slots` per ciphertext, a
+        multiple of layout.slots (default: the largest that fits (key_bits - 2) // slot_bits), from ONE pai_repack call,
+        out_c = prod_j c_(c g + j)^(2^(layout.slots slot_bits j)) with g = slots // layout.slots; needs the public key
+        only. Value i stays value i: count, shape and bound are kept, the layout becomes (slot_bits, value_bits, exponent,
+        slots), and decrypt gives exactly what it gives for this buffer. The result is NOT re-randomised
+        (obfuscated=False; to_wire(be_secure=True) does that), so repack goes after the last histogram / cumsum / take --
+        which address whole ciphertexts along axes of `shape` and refuse a repacked buffer -- and before the
+        re-randomisation. slots == layout.slots returns self; a resident buffer stays resident."""
+        lay = self.layout
+        s, most = lay.slots, (lay.key_bits - 2) // lay.slot_bits
+        slots = most // s * s if slots is None else int(slots)
+        if slots < s or slots % s:
+            raise ValueError(f"repack: slots must be a multiple of the layout's {s} slots, not {slots}")
+        if slots > most:
+            raise ValueError(f"repack: {slots} slots of {lay.slot_bits} bits do not fit a {lay.key_bits}-bit key (at most {most})")
+        if slots == s:
+            return self
+        g = slots // s
+        if self.resident:
+            from .device_buffer import repack_dev
+            out = repack_dev(self.public_key, self.words, lay, g)
+        elif self.words.shape[0] == 0:
+            out = self.words
+        elif _gpu():
+            from . import _runtime
+            out = _runtime.context(self.public_key).repack(self.words, lay, g)
+        else:
+            out = _to_words(host_repack(_ints(self.words), lay, g, self.public_key), self.words.shape[1])
+        wide = PackedLayout(self.public_key, lay.slot_bits, lay.value_bits, lay.exponent, slots)
+        return PackedCiphertextBuffer(self.public_key, out, wide, self.count, self.shape, False, self.bound)
 
     def apply_obfuscation(self) -> "PackedCiphertextBuffer":
         """Re-randomise every ciphertext in ONE pai_obfuscate call, unless the flag is already set. Returns self."""
@@ -378,7 +416,8 @@ class PackedCiphertextBuffer(object):
         from .cipher_buffer import axis_split
         k, C = self.layout.slots, self.words.shape[0]
         if len(self.shape) < 2 or self.shape[-1] != k or self.count != C * k:
-            raise ValueError(f"take: shape {self.shape} is not (..., {k}) with one ciphertext per index of the leading axes")
+            raise ValueError(f"take: shape {self.shape} is not (..., {k}) with one ciphertext per index of the leading axes "
+                             "(repack() goes after take)")
         lead = self.shape[:-1]
         axis_split(lead, axis)                                                  # (the axis rules; the slot axis is out)
         idx = np.take(np.arange(C, dtype=np.int64).reshape(lead), indices, axis=axis)
@@ -520,6 +559,18 @@ def host_pack_ciphertexts(cts: Sequence[int], exps: Sequence[int], layout: Packe
             st.append(0)
             out[i // k] = out[i // k] * _bigint.powmod(int(c), 1 << (4 * d + sb * (i % k)), nsq) % nsq
     return out, np.array(st, dtype=np.int32)
+
+
+def host_repack(cts: Sequence[int], layout: PackedLayout, group: int, pub_key):
+    """pai_repack on Python integers: packed ciphertext c_i under `layout` contributes c_i^(2^(slots slot_bits j)) to
+    output i // group, j = i % group."""
+    nsq, g, stride = pub_key.nsquare, int(group), layout.slots * layout.slot_bits
+    if g < 1 or layout.slots * g > (layout.key_bits - 2) // layout.slot_bits:
+        raise ValueError("repack: slots * group must be in [slots, (key_bits - 2) // slot_bits]")
+    out = [1] * -(-len(cts) // g)
+    for i, c in enumerate(cts):
+        out[i // g] = out[i // g] * _bigint.powmod(int(c), 1 << (stride * (i % g)), nsq) % nsq
+    return out
 
 
 def _slot_bound(layout: PackedLayout, max_abs, terms: int = 1) -> int:

@@ -250,6 +250,16 @@ def histogram_packed(x, bins, n_bins, layout, max_abs, node=None, n_nodes=1, def
     return _fold(pk, out, np.ascontiguousarray(oe, dtype=np.int32), layout, bound, shape), cnt.reshape(shape)
 
 
+def repack(buf, slots=None):
+    """PackedCiphertextBuffer.repack: the values of a packed buffer (what histogram_packed, or a packed g/h buffer's
+    histogram and cumsum, return) in fewer, fuller ciphertexts of `slots` slots (default: as many as the key holds), in
+    ONE pai_repack call; after the last cumsum, before to_wire(be_secure=True)."""
+    from .packed_buffer import PackedCiphertextBuffer
+    if not isinstance(buf, PackedCiphertextBuffer):
+        raise TypeError(f"unsupported operand {type(buf)} for repack")
+    return buf.repack(slots)
+
+
 def good_bad_calc(y: np.ndarray, index_lists):
     """HeteroBin.en_good_bad_calc (hetero_bin.py:27-36) on the GPU: good_s = sum(y[i]), bad_s = len(i) -
     good_s for every bin; returns the two numpy arrays the reference builds."""

@@ -214,6 +214,22 @@ typedef struct pai_comm pai_comm;
                                   * every level of the scan (T >= L: row chains). Same bits for every value */
 #define PAI_OPT_SCAN_PATH 24     /* read-only: the path of this context's last pai_cumsum[_dev] call: 0 = none yet,
                                   * 1 = row chains, 2 = blocked scan                                             */
+#define PAI_OPT_FOLD_ROWS 25     /* pai_pack_ciphertexts[_dev] and pai_repack[_dev]: 1 (default) automatic -- calls of at
+                                  * most PAI_FOLD_ROWS_MAX_<key bits> outputs fold on 16-lane rows (k_pack_fold_w,
+                                  * csrc/kernels_foldw.hpp), larger ones on lane groups (k_pack_fold); 0: never rows; 2:
+                                  * rows wherever a row kernel exists (n^2 of 74, 148 or 296 limbs of 28 bits). A host-buffer
+                                  * call decides once, by the outputs of the whole call, whatever its chunks. Same bits
+                                  * for every value */
+#define PAI_OPT_FOLD_PATH 26     /* read-only: the path of this context's last pai_pack_ciphertexts[_dev] or
+                                  * pai_repack[_dev] call: 0 = none yet, 1 = lane groups, 2 = rows               */
+/* The automatic choice of PAI_OPT_FOLD_ROWS: the largest output count at which the row kernel was more than 5 % faster
+ * than the group kernel in the same-process A/B of tools/fold_ab.py on an MI355X (profiles/fold_ab.json),
+ * per key size (n^2 of 74 / 148 / 296 limbs). 0: that key size stays on lane groups. Measured at 64, 1 024, 4 096, 16 384
+ * and 65 536 outputs, rows / groups for pai_pack_ciphertexts and pai_repack alike: 0.24, 0.24, 0.26, 0.79, 1.47 at 1024
+ * bits; 0.36, 0.36, 0.37, 1.16, 1.21 at 2048; 0.68, 0.68, 0.68, 1.12, 1.06 at 4096. */
+#define PAI_FOLD_ROWS_MAX_1024 16384
+#define PAI_FOLD_ROWS_MAX_2048 4096
+#define PAI_FOLD_ROWS_MAX_4096 4096
 
 /* Number of visible GPUs (0 when there is none or the runtime cannot start). */
 int pai_device_count(int* count);
@@ -593,11 +609,31 @@ int pai_decrypt_packed_dev(pai_ctx* ctx, const uint32_t* d_ct, const pai_pack_la
  * d_out overlapping d_ct is PAI_ERR_ARG. The _dev call never waits on the host (no inversion, no scratch: capturable),
  * takes the context lock and chains on the previous call's event like its neighbours; the host-buffer call chunks at
  * multiples of k values, like pai_encrypt_packed. Per output (k - 1) sb + 2 k + 1 products mod n^2 depend on each other, so a
- * call of few outputs is latency-bound, like one public exponentiation. */
+ * call of few outputs is latency-bound, like one public exponentiation: such calls run the chain on 16-lane rows
+ * (PAI_OPT_FOLD_ROWS), with the same bits. */
 int pai_pack_ciphertexts(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N,
                          const pai_pack_layout* layout, uint32_t* ct_out, int32_t* status_out);
 int pai_pack_ciphertexts_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N,
                              const pai_pack_layout* layout, uint32_t* d_out, int32_t* d_status, void* stream);
+/* Repack PACKED ciphertexts into fewer, fuller ones (SecureBoost+'s cipher compression on top of g/h packing: a
+ * histogram cell carries 2 slots of the ~nb - 2 plaintext bits). Needs the public key only. The N inputs are packed
+ * ciphertexts under in_layout = (sb, vb, e, s), validated as above; input j of output c is ct[c g + j], g = group >= 1
+ * with s g <= floor((nb - 2) / sb). ct_out holds ceil(N / g) * W words under the layout (sb, vb, e, s g): value i of the
+ * input buffer is value i of the output buffer (ciphertext i / (s g), slot i % (s g)).
+ * Bits: out_c = prod_j ct[c g + j]^(2^(s sb j)) mod n^2, canonical (below n^2): the bits of the reference's
+ *   sum(c_j * (1 << (s sb j))) through PaillierEncryptedNumber.__mul__ and __add__ at one exponent. A packed ciphertext
+ *   encrypts the signed integer M_j, so the product encrypts sum_j M_j 2^(s sb j), the plaintext pai_decrypt_packed
+ *   decodes under (sb, vb, e, s g); negative M_j work because m_j == M_j (mod n). Inputs past N are the factor 1. No
+ *   exponents are passed; the output is NOT re-randomised (pai_obfuscate does that afterwards). The stride s sb is
+ *   internal to this entry: a slot of any other entry stays at most 64 bits wide.
+ * PAI_ERR_ARG before any launch: a null pointer, group < 1, an invalid in_layout, s g above the bound, an output that
+ * overlaps the input. N = 0 is PAI_OK. The _dev call takes the context lock, chains on the previous call's event, never
+ * waits on the host and needs no scratch; the host-buffer call chunks at multiples of g inputs. The kernel is
+ * pai_pack_ciphertexts' (PAI_OPT_FOLD_ROWS / PAI_OPT_FOLD_PATH): (g - 1) s sb + 2 g + 1 dependent products per output. */
+int pai_repack(pai_ctx* ctx, const uint32_t* ct, size_t N, const pai_pack_layout* in_layout, int group,
+               uint32_t* ct_out);
+int pai_repack_dev(pai_ctx* ctx, const uint32_t* d_ct, size_t N, const pai_pack_layout* in_layout, int group,
+                   uint32_t* d_out, void* stream);
 
 /* Obfuscator pool: r^n drawn ahead of time (no reference counterpart: the reference draws r and raises it to n inside
  * every encrypt, obfuscator.py:23-37). r^n does not depend on the plaintext, so a party draws obfuscators while it waits

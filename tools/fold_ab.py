@@ -17,6 +17,18 @@ against the chip's 35.13 T lane-MAC/s scaled to the SIMDs the call's blocks occu
 ciphertext words on the wire. Writes profiles/fold_ab.json (--out) and prints it.
 
     python tools/fold_ab.py [--rounds 3] [--size 262144] [--out profiles/fold_ab.json]
+
+--rows: the A/B of the fold's two kernels instead, k_pack_fold_w on 16-lane rows against k_pack_fold on lane groups, for
+the threshold of PAI_OPT_FOLD_ROWS (include/flexpai.h PAI_FOLD_ROWS_MAX_*). One process, one library, public contexts;
+the two paths alternate through PAI_OPT_FOLD_ROWS = 0 / 2 and PAI_OPT_FOLD_PATH is checked after every call; HIP events
+around pai_pack_ciphertexts_dev (32-bit slots, k = 63, or the 31 that fit a 1024-bit key) and pai_repack_dev (s = 2,
+sb = 48, the largest g) on a side stream; one warm-up pass, then --rounds rounds, medians; 64, 1 024, 4 096, 16 384 and
+65 536 outputs (--counts) at 1024, 2048 and 4096 bits (--bits). The inputs are random residues below n^2 (the chains do
+not depend on the data); the two paths' outputs are compared once per cell. Per key size and entry point the table
+gives rows / groups and the largest count at which the rows are more than 5 % faster; the result is merged into --out
+under "rows_ab" (the record above stays).
+
+    python tools/fold_ab.py --rows [--rounds 3] [--bits 1024,2048,4096] [--counts 64,1024,4096,16384,65536]
 """
 import argparse
 import ctypes
@@ -36,12 +48,102 @@ PEAK_LANE_MACS = 35.13e12          # the chip's integer multiply-
 TPI = {1024: 2, 2048: 4, 4096: 8}
 
 
+def rows_ab(args):
+    from flex.crypto.paillier import _native as N
+    with open(os.path.join(ROOT, "tests", "golden", "paillier_golden.json")) as f:
+        keys = json.load(f)["keys"]
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    stream = torch.cuda.Stream(dev)
+    s = stream.cuda_stream
+    lib = N.load_library()
+    counts = [int(v) for v in args.counts.split(",")]
+    result = {"device": torch.cuda.get_device_name(dev), "rounds": args.rounds, "counts": counts, "margin": 0.05,
+              "keys": {}}
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record(stream)
+        fn()
+        t1.record(stream)
+        t1.synchronize()
+        return t0.elapsed_time(t1)
+
+    for nb in (int(v) for v in args.bits.split(",")):
+        ctx = N.Context(int(keys[str(nb)]["n"], 16), 0)
+        W = ctx.ct_words
+        k = min(63, (nb - 2) // 32)
+        g = (nb - 2) // 48 // 2
+        entries = {"pack_ciphertexts": (k, N.pack_layout((32, 32, 0, k))), "repack": (g, N.pack_layout((48, 48, 0, 2)))}
+        most = max(counts) * max(k, g)
+        gen = torch.Generator(device=dev).manual_seed(nb)
+        ct = torch.randint(-(1 << 31), (1 << 31) - 1, (most, W), generator=gen, dtype=torch.int32, device=dev)
+        ct[:, W - 1] = 0                                       # below 2^(32 (W - 1)) < n^2
+        ex = torch.zeros(most, dtype=torch.int32, device=dev)
+        outs = {m: torch.empty((max(counts), W), dtype=torch.int32, device=dev) for m in (0, 2)}
+        torch.cuda.synchronize()
+        per_key = {}
+        for name, (per, lay) in entries.items():
+            cells = []
+            for C in counts:
+                n_in = C * per
+
+                def call(mode):
+                    ctx.set_fold_rows(mode)
+                    if name == "repack":
+                        rc = lib.pai_repack_dev(ctx.handle, ct.data_ptr(), n_in, ctypes.byref(lay), per,
+                                                outs[mode].data_ptr(), s)
+                    else:
+                        rc = lib.pai_pack_ciphertexts_dev(ctx.handle, ct.data_ptr(), ex.data_ptr(), n_in, ctypes.byref(lay),
+                                                          outs[mode].data_ptr(), None, s)
+                    assert rc == 0, lib.pai_last_error()
+                    assert ctx.fold_path == (2 if mode == 2 else 1)
+
+                ms = {0: [], 2: []}
+                for rnd in range(args.rounds + 1):             # round 0 is the warm-up
+                    for mode in (0, 2):
+                        t = timed(lambda: call(mode))
+                        if rnd:
+                            ms[mode].append(t)
+                same = bool(torch.equal(outs[0][:C], outs[2][:C]))
+                grp, row = statistics.median(ms[0]), statistics.median(ms[2])
+                cell = {"outputs": C, "inputs_per_output": per, "same_words": same,
+                        "groups_ms": [round(v, 3) for v in ms[0]], "rows_ms": [round(v, 3) for v in ms[2]],
+                        "groups_median_ms": round(grp, 3), "rows_median_ms": round(row, 3),
+                        "rows_over_groups": round(row / grp, 3)}
+                cells.append(cell)
+                print(json.dumps({"nb": nb, "entry": name, **cell}), flush=True)
+            wins = [c["outputs"] for c in cells if c["rows_median_ms"] < (1 - result["margin"]) * c["groups_median_ms"]]
+            per_key[name] = {"cells": cells, "rows_max": max(wins) if wins else 0}
+        per_key["rows_max"] = min(v["rows_max"] for v in per_key.values())
+        result["keys"][str(nb)] = per_key
+        ctx.set_fold_rows(1)
+        ctx.close()
+        del ct, ex, outs
+        torch.cuda.empty_cache()
+    merged = {}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            merged = json.load(f)
+    merged["rows_ab"] = result
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(merged, f, indent=1)
+        f.write("\n")
+    print(json.dumps({nb: v["rows_max"] for nb, v in result["keys"].items()}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--size", type=int, default=1 << 18)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fold_ab.json"))
+    ap.add_argument("--rows", action="store_true")
+    ap.add_argument("--bits", default="1024,2048,4096")
+    ap.add_argument("--counts", default="64,1024,4096,16384,65536")
     args = ap.parse_args()
+    if args.rows:
+        return rows_ab(args)
     from flex.crypto.paillier import _native as N
     with open(os.path.join(ROOT, "tests", "golden", "paillier_golden.json")) as f:
         keys = json.load(f)["keys"]
@@ -153,6 +255,9 @@ def main():
         print(json.dumps(row), flush=True)
         del ct, by_slot, pair, acc, folded, val, mant, dst
         torch.cuda.empty_cache()
+    if os.path.exists(args.out):                               # the record of --rows stays
+        with open(args.out) as f:
+            result.update({k: v for k, v in json.load(f).items() if k == "rows_ab"})
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
