@@ -40,6 +40,21 @@ hipError_t check_below_launch(const CheckBelowParams& p, int cus, hipStream_t st
   return hipGetLastError();
 }
 
+hipError_t check_idx_launch(const CheckIdxParams& p, int cus, hipStream_t st) {
+  hipLaunchKernelGGL(k_check_idx, dim3(res_grid(std::max(p.total, p.nseg + 1), cus)), dim3(RES_BLOCK), 0, st, p);
+  return hipGetLastError();
+}
+
+hipError_t seg_offsets_launch(const SegPlanParams& p, hipStream_t st) {
+  hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(SEGPLAN_BLOCK), 0, st, p);
+  return hipGetLastError();
+}
+
+hipError_t seg_rows_launch(const SegRowsParams& p, int cus, hipStream_t st) {
+  hipLaunchKernelGGL(k_seg_rows, dim3(res_grid(p.rows * SEGPLAN_C, cus)), dim3(RES_BLOCK), 0, st, p);
+  return hipGetLastError();
+}
+
 }  // namespace fpai
 
 namespace {

@@ -3755,9 +3755,10 @@ static int run_add(pai_ctx* c, AddParams p, hipStream_t st) {
   HIPCHK(hipMemsetAsync(hist, 0, ADD_TMAX * 4, st));
   hipLaunchKernelGGL(k_add_plan<0>, dim3(g), dim3(256), 0, st, p, bucket, hist);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_add_scan<0>, dim3(1), dim3(ADD_TMAX), 0, st, hist);
+  hipLaunchKernelGGL(k_add_scan<0>, dim3(1), dim3(ADD_TMAX), 0, st, hist, p.gate);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_add_scatter<0>, dim3(g), dim3(256), 0, st, (long long)p.n, (const uint16_t*)bucket, hist, perm);
+  hipLaunchKernelGGL(k_add_scatter<0>, dim3(g), dim3(256), 0, st, (long long)p.n, (const uint16_t*)bucket, hist, perm,
+                     p.gate);
   HIPCHK(hipGetLastError());
   p.perm = perm;
   switch (c->tpi_e) {
@@ -6536,6 +6537,126 @@ int pai_take_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t 
   TakeParams p{d_ct, d_exp, (const long long*)c->d_take, (long long)M, (int)W, d_ct_out, d_exp_out};
   HIPCHK(take_launch(p, c->cus, st));
   HIPCHK(hipStreamSynchronize(st));   // the index is the caller's host memory, and d_take serves the next call
+  return 0;
+}
+
+// ------------------------------------------------------------------ index lists on the device
+// The index (and the segment offsets) are device memory, so nothing here can look at them: k_check_idx runs first on
+// the stream and leaves the smallest offenders in d_bad, and every kernel behind it reads those two words before it
+// touches anything (TakeParams.gate, AddParams.gate, SegPlanParams.gate, SegRowsParams.gate). No wait on the host, no
+// copy to the host, scratch from the context.
+static int check_idx(pai_ctx* c, const int64_t* d_index, size_t total, long long lo, size_t N, const int64_t* d_seg_off,
+                     size_t nseg, int64_t* d_bad, hipStream_t st) {
+  HIPCHK(hipMemsetAsync(d_bad, 0xFF, 16, st));
+  CheckIdxParams p{(const long long*)d_index, (long long)total, lo, (long long)N, (const long long*)d_seg_off,
+                   (long long)nseg, (unsigned long long*)d_bad};
+  HIPCHK(check_idx_launch(p, c->cus, st));
+  return 0;
+}
+
+int pai_take_idx_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_index, size_t M,
+                     int allow_empty, uint32_t* d_ct_out, int32_t* d_exp_out, int64_t* d_bad, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (!d_bad) return fail(PAI_ERR_ARG, "pai_take_idx_dev: null pointer");
+  if (M > 0 && (!d_index || !d_ct_out || !d_exp_out || (N > 0 && (!d_ct || !d_exp))))
+    return fail(PAI_ERR_ARG, "pai_take_idx_dev: null pointer");
+  if (N >= ((size_t)1 << 40) || M >= ((size_t)1 << 40)) return fail(PAI_ERR_ARG, "pai_take_idx_dev: too many rows");
+  const size_t W = c->ct_words;
+  const struct { const void* p; size_t n; } in[] = {{d_ct, N * W * 4}, {d_exp, N * 4}, {d_index, M * 8}, {d_bad, 16}},
+                                            out[] = {{d_ct_out, M * W * 4}, {d_exp_out, M * 4}};
+  for (const auto& o : out)
+    for (const auto& i : in)
+      if (i.n && o.n && ranges_overlap(i.p, i.n, o.p, o.n))
+        return fail(PAI_ERR_ARG, "pai_take_idx_dev: the output overlaps the input");
+  if (M && (ranges_overlap(d_ct_out, M * W * 4, d_exp_out, M * 4) || ranges_overlap(d_bad, 16, d_index, M * 8)))
+    return fail(PAI_ERR_ARG, "pai_take_idx_dev: the output overlaps the input");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  int rc = check_idx(c, d_index, M, allow_empty ? -1 : 0, N, nullptr, 0, d_bad, st);
+  if (rc || M == 0) return rc;
+  TakeParams p{d_ct, d_exp, (const long long*)d_index, (long long)M, (int)W, d_ct_out, d_exp_out, (const long long*)d_bad};
+  HIPCHK(take_launch(p, c->cus, st));
+  return 0;
+}
+
+// The tree of pai_segment_add_dev (parts of SEG_CHUNK members through k_add with gather rows), planned on the device.
+// The host knows `total` and `nseg` only, so it launches LEVELS = the smallest l >= 1 with 16^l >= total levels: no
+// segment is longer than total, so after l - 1 levels every segment is down to at most 16 rows and the last level writes
+// one row per segment. A segment that is finished earlier passes through: a part of one member is that member again
+// (k_add of one operand below n^2 multiplies nothing), so the bits are those of the host-list call. Level k launches
+// k_add over total / 16^(k + 1) + nseg rows, the host's bound on its parts; the rows past the real count gather nothing
+// and write the identity into scratch that nobody reads.
+int pai_segment_add_idx_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_index,
+                            size_t total, const int64_t* d_seg_off, size_t nseg, uint32_t* d_out, int32_t* d_exp_out,
+                            int64_t* d_bad, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (!d_bad || !d_seg_off) return fail(PAI_ERR_ARG, "pai_segment_add_idx_dev: null pointer");
+  if ((nseg > 0 && (!d_out || !d_exp_out)) || (total > 0 && (!d_index || !d_ct || !d_exp)))
+    return fail(PAI_ERR_ARG, "pai_segment_add_idx_dev: null pointer");
+  // k_add numbers its instances with an int (the schedule sort's perm)
+  if (N >= ((size_t)1 << 40) || total >= ((size_t)1 << 40) || nseg >= ((size_t)1 << 30) ||
+      total / SEG_CHUNK + nseg >= ((size_t)1 << 31))
+    return fail(PAI_ERR_ARG, "pai_segment_add_idx_dev: too many rows");
+  const size_t W = c->ct_words;
+  const struct { const void* p; size_t n; } in[] = {{d_ct, N * W * 4}, {d_exp, N * 4}, {d_index, total * 8},
+                                                    {d_seg_off, (nseg + 1) * 8}, {d_bad, 16}},
+                                            out[] = {{d_out, nseg * W * 4}, {d_exp_out, nseg * 4}};
+  for (const auto& o : out)
+    for (const auto& i : in)
+      if (i.n && o.n && ranges_overlap(i.p, i.n, o.p, o.n))
+        return fail(PAI_ERR_ARG, "pai_segment_add_idx_dev: the output overlaps the input");
+  if ((nseg && ranges_overlap(d_out, nseg * W * 4, d_exp_out, nseg * 4)) ||
+      (total && ranges_overlap(d_bad, 16, d_index, total * 8)) || ranges_overlap(d_bad, 16, d_seg_off, (nseg + 1) * 8))
+    return fail(PAI_ERR_ARG, "pai_segment_add_idx_dev: the output overlaps the input");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  int rc = check_idx(c, d_index, total, 0, N, d_seg_off, nseg, d_bad, st);
+  if (rc || nseg == 0) return rc;
+  const int C = SEG_CHUNK;
+  static_assert(SEG_CHUNK == SEGPLAN_C, "the plan kernels cut segments as the host-list call does");
+  int levels = 1;
+  for (size_t cap = C; cap < total; cap *= C) ++levels;
+  const size_t P = total / C + nseg;   // no level has more partial sums
+  const size_t o_a = 0, o_b = align16(o_a + P * W * 4), o_ea = align16(o_b + P * W * 4), o_eb = align16(o_ea + P * 4),
+               o_off = align16(o_eb + P * 4), o_g = align16(o_off + (size_t)(levels - 1) * (nseg + 1) * 8),
+               need = align16(o_g + std::max(P, nseg) * C * 8);
+  if ((rc = ensure_buf(&c->d_seg, &c->seg_bytes, need))) return rc;
+  char* b = (char*)c->d_seg;
+  uint32_t* part[2] = {(uint32_t*)(b + o_a), (uint32_t*)(b + o_b)};
+  int32_t* pexp[2] = {(int32_t*)(b + o_ea), (int32_t*)(b + o_eb)};
+  long long* d_off = (long long*)(b + o_off);
+  long long* d_g = (long long*)(b + o_g);
+  const long long* gate = (const long long*)d_bad;
+  if (levels > 1) {
+    SegPlanParams sp{(const long long*)d_seg_off, (long long)nseg, levels, d_off, gate};
+    HIPCHK(seg_offsets_launch(sp, st));
+  }
+  const uint32_t* in_ct = d_ct;
+  const int32_t* in_e = d_exp;
+  size_t cap = total;   // bound on the rows that enter level k, without the nseg term
+  for (int k = 0; k < levels; ++k) {
+    const bool last = k == levels - 1;
+    cap /= C;
+    const long long rows = last ? (long long)nseg : (long long)(cap + nseg);
+    SegRowsParams rp{};
+    rp.in_off = k == 0 ? (const long long*)d_seg_off : d_off + (size_t)(k - 1) * (nseg + 1);
+    rp.index = k == 0 ? (const long long*)d_index : nullptr;
+    rp.out_off = last ? nullptr : d_off + (size_t)k * (nseg + 1);
+    rp.nseg = (long long)nseg;
+    rp.rows = rows;
+    rp.gidx = d_g;
+    rp.gate = gate;
+    HIPCHK(seg_rows_launch(rp, c->cus, st));
+    uint32_t* o = last ? d_out : part[k & 1];
+    int32_t* oe = last ? d_exp_out : pexp[k & 1];
+    AddParams ap = add_params(in_ct, in_e, C, rows, o, oe, d_g);
+    ap.gate = gate;
+    if ((rc = run_add(c, ap, st))) return rc;
+    in_ct = o;
+    in_e = oe;
+  }
   return 0;
 }
 

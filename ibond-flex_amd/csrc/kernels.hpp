@@ -79,6 +79,9 @@ struct AddParams {
   // segmented sums (pai_segment_add) gather their members this way
   const long long* gidx;
   const int* perm;        // nullable: instance slot t processes instance perm[t] (schedule sort)
+  // nullable: two device words written by a check kernel earlier on the stream (pai_segment_add_idx_dev); the add
+  // kernels write nothing when either is >= 0, so rows gathered through an unchecked device index are never read
+  const long long* gate;
 };
 
 // Per-half (p: h=0, q: h=1) constants for CRT decryption; all LB-bit limb arrays of S limbs.
@@ -364,6 +367,8 @@ __device__ __forceinline__ long long add_src(const AddParams& p, long long e, in
   return p.gidx ? p.gidx[e * p.k + j] : (long long)j * p.n + e;
 }
 __device__ __forceinline__ int add_exp(const AddParams& p, long long src) { return src < 0 ? PAD_EXP : p.exps[src]; }
+// uniform over the grid: every lane reads the same two words
+__device__ __forceinline__ bool add_gate_shut(const long long* gate) { return gate && (gate[0] >= 0 || gate[1] >= 0); }
 
 // Products the Horner schedule of instance e needs (0 for an all-padding instance).
 __device__ __forceinline__ int add_steps(const AddParams& p, long long e, int& E) {
@@ -397,6 +402,7 @@ __device__ __forceinline__ int add_steps(const AddParams& p, long long e, int& E
 
 template <int DUMMY = 0>
 __global__ __launch_bounds__(256) void k_add_plan(AddParams p, uint16_t* bucket, unsigned* hist) {
+  if (add_gate_shut(p.gate)) return;
   __shared__ unsigned h[ADD_TMAX];
   for (int t = threadIdx.x; t < ADD_TMAX; t += blockDim.x) h[t] = 0u;
   __syncthreads();
@@ -413,7 +419,8 @@ __global__ __launch_bounds__(256) void k_add_plan(AddParams p, uint16_t* bucket,
 
 // exclusive prefix sum of the ADD_TMAX bucket counts (one block of ADD_TMAX threads)
 template <int DUMMY = 0>
-__global__ __launch_bounds__(ADD_TMAX) void k_add_scan(unsigned* hist) {
+__global__ __launch_bounds__(ADD_TMAX) void k_add_scan(unsigned* hist, const long long* gate) {
+  if (add_gate_shut(gate)) return;
   __shared__ unsigned v[ADD_TMAX];
   const int t = threadIdx.x;
   v[t] = hist[t];
@@ -428,13 +435,16 @@ __global__ __launch_bounds__(ADD_TMAX) void k_add_scan(unsigned* hist) {
 }
 
 template <int DUMMY = 0>
-__global__ __launch_bounds__(256) void k_add_scatter(long long n, const uint16_t* bucket, unsigned* offs, int* perm) {
+__global__ __launch_bounds__(256) void k_add_scatter(long long n, const uint16_t* bucket, unsigned* offs, int* perm,
+                                                      const long long* gate) {
+  if (add_gate_shut(gate)) return;
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
     perm[atomicAdd(&offs[bucket[e]], 1u)] = (int)e;
 }
 
 template <int TPI>
 __global__ __launch_bounds__(BLOCK, 2) void k_add(AddParams p) {
+  if (add_gate_shut(p.gate)) return;
   constexpr int S = TPI * L;
   constexpr int GPB = BLOCK / TPI;
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];

@@ -61,8 +61,10 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_cumsum", "pai_cumsum_dev",
             "pai_pool_reserve", "pai_pool_fill", "pai_pool_fill_dev", "pai_pool_put", "pai_pool_put_dev", "pai_pool_info",
             "pai_dev_alloc", "pai_dev_free", "pai_dev_upload", "pai_dev_download", "pai_dev_copy", "pai_dev_io_stats",
-            "pai_dev_release_staging", "pai_take_dev", "pai_check_below_dev")
-RESIDENT = EXPORTED[-9:]      # device-resident buffers (include/flexpai.h)
+            "pai_dev_release_staging", "pai_take_dev", "pai_check_below_dev",
+            "pai_take_idx_dev", "pai_segment_add_idx_dev")
+RESIDENT = EXPORTED[-11:-2]   # device-resident buffers (include/flexpai.h)
+DEVICE_INDEX = EXPORTED[-2:]  # take and segment sums over index lists that are device memory
 PAI_COMM_ID_BYTES = 128
 
 _lib = None
@@ -172,8 +174,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.pai_dev_release_staging.argtypes = []
             lib.pai_take_dev.argtypes = [P, P, P, S, P, S, P, P, P]
             lib.pai_check_below_dev.argtypes = [P, P, S, P, P]
+        device_index = hasattr(lib, "pai_take_idx_dev")
+        if device_index:
+            lib.pai_take_idx_dev.argtypes = [P, P, P, S, P, S, I, P, P, P, P]
+            lib.pai_segment_add_idx_dev.argtypes = [P, P, P, S, P, S, P, S, P, P, P, P]
         for name in EXPORTED:
-            if not resident and name in RESIDENT:
+            if (not resident and name in RESIDENT) or (not device_index and name in DEVICE_INDEX):
                 continue
             if name not in ("pai_ctx_destroy", "pai_last_error", "pai_comm_destroy", "pai_release_table_cache"):
                 getattr(lib, name).restype = ctypes.c_int
@@ -730,6 +736,20 @@ class Context:
         """pai_take_dev: out[j] = in[index[j]] (host int64 index; -1: ciphertext 1, exponent INT32_MIN)."""
         index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
         self.dev_call("pai_take_dev", d_ct, d_exp, int(N), _ptr(index), index.size, d_ct_out, d_exp_out)
+
+    def take_idx_dev(self, d_ct: int, d_exp: int, N: int, d_index: int, M: int, allow_empty: bool, d_ct_out: int,
+                     d_exp_out: int, d_bad: int) -> None:
+        """pai_take_idx_dev: out[j] = in[index[j]] for an int64 index in device memory; d_bad names two device int64 words
+        (the smallest bad position or -1; -1). Nothing is waited for."""
+        self.dev_call("pai_take_idx_dev", d_ct, d_exp, int(N), d_index, int(M), 1 if allow_empty else 0, d_ct_out,
+                      d_exp_out, d_bad)
+
+    def segment_add_idx_dev(self, d_ct: int, d_exp: int, N: int, d_index: int, total: int, d_seg_off: int, nseg: int,
+                            d_out: int, d_exp_out: int, d_bad: int) -> None:
+        """pai_segment_add_idx_dev: per-segment sums over an int64 index and nseg + 1 int64 offsets in device memory;
+        d_bad names two device int64 words (the smallest bad index position, the smallest bad offset position, or -1)."""
+        self.dev_call("pai_segment_add_idx_dev", d_ct, d_exp, int(N), d_index, int(total), d_seg_off, int(nseg), d_out,
+                      d_exp_out, d_bad)
 
     def check_below_dev(self, d_ct: int, N: int) -> int:
         """pai_check_below_dev: the smallest i with ct[i] >= n^2, or -1."""

@@ -15,6 +15,11 @@ out. Every result equals the host class's bit for bit (same kernels); the obfusc
 never imports torch: a caller that already holds device memory wraps it with DeviceCiphertextBuffer.from_pointers(...,
 owner=tensor) and reads .data_ptr() / .exps_ptr() for the way back.
 
+Plain operands can stay on the device too: a DeviceArray (device_array(np_array), or DeviceArray.from_pointer(...,
+owner=tensor) for memory somebody else made) is accepted as the int64 index of take / buf[idx] / segment_sum
+(pai_take_idx_dev, pai_segment_add_idx_dev: checked on the device, nothing goes up) and as the dense bins and the node
+ids of histogram, so that a training run uploads its bins once.
+
 This module also holds the word-level device calls (DeviceWords in, DeviceWords out) that cipher_buffer's *_words helpers
 hand a device holder to, which is how PackedCiphertextBuffer.to_device() gets its residency from the same place.
 
@@ -64,6 +69,82 @@ class DeviceWords(object):
     def to_host(self) -> np.ndarray:
         N, W = self.shape
         return self.mem.download(np.uint32, N * W).reshape(N, W)
+
+
+class DeviceArray(object):
+    """A typed plain operand on the device: a DeviceMem, a dtype and a shape (C-contiguous). device_array(a) uploads a
+    numpy array once; DeviceArray.from_pointer wraps memory somebody else owns."""
+    __slots__ = ("mem", "dtype", "shape")
+
+    def __init__(self, mem: "_native.DeviceMem", dtype, shape):
+        self.dtype = np.dtype(dtype)
+        self.shape = tuple(int(v) for v in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+        if any(v < 0 for v in self.shape):
+            raise ValueError(f"DeviceArray: bad shape {self.shape}")
+        if mem.nbytes < self.nbytes:
+            raise ValueError(f"device block of {mem.nbytes} bytes does not hold {self.shape} of {self.dtype}")
+        self.mem = mem
+
+    @classmethod
+    def from_pointer(cls, ptr: int, dtype, shape, owner=None, device: Optional[int] = None) -> "DeviceArray":
+        """Wrap device memory somebody else owns (a torch tensor's data_ptr(), C-contiguous), without a copy. `owner` is
+        kept alive as long as the array; nothing is freed. The memory must be complete before the first call that reads
+        it: the library queues its work on the null stream and knows nothing of the stream that wrote it."""
+        from . import _runtime
+        need_gpu()
+        dev = _runtime.device_index() if device is None else int(device)
+        dt = np.dtype(dtype)
+        shape = tuple(int(v) for v in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+        n = int(np.prod(shape, dtype=np.int64)) if shape else 1
+        return cls(_native.DeviceMem.wrap(ptr, n * dt.itemsize, dev, owner), dt, shape)
+
+    @property
+    def ptr(self) -> int:
+        return self.mem.ptr
+
+    @property
+    def device(self) -> int:
+        return self.mem.device
+
+    @property
+    def size(self) -> int:
+        return int(np.prod(self.shape, dtype=np.int64)) if self.shape else 1
+
+    @property
+    def ndim(self) -> int:
+        return len(self.shape)
+
+    @property
+    def nbytes(self) -> int:
+        return self.size * self.dtype.itemsize
+
+    def to_host(self) -> np.ndarray:
+        """One download (waits for the device's queued work)."""
+        return self.mem.download(self.dtype, self.size).reshape(self.shape)
+
+    def __repr__(self) -> str:
+        return f"DeviceArray(shape={self.shape}, dtype={self.dtype}, device={self.device})"
+
+
+def device_array(a, device: Optional[int] = None) -> DeviceArray:
+    """The numpy array `a` (made C-contiguous) as a DeviceArray: ONE upload, on `device` or the process's device."""
+    from . import _runtime
+    need_gpu()
+    a = np.ascontiguousarray(a)
+    dev = _runtime.device_index() if device is None else int(device)
+    return DeviceArray(_native.device_upload(a, dev), a.dtype, a.shape)
+
+
+def _index_operand(who: str, x, name: str):
+    """A take / segment_sum list as it came: a DeviceArray (int64, any shape for take) or a host integer array."""
+    if isinstance(x, DeviceArray):
+        if x.dtype != np.int64:
+            raise TypeError(f"{who}: a device {name} must be int64, not {x.dtype}")
+        return x
+    a = np.asarray(x)
+    if a.dtype.kind not in "iu" and a.size:
+        raise TypeError(f"{who}: {name} must hold integers")
+    return a.astype(np.int64)
 
 
 def ct_words(public_key) -> int:
@@ -161,6 +242,35 @@ def segment_add_dev(pk, words: DeviceWords, exps, idx: np.ndarray, off: np.ndarr
     return out, oe
 
 
+def take_idx_dev(pk, words: DeviceWords, exps, idx: DeviceArray, allow_empty: bool = False):
+    """pai_take_idx_dev over an int64 DeviceArray: (words [M, W], exponents [M], the smallest bad position or -1). The
+    index does not go up; the two check words (16 bytes) come down."""
+    (N, W), dev = words.shape, words.device
+    if idx.device != dev:
+        raise ValueError(f"the buffer lives on device {dev}, the index on device {idx.device}")
+    ctx = context_on(pk, dev)
+    ex = _exp_mem(exps, N, dev)
+    M = idx.size
+    out, oe, bad = DeviceWords.empty(M, W, dev), _i32(dev, M), _native.DeviceMem(16, dev)
+    ctx.take_idx_dev(words.ptr, ex.ptr, N, idx.ptr, M, allow_empty, out.ptr, oe.ptr, bad.ptr)
+    return out, oe, int(bad.download(np.int64, 2)[0])
+
+
+def segment_add_idx_dev(pk, words: DeviceWords, exps, idx: DeviceArray, off: DeviceArray):
+    """pai_segment_add_idx_dev over int64 DeviceArrays: (words [nseg, W], exponents, (bad index position, bad offset
+    position), each -1 when the lists are good). Empty segments: EMPTY_EXP."""
+    (N, W), dev = words.shape, words.device
+    if idx.device != dev or off.device != dev:
+        raise ValueError(f"the buffer lives on device {dev}, the lists on devices {idx.device} and {off.device}")
+    ctx = context_on(pk, dev)
+    ex = _exp_mem(exps, N, dev)
+    nseg = off.size - 1
+    out, oe, bad = DeviceWords.empty(nseg, W, dev), _i32(dev, nseg), _native.DeviceMem(16, dev)
+    ctx.segment_add_idx_dev(words.ptr, ex.ptr, N, idx.ptr, idx.size, off.ptr, nseg, out.ptr, oe.ptr, bad.ptr)
+    b = bad.download(np.int64, 2)
+    return out, oe, (int(b[0]), int(b[1]))
+
+
 def segment_dot_dev(pk, words: DeviceWords, exps, idx: np.ndarray, off: np.ndarray, x: np.ndarray):
     """pai_segment_dot_dev: (words [nseg, W], exponents, statuses [nnz] on the host)."""
     (N, W), dev = words.shape, words.device
@@ -179,17 +289,57 @@ def segment_dot_dev(pk, words: DeviceWords, exps, idx: np.ndarray, off: np.ndarr
     return out, oe, st.download(np.int32, idx.size)
 
 
-def histogram_dev(pk, words: DeviceWords, exps, bins: np.ndarray, n_bins: int, node, n_nodes: int):
+def histogram_resident_args(N: int, bins, n_bins, node, n_nodes):
+    """histogram_args when bins or node is a DeviceArray: what the host can check of a resident operand is its dtype and
+    its shape (uint8 / uint16 C-contiguous [N, F]; int32 [N]); its values are the kernel's business (a node id outside
+    [0, n_nodes) and a bin id >= n_bins put the sample in no cell). A host operand is checked as ever."""
+    if isinstance(node, DeviceArray):
+        if node.dtype != np.int32:
+            raise TypeError(f"histogram: a device node array must be int32, not {node.dtype}")
+        if node.shape != (N,):
+            raise ValueError(f"histogram: node must have shape ({N},), not {node.shape}")
+    if not isinstance(bins, DeviceArray):     # host bins with resident node ids: a stand-in node of the right shape
+        b, _, shape = histogram_args(N, bins, n_bins, np.zeros(N, dtype=np.int32), n_nodes)
+        return b, node, shape
+    if bins.dtype not in (np.uint8, np.uint16):
+        raise TypeError("histogram: bins must be uint8 or uint16")
+    if bins.ndim != 2 or bins.shape[0] != N or bins.shape[1] == 0:
+        raise ValueError(f"histogram: bins must have shape ({N}, F) with F >= 1, not {bins.shape}")
+    # the scalar rules of histogram_args, on a one-row host stand-in of the same dtype and width
+    one = np.zeros((1, bins.shape[1]), dtype=bins.dtype)
+    host_node = node if not isinstance(node, DeviceArray) else np.zeros(N, dtype=np.int32)
+    if host_node is not None:
+        host_node = np.asarray(host_node)
+        if host_node.dtype.kind in "iu" and host_node.shape != (N,):
+            raise ValueError(f"histogram: node must have shape ({N},), not {host_node.shape}")
+        _, nd, shape = histogram_args(1, one, n_bins, host_node[:1], n_nodes)
+        if not isinstance(node, DeviceArray):
+            node = np.clip(host_node, -1, int(n_nodes)).astype(np.int32)
+    else:
+        _, _, shape = histogram_args(1, one, n_bins, None, n_nodes)
+    if N * bins.shape[1] >= 1 << 31:
+        raise ValueError("histogram: bins must hold fewer than 2^31 entries")
+    return bins, node, shape
+
+
+def histogram_dev(pk, words: DeviceWords, exps, bins, n_bins: int, node, n_nodes: int):
     """pai_histogram_dev over the checked arguments of cipher_buffer.histogram_args: (words [cells, W], exponents,
-    counts int64 on the host). Only the bins and the node ids go up."""
+    counts int64 on the host). Only the bins and the node ids go up, and not even those when they are DeviceArrays."""
     (N, W), dev = words.shape, words.device
+    for a in (bins, node):
+        if isinstance(a, DeviceArray) and a.device != dev:
+            raise ValueError(f"the buffer lives on device {dev}, the operand on device {a.device}")
     ctx = context_on(pk, dev)
     ex = _exp_mem(exps, N, dev)
-    bins = np.ascontiguousarray(bins)
+    if not isinstance(bins, DeviceArray):
+        bins = np.ascontiguousarray(bins)
     F = bins.shape[1]
     cells = int(n_nodes) * F * int(n_bins)
-    db = _native.device_upload(bins, dev)
-    dn = _native.device_upload(np.ascontiguousarray(node, dtype=np.int32), dev) if node is not None else None
+    db = bins.mem if isinstance(bins, DeviceArray) else _native.device_upload(bins, dev)
+    if isinstance(node, DeviceArray):
+        dn = node.mem
+    else:
+        dn = _native.device_upload(np.ascontiguousarray(node, dtype=np.int32), dev) if node is not None else None
     out, oe, cnt = DeviceWords.empty(cells, W, dev), _i32(dev, cells), _native.DeviceMem(cells * 8, dev)
     ctx.dev_call("pai_histogram_dev", words.ptr, ex.ptr, N,
                  _native.PAI_BIN_U16 if bins.dtype.itemsize == 2 else _native.PAI_BIN_U8, db.ptr, F, F,
@@ -499,14 +649,83 @@ class DeviceCiphertextBuffer(BufferOps):
         out, oe = take_dev(self.public_key, self.words, self._ex, idx)
         return DeviceCiphertextBuffer(self.public_key, out, oe, self.obfuscated[idx], shape)
 
+    def _take_resident(self, idx: DeviceArray) -> "DeviceCiphertextBuffer":
+        if idx.dtype != np.int64:
+            raise TypeError(f"take: a device index must be int64, not {idx.dtype}")
+        out, oe, bad = take_idx_dev(self.public_key, self.words, self._ex, idx)
+        if bad >= 0:
+            raise IndexError(f"take: the index at position {bad} is out of bounds for {self.size} ciphertexts")
+        return DeviceCiphertextBuffer(self.public_key, out, oe, 1 if bool(np.all(self.obfuscated)) else 0, idx.shape)
+
+    def take(self, indices, axis=None):
+        """np.take over the ciphertexts. An int64 DeviceArray names FLAT positions in [0, size) (axis must be None): the
+        result has the index's shape and comes from one pai_take_idx_dev call that reads the index where it is; the 16
+        bytes of the device-side check come back, and IndexError names the first bad position. The obfuscation flags are a
+        host array and the index is not on the host, so the result is flagged obfuscated only when EVERY flag of this
+        buffer is set, and unflagged otherwise: the safe side, at most one re-randomisation more."""
+        if isinstance(indices, DeviceArray):
+            if axis is not None:
+                raise ValueError("take: a device index names flat positions (axis=None)")
+            return self._take_resident(indices)
+        return super().take(indices, axis)
+
+    def __getitem__(self, key):
+        """BufferOps.__getitem__; an int64 DeviceArray as in take()."""
+        if isinstance(key, DeviceArray):
+            return self._take_resident(key)
+        return super().__getitem__(key)
+
+    def segment_sum(self, index, seg_off) -> "DeviceCiphertextBuffer":
+        """Per-segment sums: segment s is the sum of the ciphertexts at the flat positions index[seg_off[s] :
+        seg_off[s + 1]] (repeats allowed), shape (nseg,); each sum is the reference's __add__ chain, an empty segment
+        ciphertext 1 at exponent 0. Two numpy lists run as pai_segment_add_dev. When either is an int64 DeviceArray both
+        are read on the device (pai_segment_add_idx_dev; a numpy one is uploaded for the call): nothing waits on the host
+        but the 16 bytes of the device-side check, which raise what the host check raises. Not obfuscated."""
+        idx = _index_operand("segment_sum", index, "index")
+        off = _index_operand("segment_sum", seg_off, "seg_off")
+        if idx.ndim != 1 or off.ndim != 1:
+            raise ValueError("segment_sum: index and seg_off must be one-dimensional")
+        if off.size < 1:
+            raise ValueError("segment_sum: seg_off must start at 0 and must not decrease")
+        nseg = off.size - 1
+        if not isinstance(idx, DeviceArray) and not isinstance(off, DeviceArray):
+            if off[0] != 0 or np.any(np.diff(off) < 0):
+                raise ValueError("segment_sum: seg_off must start at 0 and must not decrease")
+            if off[-1] != idx.size:
+                raise ValueError(f"segment_sum: {idx.size} indices, seg_off ends at {int(off[-1])}")
+            if idx.size and (idx.min() < 0 or idx.max() >= self.size):
+                raise IndexError(f"segment_sum: index out of range for {self.size} ciphertexts")
+            out, oe = segment_add_dev(self.public_key, self.words, self._ex, idx, off)
+        else:
+            self._ctx()
+            d_idx = idx if isinstance(idx, DeviceArray) else device_array(idx, self.device)
+            d_off = off if isinstance(off, DeviceArray) else device_array(off, self.device)
+            out, oe, (bad_idx, bad_off) = segment_add_idx_dev(self.public_key, self.words, self._ex, d_idx, d_off)
+            if bad_off >= 0:          # the error path may look: the offsets come down for the host check's message
+                h = d_off.to_host()
+                if h[0] != 0 or np.any(np.diff(h) < 0):
+                    raise ValueError("segment_sum: seg_off must start at 0 and must not decrease")
+                raise ValueError(f"segment_sum: {d_idx.size} indices, seg_off ends at {int(h[-1])}")
+            if bad_idx >= 0:
+                raise IndexError(f"segment_sum: index out of range for {self.size} ciphertexts")
+        e = oe.download(np.int32, nseg)
+        return self._like(out, np.where(e == EMPTY_EXP, 0, e).astype(np.int32), 0, (nseg,))
+
     def histogram(self, bins, n_bins: int, node=None, n_nodes: int = 1, default_bin=0):
         """CiphertextBuffer.histogram on the device (pai_histogram_dev, pai_histogram_sparse_dev): (DeviceCiphertextBuffer
         of shape (n_nodes, F, n_bins), int64 counts on the host). The empty cells' exponents are set to 0 on the
-        exponents alone."""
-        csr = sparse_csr(bins)
+        exponents alone. Dense bins (uint8 / uint16, C-contiguous [N, F]) and node (int32 [N]) may be DeviceArrays: their
+        pointers are passed through and nothing is uploaded for them, so a training run uploads its bins once. Sparse
+        bins stay host operands."""
+        csr = None if isinstance(bins, DeviceArray) else sparse_csr(bins)
         if csr is not None:
+            if isinstance(node, DeviceArray):
+                raise TypeError("histogram: sparse bins take host node ids")
             *args, shape = histogram_sparse_args(self.size, csr, n_bins, node, n_nodes, default_bin)
             out, oe, cnt = histogram_sparse_dev(self.public_key, self.words, self._ex, *args, shape)
+        elif isinstance(bins, DeviceArray) or isinstance(node, DeviceArray):
+            b, nd, shape = histogram_resident_args(self.size, bins, n_bins, node, n_nodes)
+            out, oe, cnt = histogram_dev(self.public_key, self.words, self._ex, b, int(n_bins), nd, int(n_nodes))
         else:
             b, nd, shape = histogram_args(self.size, bins, n_bins, node, n_nodes)
             out, oe, cnt = histogram_dev(self.public_key, self.words, self._ex, b, int(n_bins), nd, int(n_nodes))

@@ -283,6 +283,9 @@ class PackedCiphertextBuffer(object):
         int64 counts of shape (n_nodes, F, n_bins)) from one pai_histogram call, every slot summed per cell at once. The
         bound is this buffer's bound * counts.max(); the counts are taken on the host first, so that OverflowError is
         raised before any GPU call if it passes the slot. Empty cells decode as 0 in every slot.
+        On a resident buffer, dense bins (uint8 / uint16, C-contiguous [N, F]) and node (int32 [N]) may be
+        device_buffer.DeviceArrays: nothing is uploaded for them. Their cells cannot be counted on the host, so the
+        buffer's bound times ALL its samples must fit the slot (OverflowError otherwise).
         Sparse bins (anything that offers .tocsr()) take one pai_histogram_sparse call with default_bin as in
         CiphertextBuffer.histogram; a packed buffer's exponents are uniform, so the bits are the dense call's."""
         from .cipher_buffer import (histogram_args, histogram_cells, histogram_sparse_args, histogram_sparse_counts,
@@ -300,7 +303,17 @@ class PackedCiphertextBuffer(object):
         # check replaces the host-side count (22 ms for 262 144 x 16 bin ids, more than the kernels), and the counts the
         # device returns give the same exact bound afterwards. Every other case counts on the host first, as before.
         safe = self.resident and self.bound * N <= self.layout.slot_max
-        csr = sparse_csr(bins)
+        from .device_buffer import DeviceArray, histogram_resident_args
+        on_device = isinstance(bins, DeviceArray) or isinstance(node, DeviceArray)
+        csr = None if isinstance(bins, DeviceArray) else sparse_csr(bins)
+        if on_device and csr is not None:
+            raise TypeError("histogram: sparse bins take host node ids")
+        if on_device and not self.resident:
+            raise TypeError("histogram: DeviceArray operands need a resident buffer (to_device())")
+        if on_device and not safe:
+            # the exact bound needs the counts before the call, and the operands are not on the host
+            raise OverflowError(f"histogram: bound {self.bound} x {N} samples passes the slot, and the cells of DeviceArray "
+                                "operands cannot be counted on the host first: pass host bins and node ids")
         if csr is not None:
             # (a default cell is a true subset sum, T_v minus the stored rest, so counts.max() bounds it like any cell)
             *args, shape = histogram_sparse_args(N, csr, n_bins, node, n_nodes, default_bin)
@@ -310,7 +323,7 @@ class PackedCiphertextBuffer(object):
                 self._check_bound(self.bound * (int(cnt.max()) if cnt.size else 0))
             out, _, dev_cnt = histogram_sparse_words(self.public_key, self.words, self._exps(), *args, shape)
         else:
-            b, nd, shape = histogram_args(N, bins, n_bins, node, n_nodes)
+            b, nd, shape = (histogram_resident_args if on_device else histogram_args)(N, bins, n_bins, node, n_nodes)
             cells = shape[0] * shape[1] * shape[2]
             if not safe:
                 cell = histogram_cells(b, shape[2], nd, shape[0])

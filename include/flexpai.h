@@ -554,6 +554,37 @@ int pai_take_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_
                  uint32_t* d_ct_out, int32_t* d_exp_out, void* stream);
 int pai_check_below_dev(pai_ctx* ctx, const uint32_t* d_ct, size_t N, int64_t* first_bad, void* stream);
 
+/* Index lists on the device (kernels_res.hpp k_check_idx, k_seg_offsets, k_seg_rows; no reference counterpart): the
+ * take and the segment sums of above for a caller whose index is already device memory (a nonzero, an argsort, a
+ * top-k selection made on the GPU). Semantics and bits are those of pai_take_dev / pai_segment_add_dev for the same lists.
+ *
+ * Operands: d_index (`M` resp. `total` int64 entries) and d_seg_off (nseg + 1 int64 words) are DEVICE memory. `total` is
+ *   the number of index entries, which the caller knows from the index's size. An index entry lies in [0, N) and may
+ *   repeat; for pai_take_idx_dev with allow_empty != 0 it may also be -1, which writes ciphertext 1 with exponent
+ *   INT32_MIN. seg_off[0] == 0, offsets do not decrease, seg_off[nseg] == total. An empty segment gives ciphertext 1 with
+ *   exponent INT32_MIN.
+ * Validation runs on the device. d_bad names two device int64 words that the call sets:
+ *     d_bad[0]  the smallest position whose index value is invalid, or -1;
+ *     d_bad[1]  the smallest offending position of seg_off (0: seg_off[0] != 0; s + 1: seg_off[s + 1] < seg_off[s];
+ *               nseg: seg_off[nseg] != total), or -1. pai_take_idx_dev leaves it -1.
+ *   A check kernel runs first on `stream`; every kernel behind it reads d_bad first and returns without reading through
+ *   the index and without writing when either word is >= 0. On bad lists the outputs are therefore UNTOUCHED and the call
+ *   still returns PAI_OK: the caller reads the two words when it wants to know. PAI_ERR_ARG before any launch is kept for
+ *   what the host can see: a null pointer with a non-zero count (d_bad and, for the segment sums, d_seg_off are always
+ *   required), an output that overlaps an input, d_bad overlapping a list, N, M or total >= 2^40, nseg >= 2^30 or
+ *   total / 16 + nseg >= 2^31.
+ * No host wait: neither call synchronises a stream or the device, copies to the host, or allocates; scratch is the
+ *   context's, sized from total and nseg alone. Both take the context lock and chain on the previous call's event like
+ *   every _dev call, so they are asynchronous and capturable once the context's scratch has its size. The lists and
+ *   d_bad must stay valid until the stream has run the call.
+ * Levels: the host does not know the longest segment, so pai_segment_add_idx_dev runs the smallest l >= 1 with
+ *   16^l >= total levels of the 16-way tree; a segment that is finished earlier passes through unchanged. */
+int pai_take_idx_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_index, size_t M,
+                     int allow_empty, uint32_t* d_ct_out, int32_t* d_exp_out, int64_t* d_bad, void* stream);
+int pai_segment_add_idx_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_index,
+                            size_t total, const int64_t* d_seg_off, size_t nseg, uint32_t* d_out, int32_t* d_exp_out,
+                            int64_t* d_bad, void* stream);
+
 /* Packed plaintexts: many signed fixed-point values per ciphertext (no reference counterpart; opt-in, both peers must
  * be flexpai; csrc/kernels_pack.hpp). Every packed ciphertext is an ordinary reference ciphertext
  * raw_encrypt(M mod n, pk, r), so pai_add, pai_mul by an integer and pai_obfuscate act on all slots at once.
