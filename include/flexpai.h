@@ -746,7 +746,10 @@ int pai_next_prime(int device, int bits, const uint8_t* starts_le, size_t start_
 /* Kernel time (ms) and launches of pass 1 and of pass 2 in this thread's last pai_next_prime. */
 int pai_prime_last_times(float* pass1_ms, float* pass2_ms, int* pass1_launches, int* pass2_launches);
 /* verdict_u8[i * nbases + j] = 1 when candidate i (odd, bit `bits - 1` set) is a strong probable prime to base j:
- * with n - 1 = 2^s d, a^d is 1 or n - 1, or a^(2^r d) is n - 1 for some 0 < r < s. No sieving. */
+ * with n - 1 = 2^s d, a^d is 1 or n - 1, or a^(2^r d) is n - 1 for some 0 < r < s. No sieving. Any uint32 base is
+ * accepted, even ones and bases above 2^31 included; it is not reduced or checked against n. Base 0 gives 0 for every
+ * candidate (0^d = 0 is neither 1 nor n - 1) and base 1 gives 1 for every candidate, as Python's pow does in the host's
+ * test. At most 2^20 candidates and 2^12 bases per call. */
 int pai_prime_test(int device, int bits, const uint8_t* cands_le, size_t cand_bytes, size_t ncand,
                    const uint32_t* bases_u32, size_t nbases, uint8_t* verdict_u8);
 /* The sieve alone, on the host (no device): the offsets 0 < off <= window (0: the default) with x + off odd and

@@ -1,6 +1,8 @@
 """Key generation on the GPU (csrc/kernels_prime.hpp k_mr_w, csrc/engine_prime.hip): the verdict matrix of the
 strong-probable-prime test against the host's per-base test, pai_next_prime against _bigint.next_prime, and
-generate_paillier_keypair on the device path against the golden keys with the host's primality test disabled."""
+generate_paillier_keypair on the device path against the golden keys with the host's primality test disabled. The
+candidates here are random primes, golden primes and their products; moduli, exponents of two, bases, pseudoprimes and
+starts at the edges of the kernel's arithmetic are in test_gpu_prime_edges.py."""
 import random
 
 import numpy as np
