@@ -32,7 +32,7 @@ __device__ __forceinline__ int encode_float(double v, bool fixed, int fexp, int6
     e = fexp;
   }
   const double s = rint(ldexp(v, 4 * e));   // exact scaling, then ties-to-even
-  if (!(fabs(s) < 9.223372036854775e18)) return ST_ENC_RANGE;
+  if (!(fabs(s) < 9223372036854775808.0)) return ST_ENC_RANGE;   // 2^63 (NaN and +-inf too)
   M = (int64_t)s;
   return ST_OK;
 }

@@ -603,12 +603,15 @@ __device__ __forceinline__ void decode_element(const uint32_t* xl, const DecPara
       if (rem > half || (rem == half && (sticky || (keep & 1ull)))) keep += 1;
       d = ldexp((double)keep, lo_bit + drop);
     }
+    // The exponent comes from a peer and may be any int32: 4 e is never formed beyond the range where it matters.
+    // From e = 269 on 16^-e is 0.0 as a double (the reference's pow(16, -e)), and from e = -16 down no mantissa
+    // but 0 stays within int64 (kernels_dec.hpp's decode_lane clamps the same way).
     if (e > 0) {
       if (isinf(d) || B > 1024) st = ST_FLOAT_OVF;
-      else val = (neg ? -d : d) * ldexp(1.0, -4 * e);
+      else val = (neg ? -d : d) * ldexp(1.0, -4 * (e < 269 ? e : 269));
     } else {
-      val = ldexp(neg ? -d : d, -4 * e);
-      const int sh = -4 * e;
+      val = ldexp(neg ? -d : d, -4 * (e > -600 ? e : -600));
+      const int sh = B == 0 ? 0 : (e > -16 ? -4 * e : 64);
       if (B + sh <= 63) {
         const int64_t mm = (int64_t)(hi64 << sh);
         mant = neg ? -mm : mm;

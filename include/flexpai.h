@@ -333,7 +333,13 @@ int pai_obfuscate(pai_ctx* ctx, const uint32_t* ct, size_t N, int obf_mode,
 
 /* Decrypt + decode. val_out: float64 value (status OK/INT), mant_out: signed mantissa when it
  * fits int64 (nullable), status_out (required), raw_out: N * pt_words canonical plaintexts
- * m = D(c) in [0, n) (nullable).                                                              */
+ * m = D(c) in [0, n) (nullable).
+ * exp: any int32 (it arrives from a peer); the decode follows FixedPointNumber.decode over the whole range and never
+ * forms 4 * exp where that would wrap. For exp > 0 the value is float(M) * 16^-exp in double arithmetic: a denormal
+ * factor for exp = 256 .. 268 and 0.0 from exp = 269 on, so the result is +-0.0 with the mantissa's sign there
+ * (PAI_EL_FLOAT_OVF first, if |M| >= 2^1024 - 2^970). For exp <= 0 the result is the integer M * 16^-exp: PAI_EL_INT
+ * with mant_out while it has at most 63 bits (so -2^63 is PAI_EL_INT_BIG), which no M but 0 has from exp = -16 down;
+ * M = 0 is PAI_EL_INT 0 at every exp <= 0. val_out of a PAI_EL_INT_BIG element is the nearest double, +-inf beyond.  */
 int pai_decrypt(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, double* val_out,
                 int64_t* mant_out, int32_t* status_out, uint32_t* raw_out);
 

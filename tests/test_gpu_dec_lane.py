@@ -95,19 +95,22 @@ def test_lane_decrypt_edge_ciphertexts(ctxs, nb):
     for x, y in zip(a, b):
         assert np.array_equal(np.asarray(x)[unit].view(np.uint8), np.asarray(y)[unit].view(np.uint8))
     # decoded values and statuses follow the oracle's decode of the same plaintexts
-    val, mant, st, _ = a
-    for i, c in enumerate(cs):
-        try:
-            want = O.decode(raw[i], int(ex[i]), key.n, key.max_int)
-        except OverflowError:
-            assert st[i] in (N.EL_OVERFLOW, N.EL_FLOAT_OVF), f"element {i}"
-            continue
-        if isinstance(want, int):
-            assert st[i] in (N.EL_INT, N.EL_INT_BIG), f"element {i}"
-            if st[i] == N.EL_INT:
-                assert int(mant[i]) == want, f"element {i}"
-        else:
-            assert st[i] == N.EL_OK and float(val[i]) == want, f"element {i}"
+    _check_decode(a, raw, ex, key)
+
+
+def _check_decode(res, raw, ex, key):
+    """The exact status, the bits of the value (the sign of zero, denormals) and the mantissa of every element against
+    the oracle's decode of the plaintext (tests/codec_edges.py: expect_decode)."""
+    from codec_edges import expect_decode
+    val, mant, st, _ = res
+    bits = np.ascontiguousarray(val, dtype=np.float64).view(np.uint64)
+    for i, x in enumerate(raw):
+        want = expect_decode(x, int(ex[i]), key.n, key.max_int)
+        assert st[i] == want.st, f"element {i}: status {st[i]}, expected {want.st}"
+        if want.bits is not None:
+            assert int(bits[i]) == want.bits, f"element {i}: value {float(val[i]).hex()}"
+        if want.mant is not None:
+            assert int(mant[i]) == want.mant, f"element {i}"
 
 
 @pytest.mark.parametrize("nb", [1024, 2048])
@@ -142,3 +145,17 @@ def test_lane_decrypt_decode_statuses(ctxs, nb):
     _same(a, b)
     val, mant, st, raw = a
     assert N.words_to_ints(raw) == [m % n for m in ms]
+    # every branch is met, and every value, mantissa and status is the oracle's
+    _check_decode(a, [m % n for m in ms], ex, key)
+    assert set(int(s) for s in st) == {N.EL_OK, N.EL_INT, N.EL_INT_BIG, N.EL_OVERFLOW} | ({N.EL_FLOAT_OVF} if nb > 1024 else set())
+    # floats whose rounding needs the sticky bit: an exact tie under an even kept part, then the same with one bit far
+    # below it, in limb 0 (kept part 2^52 + 2: the tie stays, the sticky bit rounds up)
+    tie = ((1 << 52) + 2) << 48 | 1 << 47
+    ms2 = [tie, tie | 1, n - tie, n - (tie | 1), tie | 1 << 28, ((1 << 52) + 3) << 48 | 1 << 47]
+    ct2 = N.ints_to_words([O.raw_encrypt(m, key, 1) for m in ms2], ctx.ct_words)
+    ex2 = np.array([1, 1, 2, 2, 3, 1], dtype=np.int32)
+    a2, b2 = _both(ctx, ct2, ex2)
+    _same(a2, b2)
+    _check_decode(a2, ms2, ex2, key)
+    lo, hi = float(((1 << 52) + 2) << 48), float(((1 << 52) + 3) << 48)
+    assert [float(v) for v in a2[0]] == [lo / 16, hi / 16, -lo / 256, -hi / 256, hi / 4096, float(((1 << 52) + 4) << 48) / 16]

@@ -386,20 +386,18 @@ def _decrypt_inputs(K, key, W):
 
 
 def _check_decode(N, res, raws, ex, key, idx, what):
-    """Value, mantissa and status follow the oracle's decode of the plaintext (as test_lane_decrypt_edge_ciphertexts)."""
+    """The exact status, the bits of the value and the mantissa follow the oracle's decode of the plaintext
+    (codec_edges.expect_decode: which OverflowError, EL_INT against EL_INT_BIG, the sign of zero)."""
+    from codec_edges import expect_decode
     val, mant, st, _ = res
+    bits = np.ascontiguousarray(val, dtype=np.float64).view(np.uint64)
     for i in idx:
-        try:
-            want = O.decode(raws[i], int(ex[i]), key.n, key.max_int)
-        except OverflowError:
-            assert st[i] in (N.EL_OVERFLOW, N.EL_FLOAT_OVF), f"{what} element {i}"
-            continue
-        if isinstance(want, int):
-            assert st[i] in (N.EL_INT, N.EL_INT_BIG), f"{what} element {i}"
-            if st[i] == N.EL_INT:
-                assert int(mant[i]) == want, f"{what} element {i}"
-        else:
-            assert st[i] == N.EL_OK and float(val[i]) == want, f"{what} element {i}"
+        want = expect_decode(raws[i], int(ex[i]), key.n, key.max_int)
+        assert st[i] == want.st, f"{what} element {i}: status {st[i]}, expected {want.st}"
+        if want.bits is not None:
+            assert int(bits[i]) == want.bits, f"{what} element {i}: value {float(val[i]).hex()}"
+        if want.mant is not None:
+            assert int(mant[i]) == want.mant, f"{what} element {i}"
 
 
 @pytest.mark.parametrize("name", HOLDERS)
