@@ -17,12 +17,14 @@ __device__ __forceinline__ int floor_div(int a, int b) { return (a >= 0) ? a / b
 
 // FixedPointNumber.encode for a float value (float32 is widened exactly). precision=None:
 // e = floor((53 - frexp(v).exp) / 4); m = round_half_even(v * 16^e) computed exactly
-// (numpy-1.x semantics). |v| < 1e-200 encodes as the int 0 with e = 0.
+// (numpy-1.x semantics). |v| < 1e-200 encodes as the int 0 with e = 0. NaN and +-inf do not
+// encode: ST_ENC_RANGE with M = 0 and the exponent of that 0, so nothing libm leaves open reaches a caller.
 __device__ __forceinline__ int encode_float(double v, bool fixed, int fexp, int64_t& M, int& e) {
-  if (fabs(v) < 1e-200) {
+  const bool finite = fabs(v) <= 1.7976931348623157e308;   // false for NaN
+  if (fabs(v) < 1e-200 || !finite) {
     M = 0;
     e = fixed ? fexp : 0;
-    return ST_OK;
+    return finite ? ST_OK : ST_ENC_RANGE;
   }
   if (!fixed) {
     int fe;
@@ -32,7 +34,7 @@ __device__ __forceinline__ int encode_float(double v, bool fixed, int fexp, int6
     e = fexp;
   }
   const double s = rint(ldexp(v, 4 * e));   // exact scaling, then ties-to-even
-  if (!(fabs(s) < 9223372036854775808.0)) return ST_ENC_RANGE;   // 2^63 (NaN and +-inf too)
+  if (!(fabs(s) < 9223372036854775808.0)) return ST_ENC_RANGE;   // 2^63
   M = (int64_t)s;
   return ST_OK;
 }
@@ -58,7 +60,8 @@ __device__ __forceinline__ int encode_int(int64_t v, bool fixed, int fexp, int64
 
 // The encoding every kernel applies to element i of a plaintext array x: dtype 0 = float32, 1 = float64, 2 = int64
 // (PAI_F32 / PAI_F64 / PAI_I64); exp_mode != 0 fixes the exponent at fexp. Returns the status; M and e are written
-// as encode_float / encode_int write them (left alone on ST_ENC_RANGE).
+// as encode_float / encode_int write them (a finite value out of range leaves M alone; NaN and +-inf give M = 0 at
+// exponent 0, or fexp).
 __device__ __forceinline__ int encode_elem(const void* x, int dtype, int exp_mode, int fexp, long long i, int64_t& M,
                                            int& e) {
   const bool fixed = exp_mode != 0;

@@ -40,8 +40,8 @@ struct MulParams {
   uint32_t* scratch;      // per-lane tiles (TILE_WORDS_PER_LANE words per lane)
 };
 
-// Left-to-right fixed window 4 over a per-element exponent |M| < 2^63; the window count is the wave
-// maximum (groups with shorter exponents run leading zero digits, x^0 = R: harmless).
+// Left-to-right fixed window 4 over a per-element exponent |M| <= 2^63 (INT64_MIN: digit 8 of window 15); the window
+// count is the wave maximum (groups with shorter exponents run leading zero digits, x^0 = R: harmless).
 template <int TPI>
 __global__ __launch_bounds__(BLOCK, 2) void k_mul(MulParams p) {
   constexpr int S = TPI * L;
@@ -123,9 +123,9 @@ __global__ __launch_bounds__(BLOCK, 2) void k_mul(MulParams p) {
 //
 // M is exact for any exponent: M = +-mag 2^sh with mag < 2^64, so c0 needs only a shifted 4-limb
 // multiplier of n. Elements the device cannot decide bit-exactly get a status instead:
-//   ST_FLOAT_OVF  float scalar * 16^E overflows a double (OverflowError in the reference);
+//   ST_FLOAT_OVF  float scalar * 16^E overflows a double (OverflowError in the reference), +-inf included;
 //   ST_ENC_RANGE  |M| has more than max_bits (= nb - 3) bits (the reference's exact |M| > max_int test
-//                 is then made by the host).
+//                 is then made by the host), or the scalar is NaN (ValueError in the reference).
 struct PlainParams {
   const int32_t* exp;     // ciphertext exponents [n]: the max_exponent of each element's encode
   const void* x;          // scalars
@@ -148,6 +148,10 @@ __device__ __forceinline__ int encode_plain_max(int dtype, const void* x, long l
   neg = false;
   if (dtype != 2) {
     const double v = dtype == 0 ? (double)((const float*)x)[xi] : ((const double*)x)[xi];
+    if (!(fabs(v) <= 1.7976931348623157e308)) {   // NaN does not encode; +-inf * 16^E is not a finite double
+      E = me;
+      return v != v ? ST_ENC_RANGE : ST_FLOAT_OVF;
+    }
     if (fabs(v) < 1e-200) {            // scalar = 0, an int: exponent 0 (fixedpoint_number.py:56-57, 67-69)
       E = max(me, 0);
       return ST_OK;

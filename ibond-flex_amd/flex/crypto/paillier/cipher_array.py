@@ -449,7 +449,7 @@ def _plain_scalar(y):
         return np.float64
     if isinstance(y, (np.float32, np.float16)):
         return np.float32
-    if (type(y) is int and -(1 << 63) < y < (1 << 63)) or isinstance(y, (np.int16, np.int32, np.int64)):
+    if (type(y) is int and -(1 << 63) <= y < (1 << 63)) or isinstance(y, (np.int16, np.int32, np.int64)):
         return np.int64
     return None
 
@@ -460,6 +460,22 @@ def _plain_array(y: np.ndarray):
     if y.dtype in _DEV_INT:
         return y.astype(np.int64)
     return None
+
+
+def check_finite(x: np.ndarray) -> None:
+    """Raise what FixedPointNumber.encode raises for the first NaN or infinity of a plain operand, in array order:
+    ValueError for NaN, OverflowError for +-inf. For the calls that return no per-element status (pai_matmul) or whose
+    outputs mix several scalars (pai_segment_dot): numpy's object loop raises as a whole, and so do they, before the
+    launch."""
+    if x.dtype.kind != "f":
+        return
+    flat = x.reshape(-1)
+    bad = np.flatnonzero(~np.isfinite(flat))
+    if bad.size:
+        i = int(bad[0])
+        if np.isnan(flat[i]):
+            raise ValueError(f"cannot convert float NaN to integer (plain operand, element {i})")
+        raise OverflowError(f"cannot convert float infinity to integer (plain operand, element {i})")
 
 
 def _encrypted_operand(a):
@@ -510,6 +526,13 @@ def mul_plain(a, y):
     words, exps, _ = pack(a if A is a else A, pk)
     ctx = _runtime.context(pk)
     out, oe, st = ctx.mul(words, exps, xs)
+    bad = np.flatnonzero(st)
+    if bad.size:
+        # a scalar the device does not encode (NaN, +-inf): the per-element operator on the first one raises the
+        # reference's exception, as numpy's object loop would at that element
+        i = int(bad[0])
+        np.asarray(A).reshape(-1)[i] * xs[i if xs.size > 1 else 0].item()
+        raise ValueError(f"the scalar {xs[i if xs.size > 1 else 0]!r} at element {i} does not encode")
     # __mul__ returns fresh, not-yet-obfuscated numbers (encrypted_number.py:113)
     return materialize(pk, out, oe, shape, obfuscated=False)
 
@@ -530,6 +553,7 @@ def dot_plain(a, b):
     K = A.shape[-1]
     if K == 0 or x.shape[0] != K:
         return NotImplemented
+    check_finite(x)
     m = A.shape[0] if A.ndim == 2 else 1
     d = x.shape[1] if x.ndim == 2 else 1
     words, exps, _ = pack(a if A is a else A, pk)

@@ -108,10 +108,11 @@ class BufferOps(object):
         x = np.asarray(b)
         if len(self.shape) not in (1, 2) or x.ndim not in (1, 2) or x.shape[0] != self.shape[-1]:
             raise ValueError(f"dot: shapes {self.shape} and {x.shape} not aligned")
-        from .cipher_array import _plain_array
+        from .cipher_array import _plain_array, check_finite
         xs = _plain_array(x)
         if xs is None:
             raise TypeError(f"dot: unsupported operand dtype {x.dtype}")
+        check_finite(xs)                                        # pai_matmul reports no status: refuse before the launch
         m = self.shape[0] if len(self.shape) == 2 else 1
         d = x.shape[1] if x.ndim == 2 else 1
         shape = tuple(([m] if len(self.shape) == 2 else []) + ([d] if x.ndim == 2 else []))
@@ -262,13 +263,22 @@ class CiphertextBuffer(BufferOps):
     def __mul__(self, y):
         if isinstance(y, (PaillierEncryptedNumber, CiphertextBuffer)):
             raise ValueError("PaillierEncryptedNumber * PaillierEncryptedNumber is not allowed.")
-        out, oe, _ = self._ctx().mul(self.words, self.exps, _plain(y, self.size))
+        x = _plain(y, self.size)
+        out, oe, st = self._ctx().mul(self.words, self.exps, x)
+        bad = np.flatnonzero(st)
+        if bad.size:
+            # a scalar the device does not encode (NaN, +-inf): the per-element operator on the first one raises the
+            # reference's exception
+            i = int(bad[0])
+            PaillierEncryptedNumber(self.public_key, _ints(self.words[i:i + 1])[0], int(self.exps[i])) * _item(y, i)
+            raise ValueError(f"the scalar {_item(y, i)!r} at element {i} does not encode")
         return self._like(out, oe)
 
     def segment_dot(self, index, seg_off, weights) -> "CiphertextBuffer":
         """Segmented weighted sums, shape (nseg,): out[s] = sum over t in [seg_off[s], seg_off[s+1]) of
         self[index[t]] * weights[t] (flat indices; pai_segment_dot, one call). Each term is the reference's __mul__, each
-        sum its __add__ chain; a weight that does not encode raises ValueError naming its position. An empty segment
+        sum its __add__ chain; a weight that does not encode raises the reference's exception (ValueError for NaN,
+        OverflowError for +-inf) naming its position, before any launch. An empty segment
         is ciphertext 1 at exponent 0, an unobfuscated encryption of 0. Without a GPU the same runs on Python integers."""
         idx, off, w = segment_dot_args(self.size, index, seg_off, weights)
         out, oe = segment_dot_words(self.public_key, self.words, self.exps, idx, off, w)
@@ -429,6 +439,12 @@ def segment_dot_args(N: int, index, seg_off, weights):
     x = _plain_array(w) if w.size else w.astype(np.float64)
     if x is None:
         raise TypeError(f"segment_dot: unsupported weight dtype {w.dtype}")
+    if x.dtype.kind == "f":
+        bad = np.flatnonzero(~np.isfinite(x))
+        if bad.size:                # what the reference's __mul__ raises at the first such weight: no partial result
+            t = int(bad[0])
+            raise (ValueError if np.isnan(x[t]) else OverflowError)(
+                f"segment_dot: weight {w[t]!r} at index {t} does not encode")
     return idx, off, np.ascontiguousarray(x)
 
 
@@ -455,7 +471,7 @@ def segment_dot_words(pk, words, exps, idx, off, w):
             try:
                 term = PaillierEncryptedNumber(pk, cts[i], int(exps[i])) * w[t]
             except (ValueError, OverflowError) as e:
-                raise ValueError(f"segment_dot: weight {w[t]!r} at index {t} does not encode") from e
+                raise type(e)(f"segment_dot: weight {w[t]!r} at index {t} does not encode") from e
             acc = term if acc is None else acc + term
         vals.append(1 if acc is None else acc.ciphertext(False))
         oe.append(0 if acc is None else acc.exponent)

@@ -346,13 +346,15 @@ int pai_decrypt(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, 
 /* Ciphertext x plaintext, element-wise: out_i = ct_i (x) x_(i*x_stride) (x_stride 0: one scalar for all,
  * 1: one per element), x of dtype PAI_F32/F64/I64 encoded like FixedPointNumber.encode; exponent
  * exp_i + e(x). Negative scalars: invert(ct)^|m|, computed as ONE batch inversion for the array.
- * status_out (nullable): PAI_EL_ENC_RANGE where the scalar does not fit the 64-bit encoder.      */
+ * status_out (nullable): PAI_EL_ENC_RANGE where the scalar does not encode (NaN, +-inf). A scalar that does not encode
+ * contributes the factor 1 at exponent exp_i + 0: ciphertext 1, exponent exp_i.                  */
 int pai_mul(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int dtype, const void* x, size_t x_stride,
             uint32_t* ct_out, int32_t* exp_out, int32_t* status_out);
 /* Ciphertext + plaintext, element-wise: out_i = ct_i (+) x_(i*x_stride), x encoded like
  * FixedPointNumber.encode(x, max_exponent=exp_i) (fixedpoint_number.py:81-84) and raw-encrypted with r = 1,
  * exponent max(exp_i, e(x)). status_out (nullable): PAI_EL_FLOAT_OVF where x * 16^E is not a finite double
- * (OverflowError), PAI_EL_ENC_RANGE where |M| >= 2^(nb-3) (the exact |M| > max_int test is the caller's);
+ * (OverflowError; +-inf at every E), PAI_EL_ENC_RANGE where |M| >= 2^(nb-3) (the exact |M| > max_int test is the
+ * caller's) and for NaN (ValueError);
  * those outputs are undefined and the caller redoes them. Integers are exact (numpy's object add loop sees
  * Python ints), so int64 * 16^E never wraps. */
 int pai_add_plain(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int dtype, const void* x,
@@ -373,8 +375,8 @@ int pai_segment_add(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t
  *   __add__'s alignment to the segment's largest exponent; stored zeros count towards that maximum, as in pai_matmul.
  *   An empty segment yields ciphertext 1 with exponent INT32_MIN. ct_out and exp_out equal, bit for bit, pai_mul over
  *   the gathered entries followed by pai_segment_add over consecutive ranges, entries whose scalar does not encode
- *   included (the factor 1); status_out (nullable, nnz entries) holds pai_mul's statuses. A ciphertext without inverse
- *   mod n^2 that meets a negative scalar ends the call with PAI_ERR_NOINV. The output is not re-randomised.
+ *   included: such a scalar (NaN, +-inf) contributes the factor 1 at exponent exp[index[t]] + 0; status_out (nullable,
+ *   nnz entries) holds pai_mul's statuses. A ciphertext without inverse mod n^2 that meets a negative scalar ends the call with PAI_ERR_NOINV. The output is not re-randomised.
  * PAI_OPT_SEGDOT_FUSED / PAI_OPT_SEGDOT_PATH: window tables are built once per distinct ciphertext that a block of
  * chunks (16 consecutive entries of one segment) references, so the cost follows the stored entries; same bits on
  * either path. The _dev variant synchronises `stream` (sign flags, batch inversion, every level of the segmented add). */
@@ -465,7 +467,8 @@ int pai_cumsum(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t oute
  * d >= 16 columns that fills the chip computes every output as a fused multi-exponentiation over chunks of 16 k
  * (PAI_OPT_MATMUL_FUSED; PAI_OPT_MATMUL_PATH reports the path taken): window tables of the m K ciphertexts, and of the inverses of those in a row k of x that holds a negative
  * scalar, are built once and shared by the d columns. A ciphertext without inverse mod n^2 in such a row ends the call
- * with PAI_ERR_NOINV, as on the term path. */
+ * with PAI_ERR_NOINV, as on the term path. A scalar that does not encode (NaN, +-inf) contributes the factor 1 at
+ * exponent exp[i][k] + 0 on both paths; there is no status, so a caller that must refuse such scalars checks x first. */
 int pai_matmul(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t m, size_t K, int dtype, const void* x,
                size_t d, uint32_t* ct_out, int32_t* exp_out);
 
