@@ -78,4 +78,37 @@ hipError_t hist_acc_launch(int tpi, const HistAccParams& p, int cus, hipStream_t
   return hipErrorInvalidValue;
 }
 
+template <int TPI>
+static hipError_t hist_acc_cols_launch_t(HistAccColsParams p, int cus, hipStream_t st) {
+  constexpr int GPB = BLOCK / TPI;
+  p.stage_runs = hist_acc_cols_stage(GPB, p.C);
+  const size_t lds = (size_t)GPB * TPI * L * 4 + (size_t)p.stage_runs * HIST_RUN * 4;
+  if (lds > 65536) return hipErrorInvalidValue;   // C = 1 at TPI = 2: k_hist_acc's case
+  int occ = 1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_hist_acc_c<TPI>, BLOCK, lds) != hipSuccess || occ < 1) {
+    (void)hipGetLastError();
+    occ = 1;
+  }
+  const long long items = p.nruns * p.C;
+  const int grid = (int)std::max<long long>(1, std::min<long long>((items + GPB - 1) / GPB, (long long)occ * cus));
+  hipLaunchKernelGGL(k_hist_acc_c<TPI>, dim3(grid), dim3(BLOCK), lds, st, p);
+  return hipGetLastError();
+}
+
+hipError_t hist_acc_cols_launch(int tpi, const HistAccColsParams& p, int cus, hipStream_t st) {
+  if (p.nruns <= 0) return hipSuccess;
+  if (p.C < 1) return hipErrorInvalidValue;
+  if (tpi == 2) return hist_acc_cols_launch_t<2>(p, cus, st);
+  if (tpi == 4) return hist_acc_cols_launch_t<4>(p, cus, st);
+  if (tpi == 8) return hist_acc_cols_launch_t<8>(p, cus, st);
+  return hipErrorInvalidValue;
+}
+
+hipError_t hist_seg_cols_launch(const HistSegColsParams& p, int cus, hipStream_t st) {
+  const long long n = std::max(p.nruns, p.ncell) * p.C + 1;
+  const int g = (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 8ll * cus));
+  hipLaunchKernelGGL(k_hist_seg_cols<0>, dim3(g), dim3(256), 0, st, p);
+  return hipGetLastError();
+}
+
 }  // namespace fpai

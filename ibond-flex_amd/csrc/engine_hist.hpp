@@ -11,5 +11,10 @@ hipError_t hist_scatter_launch(HistParams p, int cus, hipStream_t st);
 hipError_t hist_rows_launch(const HistRowsParams& p, int cus, hipStream_t st);
 // one lane group per run, resident blocks by the occupancy query; hipErrorInvalidValue: unsupported group size
 hipError_t hist_acc_launch(int tpi, const HistAccParams& p, int cus, hipStream_t st);
+// pai_histogram_cols: one lane group per (run, column); the LDS holds the member ids of the runs of a block
+// (p.stage_runs is set here). hipErrorInvalidValue: unsupported group size, C < 1
+hipError_t hist_acc_cols_launch(int tpi, const HistAccColsParams& p, int cus, hipStream_t st);
+// the closing add's device lists of a range of cells (k_hist_seg_cols)
+hipError_t hist_seg_cols_launch(const HistSegColsParams& p, int cus, hipStream_t st);
 
 }  // namespace fpai

@@ -5461,6 +5461,259 @@ int pai_histogram(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, 
   return 0;
 }
 
+// ------------------------------------------------------------------ histograms over C ciphertext columns
+// ct is [N][C][W]: the member lists are those of the bin matrix, built once (k_hist_count, one read-back of the counts,
+// k_hist_scatter per feature block), and k_hist_acc_c writes one partial per (run, column) at [run][C]. The closing add
+// runs per feature block, so the block's partials are scratch like its member lists and the budget covers both: a block
+// takes features while 4 bytes per member + C (4 W + 4) bytes per run fit. Its lists (segment (cell, c) = the rows
+// run C + c of the cell's runs) are written by k_hist_seg_cols and summed by the device-planned segmented add with the
+// longest cell's runs as its bound, so nothing but the counts is waited for, whatever C is. A block's cells are one
+// range of the output when the block holds every feature, and one range per node otherwise.
+static int segment_add_idx_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_index,
+                               size_t total, size_t max_len, const int64_t* d_seg_off, size_t nseg, uint32_t* d_out,
+                               int32_t* d_exp_out, int64_t* d_bad, void* stream);
+
+static int hist_cols_check(const void* ct, const void* exp, size_t N, size_t C, int bin_dtype, const void* bins, size_t F,
+                           size_t bin_stride, const int32_t* node, size_t nodes, size_t B, const void* ct_out, const void* exp_out,
+                           const char* who) {
+  const int rc = hist_check(ct, exp, N, bin_dtype, bins, F, bin_stride, node, nodes, B, ct_out, exp_out, who);
+  if (rc) return rc;
+  const std::string w(who);
+  if (C == 0) return fail(PAI_ERR_ARG, w + ": C must be at least 1");
+  if (C > HIST_MAX_CELLS || nodes * F * B * C > HIST_MAX_CELLS) return fail(PAI_ERR_ARG, w + ": more than 2^24 cells x columns");
+  if (N * C >= ((size_t)1 << 31)) return fail(PAI_ERR_ARG, w + ": N C must be below 2^31");
+  return 0;
+}
+
+int pai_histogram_cols_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, size_t C, int bin_dtype,
+                           const void* d_bins, size_t F, size_t bin_stride, const int32_t* d_node, size_t nodes, size_t B,
+                           uint32_t* d_out, int32_t* d_exp_out, int64_t* d_count_out, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  const std::string who = "pai_histogram_cols_dev";
+  int rc = hist_cols_check(d_ct, d_exp, N, C, bin_dtype, d_bins, F, bin_stride, d_node, nodes, B, d_out, d_exp_out, who.c_str());
+  if (rc) return rc;
+  if (C == 1)   // the same layout on both sides
+    return pai_histogram_dev(c, d_ct, d_exp, N, bin_dtype, d_bins, F, bin_stride, d_node, nodes, B, d_out, d_exp_out, d_count_out, stream);
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t W = c->ct_words, cells = nodes * F * B, R = HIST_RUN;
+  auto& h = c->hist;
+  HistParams hp{};
+  hp.bins = d_bins;
+  hp.bin_u16 = bin_dtype == PAI_BIN_U16 ? 1 : 0;
+  hp.stride = (long long)bin_stride;
+  hp.node = d_node;
+  hp.nodes = (int)nodes;
+  hp.B = (int)B;
+  hp.N = (long long)N;
+  hp.F = (long long)F;
+  // counts of all cells
+  const size_t o_off = d_count_out ? 0 : align16(cells * 8), o_cur = align16(o_off + cells * 4),
+               o_roff = align16(o_cur + cells * 4), o_bad = align16(o_roff + (cells + 1) * 8), o_runs = o_bad + 16;
+  if ((rc = ensure_buf(&c->d_histmeta, &c->histmeta_bytes, o_runs))) return rc;
+  unsigned long long* d_cnt = d_count_out ? (unsigned long long*)d_count_out : (unsigned long long*)c->d_histmeta;
+  HIPCHK(hipMemsetAsync(d_cnt, 0, cells * 8, st));
+  h.cnt.assign(cells, 0);
+  if (N) {
+    hp.count = d_cnt;
+    hp.f0 = 0;
+    hp.f1 = (long long)F;
+    HIPCHK(hist_count_launch(hp, c->cus, st));
+    HIPCHK(hipMemcpyAsync(h.cnt.data(), d_cnt, cells * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  // feature blocks: members and C partials per run within the budget, one feature at least
+  struct Block {
+    size_t f0, f1, entries, runs, row0;
+  };
+  std::vector<Block> blocks;
+  const size_t budget = hist_budget(c), run_bytes = C * (W * 4 + 4);
+  size_t total_runs = 0, max_len = 1;
+  {
+    Block b{0, 0, 0, 0, 0};
+    for (size_t f = 0; f < F; ++f) {
+      size_t ent = 0, runs = 0;
+      for (size_t v = 0; v < nodes; ++v)
+        for (size_t q = 0; q < B; ++q) {
+          const long long n = h.cnt[(v * F + f) * B + q];
+          if (n < 0 || (size_t)n > N) return fail(PAI_ERR_HIP, who + ": cell count out of range");
+          ent += (size_t)n;
+          runs += ((size_t)n + R - 1) / R;
+          max_len = std::max(max_len, ((size_t)n + R - 1) / R);
+        }
+      if (b.f1 > b.f0 && (b.entries + ent) * 4 + (b.runs + runs) * run_bytes > budget) {
+        blocks.push_back(b);
+        total_runs += b.runs;
+        b = Block{f, f, 0, 0, total_runs};
+      }
+      b.f1 = f + 1;
+      b.entries += ent;
+      b.runs += runs;
+    }
+    blocks.push_back(b);
+    total_runs += b.runs;
+  }
+  if (total_runs * C >= (size_t)INT32_MAX) return fail(PAI_ERR_ARG, who + ": too many runs");
+  // member offsets and runs in block order (v, f, b); the output ranges of every block with their first partial row
+  struct Range {
+    size_t cell0, ncell, run0, nruns;
+  };
+  std::vector<Range> ranges;
+  h.cell_off.assign(cells, 0);
+  h.runs.clear();
+  h.runs.reserve(total_runs);
+  size_t max_ent = 1, max_runs = 1;
+  for (const Block& b : blocks) {
+    const bool whole = b.f0 == 0 && b.f1 == F;
+    size_t off = 0;
+    for (size_t v = 0; v < nodes; ++v) {
+      const size_t run0 = h.runs.size() - b.row0;
+      for (size_t f = b.f0; f < b.f1; ++f)
+        for (size_t q = 0; q < B; ++q) {
+          const size_t cell = (v * F + f) * B + q, n = (size_t)h.cnt[cell];
+          h.cell_off[cell] = (int32_t)off;
+          for (size_t t = 0; t < n; t += R) h.runs.push_back(make_int2((int)(off + t), (int)std::min(R, n - t)));
+          off += n;
+        }
+      if (!whole) ranges.push_back(Range{(v * F + b.f0) * B, (b.f1 - b.f0) * B, run0, h.runs.size() - b.row0 - run0});
+    }
+    if (whole) ranges.push_back(Range{0, cells, 0, b.runs});
+    max_ent = std::max(max_ent, b.entries);
+    max_runs = std::max(max_runs, b.runs);
+  }
+  h.segoff.assign(cells + 1, 0);   // the scan of the cells' run counts in output order
+  for (size_t cell = 0; cell < cells; ++cell) h.segoff[cell + 1] = h.segoff[cell] + (long long)(((size_t)h.cnt[cell] + R - 1) / R);
+  if ((rc = ensure_buf(&c->d_histmeta, &c->histmeta_bytes, o_runs + align16(std::max<size_t>(total_runs, 1) * 8)))) return rc;
+  if (!d_count_out && N) {   // (a grown buffer lost the counts it held: they are on the host)
+    d_cnt = (unsigned long long*)c->d_histmeta;
+    HIPCHK(hipMemcpyAsync(d_cnt, h.cnt.data(), cells * 8, hipMemcpyHostToDevice, st));
+  }
+  char* mb = (char*)c->d_histmeta;
+  int32_t* d_off = (int32_t*)(mb + o_off);
+  unsigned* d_cur = (unsigned*)(mb + o_cur);
+  long long* d_roff = (long long*)(mb + o_roff);
+  int64_t* d_bad = (int64_t*)(mb + o_bad);
+  int2* d_runs = (int2*)(mb + o_runs);
+  size_t max_ncell = 1;
+  for (const Range& r : ranges) max_ncell = std::max(max_ncell, r.ncell);
+  const size_t o_seg = align16(max_ent * 4), o_idx = align16(o_seg + (max_ncell * C + 1) * 8);
+  if ((rc = ensure_buf(&c->d_histwork, &c->histwork_bytes, o_idx + max_runs * C * 8))) return rc;
+  int32_t* d_mem = (int32_t*)c->d_histwork;
+  long long* d_seg = (long long*)((char*)c->d_histwork + o_seg);
+  long long* d_idx = (long long*)((char*)c->d_histwork + o_idx);
+  const size_t o_pexp = align16(max_runs * C * W * 4);
+  if ((rc = ensure_buf(&c->d_histpart, &c->histpart_bytes, o_pexp + align16(max_runs * C * 4)))) return rc;
+  uint32_t* part = (uint32_t*)c->d_histpart;
+  int32_t* pexp = (int32_t*)((char*)c->d_histpart + o_pexp);
+  HIPCHK(hipMemcpyAsync(d_roff, h.segoff.data(), (cells + 1) * 8, hipMemcpyHostToDevice, st));
+  if (total_runs) {
+    HIPCHK(hipMemcpyAsync(d_off, h.cell_off.data(), cells * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_cur, 0, cells * 4, st));
+    HIPCHK(hipMemcpyAsync(d_runs, h.runs.data(), total_runs * 8, hipMemcpyHostToDevice, st));
+  }
+  size_t ri = 0;
+  for (const Block& b : blocks) {
+    if (b.runs) {
+      HIPCHK(hipMemsetAsync(d_mem, 0, b.entries * 4, st));
+      hp.count = d_cnt;
+      hp.cell_off = d_off;
+      hp.cursor = d_cur;
+      hp.members = d_mem;
+      hp.f0 = (long long)b.f0;
+      hp.f1 = (long long)b.f1;
+      HIPCHK(hist_scatter_launch(hp, c->cus, st));
+      HistAccColsParams ap{};
+      ap.cts = d_ct;
+      ap.exps = d_exp;
+      ap.members = d_mem;
+      ap.runs = d_runs + b.row0;
+      ap.nruns = (long long)b.runs;
+      ap.C = (int)C;
+      ap.out = part;
+      ap.out_exp = pexp;
+      ap.N = c->d_N;
+      ap.RS = c->d_RS;
+      ap.mprime = c->mprime_N;
+      ap.ct_words = c->ct_words;
+      HIPCHK(hist_acc_cols_launch(c->tpi_e, ap, c->cus, st));
+    }
+    // the block's ranges: an empty cell has no rows (ciphertext 1, INT32_MIN)
+    const size_t nr = b.f0 == 0 && b.f1 == F ? 1 : nodes;
+    for (size_t q = 0; q < nr; ++q, ++ri) {
+      const Range& r = ranges[ri];
+      HistSegColsParams sp{d_roff + r.cell0, (long long)r.ncell, (long long)r.nruns, (long long)r.run0, (int)C, d_seg, d_idx};
+      HIPCHK(hist_seg_cols_launch(sp, c->cus, st));
+      if ((rc = segment_add_idx_dev(c, part, pexp, std::max<size_t>(b.runs, 1) * C, (const int64_t*)d_idx, r.nruns * C, max_len,
+                                    (const int64_t*)d_seg, r.ncell * C, d_out + r.cell0 * C * W, d_exp_out + r.cell0 * C, d_bad,
+                                    (void*)st)))
+        return rc;
+    }
+  }
+  return 0;
+}
+
+int pai_histogram_cols(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, size_t C, int bin_dtype, const void* bins,
+                       size_t F, size_t bin_stride, const int32_t* node, size_t nodes, size_t B, uint32_t* ct_out,
+                       int32_t* exp_out, int64_t* count_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  int rc = hist_cols_check(ct, exp, N, C, bin_dtype, bins, F, bin_stride, node, nodes, B, ct_out, exp_out, "pai_histogram_cols");
+  if (rc) return rc;
+  if (C == 1) return pai_histogram(c, ct, exp, N, bin_dtype, bins, F, bin_stride, node, nodes, B, ct_out, exp_out, count_out);
+  HIPCHK(hipSetDevice(c->device));
+  const size_t W = c->ct_words, cells = nodes * F * B, outs = cells * C, bsz = bin_dtype == PAI_BIN_U16 ? 2 : 1;
+  // chunks of whole rows of C ciphertexts, as many ciphertexts as a chunk of pai_histogram; their cell sums
+  // [chunk][cells][C] are the operands of one k-way add (an empty cell: PAD_EXP)
+  size_t chunk = std::max<size_t>(HIST_HOST_CHUNK / C, 1);
+  if (const char* e = xcheck_env("FLEXPAI_HIST_CHUNK")) {           // test build: chunks at small shapes
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    if (v > 0) chunk = (size_t)v;
+  }
+  const size_t kmax = std::max<size_t>(HIST_HOST_PART_BYTES / (outs * W * 4), 1);
+  if ((N + chunk - 1) / chunk > kmax) chunk = (N + kmax - 1) / kmax;
+  const size_t k = std::max<size_t>((N + chunk - 1) / chunk, 1), nc = std::min(chunk, std::max<size_t>(N, 1));
+  DevScope ds;
+  uint32_t* dct = ds.alloc<uint32_t>(nc * C * W);
+  int32_t* dexp = ds.alloc<int32_t>(nc * C);
+  uint8_t* dbins = ds.alloc<uint8_t>(nc * bin_stride * bsz);
+  int32_t* dnode = node ? ds.alloc<int32_t>(nc) : nullptr;
+  uint32_t* dpart = ds.alloc<uint32_t>(k * outs * W);
+  int32_t* dpexp = ds.alloc<int32_t>(k * outs);
+  int64_t* dcnt = ds.alloc<int64_t>(cells);
+  uint32_t* dout = k > 1 ? ds.alloc<uint32_t>(outs * W) : dpart;
+  int32_t* dexo = k > 1 ? ds.alloc<int32_t>(outs) : dpexp;
+  if (!dct || !dexp || !dbins || (node && !dnode) || !dpart || !dpexp || !dcnt || !dout || !dexo)
+    return fail(PAI_ERR_HIP, "pai_histogram_cols: device allocation failed");
+  std::vector<int64_t> cnt(cells);
+  if (count_out) std::fill(count_out, count_out + cells, (int64_t)0);
+  for (size_t q = 0; q < k; ++q) {
+    const size_t i0 = q * chunk, n = N ? std::min(chunk, N - i0) : 0;
+    if (n) {
+      HIPCHK(hipMemcpy(dct, ct + i0 * C * W, n * C * W * 4, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(dexp, exp + i0 * C, n * C * 4, hipMemcpyHostToDevice));
+      // (the last row of a strided matrix ends after its F elements)
+      HIPCHK(hipMemcpy(dbins, (const char*)bins + i0 * bin_stride * bsz, ((n - 1) * bin_stride + F) * bsz, hipMemcpyHostToDevice));
+      if (node) HIPCHK(hipMemcpy(dnode, node + i0, n * 4, hipMemcpyHostToDevice));
+    }
+    rc = pai_histogram_cols_dev(c, dct, dexp, n, C, bin_dtype, dbins, F, bin_stride, dnode, nodes, B, dpart + q * outs * W,
+                                dpexp + q * outs, dcnt, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    if (count_out) {
+      HIPCHK(hipMemcpy(cnt.data(), dcnt, cells * 8, hipMemcpyDeviceToHost));
+      for (size_t s = 0; s < cells; ++s) count_out[s] += cnt[s];
+    }
+  }
+  if (k > 1) {
+    if ((rc = add_dev(c, dpart, dpexp, (int)k, (long long)outs, dout, dexo, nullptr))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+  }
+  HIPCHK(hipMemcpy(ct_out, dout, outs * W * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(exp_out, dexo, outs * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // ------------------------------------------------------------------ sparse histograms (kernels_shist.hpp)
 // The bin matrix is CSR. Step one (shist_slots_dev) is the histogram above over the STORED entries: every (node,
 // feature) has B + 1 slots (the bins, and one for stored missing values), entries at the feature's default bin are
@@ -6587,9 +6840,12 @@ int pai_take_idx_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, siz
 // (k_add of one operand below n^2 multiplies nothing), so the bits are those of the host-list call. Level k launches
 // k_add over total / 16^(k + 1) + nseg rows, the host's bound on its parts; the rows past the real count gather nothing
 // and write the identity into scratch that nobody reads.
-int pai_segment_add_idx_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_index,
-                            size_t total, const int64_t* d_seg_off, size_t nseg, uint32_t* d_out, int32_t* d_exp_out,
-                            int64_t* d_bad, void* stream) {
+//
+// `max_len` is the host's bound on the longest segment: `total` for a caller's lists, less where the library built the
+// lists itself and knows the lengths (pai_histogram_cols), which saves the levels that would only pass rows through.
+static int segment_add_idx_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_index,
+                               size_t total, size_t max_len, const int64_t* d_seg_off, size_t nseg, uint32_t* d_out,
+                               int32_t* d_exp_out, int64_t* d_bad, void* stream) {
   if (!c) return fail(PAI_ERR_ARG, "null ctx");
   CtxLock lk(c, (hipStream_t)stream);
   if (!d_bad || !d_seg_off) return fail(PAI_ERR_ARG, "pai_segment_add_idx_dev: null pointer");
@@ -6617,7 +6873,7 @@ int pai_segment_add_idx_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_e
   const int C = SEG_CHUNK;
   static_assert(SEG_CHUNK == SEGPLAN_C, "the plan kernels cut segments as the host-list call does");
   int levels = 1;
-  for (size_t cap = C; cap < total; cap *= C) ++levels;
+  for (size_t cap = C; cap < std::min(max_len, total); cap *= C) ++levels;
   const size_t P = total / C + nseg;   // no level has more partial sums
   const size_t o_a = 0, o_b = align16(o_a + P * W * 4), o_ea = align16(o_b + P * W * 4), o_eb = align16(o_ea + P * 4),
                o_off = align16(o_eb + P * 4), o_g = align16(o_off + (size_t)(levels - 1) * (nseg + 1) * 8),
@@ -6658,6 +6914,12 @@ int pai_segment_add_idx_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_e
     in_e = oe;
   }
   return 0;
+}
+
+int pai_segment_add_idx_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_index,
+                            size_t total, const int64_t* d_seg_off, size_t nseg, uint32_t* d_out, int32_t* d_exp_out,
+                            int64_t* d_bad, void* stream) {
+  return segment_add_idx_dev(c, d_ct, d_exp, N, d_index, total, total, d_seg_off, nseg, d_out, d_exp_out, d_bad, stream);
 }
 
 // The wire-ingest range check on the device (k_check_below): one read-back of one word.

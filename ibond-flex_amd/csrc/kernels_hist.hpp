@@ -249,4 +249,187 @@ __global__ __launch_bounds__(BLOCK, 2) void k_hist_acc(HistAccParams p) {
   }
 }
 
+// ------------------------------------------------------------------ C ciphertext columns per sample (pai_histogram_cols)
+// The member lists depend on the bin matrix alone, so C columns share them: k_hist_count and k_hist_scatter run once and
+// k_hist_acc_c reads column c of member i at row i C + c of the [N][C][W] words.
+
+struct HistAccColsParams {
+  const uint32_t* cts;     // [N][C][W]
+  const int32_t* exps;     // [N][C]
+  const int32_t* members;
+  const int2* runs;        // [nruns] (first member, 1 .. HIST_RUN members)
+  long long nruns;
+  int C;
+  int stage_runs;          // runs whose member ids the launch's LDS holds: hist_acc_cols_stage(GPB, C)
+  uint32_t* out;           // [nruns][C][W]
+  int32_t* out_exp;        // [nruns][C]
+  const uint32_t* N;
+  const uint32_t* RS;      // [ADD_KMAX + 2][ct_words]: R^s mod n^2
+  uint32_t mprime;
+  int ct_words;
+};
+
+// The runs that GPB consecutive items run * C + c can touch: the first run may enter at any of its columns.
+__host__ __device__ constexpr int hist_acc_cols_stage(int gpb, int C) {
+  return C >= gpb ? 2 : (gpb + C - 2) / C + 1;
+}
+
+// k_hist_acc over C columns. The work item is (run, column), numbered run C + c, and a block takes BLOCK / TPI consecutive
+// items: the C columns of consecutive runs, so every lane group has an item whatever C is (2 columns fill 64 runs' worth
+// of a 128-group block, 200 columns are cut into blocks of whole lane groups). The member ids of the block's runs
+// (<= stage_runs rows of HIST_RUN ids, -1 past a ragged run's end) are read from global memory once, by the whole block
+// and coalesced, and stay in LDS behind the groups' operand slots; the C groups of a run take them from there for the
+// exponent scans (one per level of the Horner product) and for the operand addresses. Everything per item is
+// k_hist_acc's: the exponent maximum and the alignment powers come from exps[i C + c], the operands from
+// cts + (i C + c) W, and the canonical partial at the item's largest exponent goes to row run C + c.
+//
+// LDS: BLOCK / TPI slots of TPI L limbs (37 KiB at every TPI) + stage_runs x 256 bytes of ids. The call sends C = 1 to
+// k_hist_acc, so the largest footprint is C = 2 at TPI = 2 (65 runs): 53.25 KiB, inside the 64 KiB a launch may ask for
+// without an attribute; 48 KiB at C = 3, under 38 KiB from C = 128 on. The launch bound asks for 2 blocks per CU and
+// the CU's 160 KiB of LDS hold 3 at the largest footprint, so the ids never cost a resident block.
+template <int TPI>
+__global__ __launch_bounds__(BLOCK, 2) void k_hist_acc_c(HistAccColsParams p) {
+  constexpr int S = TPI * L;
+  constexpr int GPB = BLOCK / TPI;
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const int lane = threadIdx.x & 63;
+  const int tig = threadIdx.x % TPI;
+  const int gib = threadIdx.x / TPI;
+  uint32_t* slot = smem + gib * S;
+  int32_t* ids = reinterpret_cast<int32_t*>(smem + GPB * S);   // [stage_runs][HIST_RUN]
+  uint32_t m[L];
+  load_limbs_g<TPI>(p.N, m, tig);
+  const long long C = p.C, items = p.nruns * C;
+
+  for (long long base = (long long)blockIdx.x * GPB; base < items; base += (long long)gridDim.x * GPB) {
+    const long long r0 = base / C, r1 = (min(base + GPB, items) - 1) / C;   // r1 - r0 < stage_runs
+    const int staged = (int)(r1 - r0 + 1) * HIST_RUN;
+    __syncthreads();   // the previous pass has read its ids
+    for (int t = threadIdx.x; t < staged; t += BLOCK) {
+      const int2 run = p.runs[r0 + t / HIST_RUN];
+      const int j = t % HIST_RUN;
+      ids[t] = j < run.y ? p.members[(long long)run.x + j] : -1;
+    }
+    __syncthreads();
+
+    const long long item = base + gib;
+    const bool valid = item < items;
+    const long long el = valid ? item : items - 1;
+    const long long r = el / C, col = el - r * C;
+    const int32_t* mem = ids + (r - r0) * HIST_RUN;
+    const int k = min(p.runs[r].y, HIST_RUN);
+    const int32_t* ex = p.exps + col;                          // member i: ex[i C]
+    const uint32_t* ct = p.cts + col * p.ct_words;             // member i: ct + i C W
+    const long long cw = C * p.ct_words;
+    int E = PAD_EXP, cur = INT32_MAX;
+    for (int j = 0; j < k; ++j) {
+      const int ej = ex[mem[j] * C];
+      E = max(E, ej);
+      cur = min(cur, ej);
+    }
+    uint32_t a[L];
+    int jc = 0, sq = 0, mcount = 1;
+    bool done = false;
+    while (ex[mem[jc] * C] != cur) ++jc;
+    stage_words_to_limbs<TPI>(slot, ct + mem[jc] * cw, p.ct_words, a, tig);   // rho = 0
+    ++jc;
+#pragma clang loop unroll(disable)
+    for (;;) {
+      // this group's next step: 0 square, 1 times operand `osrc`, 2 times R^s, 3 nothing (times R)
+      int op = 3, s = 1;
+      long long osrc = 0;
+      if (!done) {
+        if (sq > 0) {
+          op = 0;
+          --sq;
+        } else {
+          while (jc < k && ex[mem[jc] * C] != cur) ++jc;
+          if (jc < k) {
+            if (mcount == ADD_KMAX) {                  // rho = 1 - mcount -> 0; the operand waits a step
+              op = 2;
+              s = mcount;
+              mcount = 1;
+            } else {
+              op = 1;
+              osrc = mem[jc];
+              ++jc;
+              ++mcount;
+            }
+          } else {
+            int nl = INT32_MAX;
+            for (int j = 0; j < k; ++j) {
+              const int ej = ex[mem[j] * C];
+              if (ej > cur && ej < nl) nl = ej;
+            }
+            if (nl != INT32_MAX) {
+              op = 2;
+              s = 1 + mcount;                          // back to rho = 1 for the squarings
+              sq = 4 * (nl - cur);
+              cur = nl;
+              jc = 0;
+              mcount = 0;
+            } else {
+              done = true;
+              if (mcount >= 2) {                       // rho = 1 - mcount -> 0
+                op = 2;
+                s = mcount;
+              }
+            }
+          }
+        }
+      }
+      if (ballot(op != 3) == 0ull) break;
+      {
+        const uint32_t* src = op == 1 ? ct + osrc * cw : p.RS + (size_t)s * p.ct_words;
+        uint32_t t[L];
+        stage_words_to_limbs<TPI>(slot, src, p.ct_words, t, tig);
+#pragma unroll
+        for (int i = 0; i < L; ++i) t[i] = op == 0 ? a[i] : t[i];
+        write_limbs_lds<TPI>(slot, t, tig);
+      }
+      montmul<TPI>(a, a, slot, TPI, m, p.mprime, lane, tig);
+    }
+    cond_sub<TPI>(a, m, lane, tig);
+    emit_words<TPI>(slot, a, p.out + el * p.ct_words, p.ct_words, valid, tig);
+    if (valid && tig == 0) p.out_exp[el] = E;
+  }
+}
+
+// The closing add's lists for a range of `ncell` cells whose runs are `nruns` consecutive rows of the partials, from
+// row `run_base` on: segment (cell, c) = cell C + c sums the partials (run, c) of the cell's runs,
+//
+//   seg_off[cell C + c] = rel(cell) C + c len(cell),     index[seg_off[cell C + c] + q] = (run_base + rel(cell) + q) C + c,
+//
+// with rel = run_off[cell] - run_off[0] and len = run_off[cell + 1] - run_off[cell] (run_off: the exclusive scan of the
+// cells' run counts, [ncell + 1] entries of the range). One lane per (run, column) finds the run's cell by bisection
+// (the last cell whose offset is <= the run, which skips empty cells) and one lane per segment writes its offset.
+struct HistSegColsParams {
+  const long long* run_off;   // [ncell + 1]
+  long long ncell, nruns, run_base;
+  int C;
+  long long* seg_off;         // [ncell C + 1]
+  long long* index;           // [nruns C]
+};
+
+template <int DUMMY = 0>
+__global__ __launch_bounds__(256) void k_hist_seg_cols(HistSegColsParams p) {
+  const long long step = (long long)gridDim.x * 256, first = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long C = p.C, o0 = p.run_off[0];
+  for (long long s = first; s <= p.ncell * C; s += step) {
+    const long long cell = s / C, c = s - cell * C;
+    p.seg_off[s] = cell == p.ncell ? p.nruns * C : (p.run_off[cell] - o0) * C + c * (p.run_off[cell + 1] - p.run_off[cell]);
+  }
+  for (long long u = first; u < p.nruns * C; u += step) {
+    const long long r = u / C, c = u - r * C;
+    long long lo = 0, hi = p.ncell;
+    while (hi - lo > 1) {
+      const long long mid = lo + (hi - lo) / 2;
+      if (p.run_off[mid] - o0 <= r) lo = mid;
+      else hi = mid;
+    }
+    const long long rel = p.run_off[lo] - o0, len = p.run_off[lo + 1] - p.run_off[lo];
+    p.index[rel * C + c * len + (r - rel)] = (p.run_base + r) * C + c;
+  }
+}
+
 }  // namespace fpai

@@ -57,6 +57,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_pack_max_slots", "pai_encrypt_packed", "pai_encrypt_packed_dev", "pai_decrypt_packed",
             "pai_decrypt_packed_dev", "pai_pack_ciphertexts", "pai_pack_ciphertexts_dev", "pai_repack", "pai_repack_dev",
             "pai_segment_dot", "pai_segment_dot_dev", "pai_histogram", "pai_histogram_dev",
+            "pai_histogram_cols", "pai_histogram_cols_dev",
             "pai_histogram_sparse", "pai_histogram_sparse_dev",
             "pai_cumsum", "pai_cumsum_dev",
             "pai_pool_reserve", "pai_pool_fill", "pai_pool_fill_dev", "pai_pool_put", "pai_pool_put_dev", "pai_pool_info",
@@ -143,6 +144,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_segment_dot_dev.argtypes = [P, P, P, S, P, P, S, I, P, P, P, P, P]
         lib.pai_histogram.argtypes = [P, P, P, S, I, P, S, S, P, S, S, P, P, P]
         lib.pai_histogram_dev.argtypes = [P, P, P, S, I, P, S, S, P, S, S, P, P, P, P]
+        lib.pai_histogram_cols.argtypes = [P, P, P, S, S, I, P, S, S, P, S, S, P, P, P]
+        lib.pai_histogram_cols_dev.argtypes = [P, P, P, S, S, I, P, S, S, P, S, S, P, P, P, P]
         lib.pai_histogram_sparse.argtypes = [P, P, P, S, P, P, I, P, S, P, P, S, S, P, P, P]
         lib.pai_histogram_sparse_dev.argtypes = [P, P, P, S, P, P, I, P, S, P, P, S, S, P, P, P, P]
         lib.pai_cumsum.argtypes = [P, P, P, S, S, S, I, P, P]
@@ -1019,15 +1022,21 @@ class Context:
                                         _ptr(out), _ptr(oe)))
         return out, oe
 
-    def histogram(self, ct: np.ndarray, exp: np.ndarray, bins: np.ndarray, n_bins: int, node=None, n_nodes: int = 1):
+    def histogram(self, ct: np.ndarray, exp: np.ndarray, bins: np.ndarray, n_bins: int, node=None, n_nodes: int = 1,
+                  cols=None):
         """Per-cell sums of the N ciphertexts over bins [N, F] (uint8 / uint16, rows may be strided) and an optional
         int32 node id per sample (pai_histogram, one call, no index list). Returns (words [n_nodes F n_bins, W],
         exponents, counts int64), cell (v, f, b) at (v F + f) n_bins + b; an empty cell gives ciphertext 1 and exponent
-        INT32_MIN. The arguments are the checked ones of cipher_buffer.histogram_args."""
+        INT32_MIN. The arguments are the checked ones of cipher_buffer.histogram_args.
+        With `cols` = C (pai_histogram_cols, C = 1 included) ct holds C ciphertexts per sample ([N C, W], row-major)
+        and the outputs C per cell, (cell, column) at cell C + column; the counts stay one per cell."""
         ct = np.ascontiguousarray(ct, dtype=np.uint32)
         exp = np.ascontiguousarray(exp, dtype=np.int32)
-        N = exp.size
-        self._check_words(ct, exp, N)
+        C = 1 if cols is None else int(cols)
+        self._check_words(ct, exp, exp.size)
+        N = exp.size // C if C > 0 else bins.shape[0]          # (C = 0 is the library's to refuse)
+        if N * C != exp.size:
+            raise ValueError("histogram: the ciphertexts must fill whole rows of cols columns")
         if bins.ndim != 2 or bins.shape[0] != N or bins.dtype not in (np.uint8, np.uint16):
             raise ValueError("histogram: bins must be a uint8 / uint16 matrix with one row per ciphertext")
         isz = bins.dtype.itemsize
@@ -1042,10 +1051,18 @@ class Context:
             if node.shape != (N,):
                 raise ValueError("histogram: one node id per ciphertext")
         cells = int(n_nodes) * F * int(n_bins)
+        cnt = np.empty(max(cells, 0), dtype=np.int64)
+        if cols is not None:
+            self.calls["pai_histogram_cols"] += 1
+            out = np.empty((max(cells, 0) * C, self.ct_words), dtype=np.uint32)
+            oe = np.empty(max(cells, 0) * C, dtype=np.int32)
+            self._chk(self.lib.pai_histogram_cols(self._h, _ptr(ct), _ptr(exp), N, C, PAI_BIN_U16 if isz == 2 else PAI_BIN_U8,
+                                               _ptr(bins), F, stride, _ptr(node) if node is not None else None,
+                                               int(n_nodes), int(n_bins), _ptr(out), _ptr(oe), _ptr(cnt)))
+            return out, oe, cnt
         self.calls["pai_histogram"] += 1
         out = np.empty((max(cells, 0), self.ct_words), dtype=np.uint32)
         oe = np.empty(max(cells, 0), dtype=np.int32)
-        cnt = np.empty(max(cells, 0), dtype=np.int64)
         self._chk(self.lib.pai_histogram(self._h, _ptr(ct), _ptr(exp), N, PAI_BIN_U16 if isz == 2 else PAI_BIN_U8,
                                       _ptr(bins), F, stride, _ptr(node) if node is not None else None, int(n_nodes),
                                       int(n_bins), _ptr(out), _ptr(oe), _ptr(cnt)))

@@ -307,17 +307,24 @@ class CiphertextBuffer(BufferOps):
         pai_histogram_sparse call whose cost follows the stored entries: an entry that is not stored has bin
         default_bin (a scalar or one per feature, out of range: in no cell), and the default cell [v, f, default_bin[f]]
         is T_v - S: the node's total minus the feature's stored entries off the default bin, at the node's largest
-        exponent (the dense call's plaintext; its bits too wherever a node's exponents are uniform)."""
+        exponent (the dense call's plaintext; its bits too wherever a node's exponents are uniform).
+        A buffer of shape (N, C), C >= 2, over bins of N rows holds C ciphertext columns per sample (g and h, the C
+        gradients of multi-class boosting): ONE pai_histogram_cols call sums every column over the same member lists
+        and returns a buffer of shape (n_nodes, F, n_bins, C), so cumsum(axis=2) follows as it is; the counts keep the
+        shape (n_nodes, F, n_bins). Column c holds what histogram gives on column c alone. Dense bins only
+        (TypeError for sparse ones)."""
+        C = histogram_cols(self.shape, bins)
         csr = sparse_csr(bins)
         if csr is not None:
             *args, shape = histogram_sparse_args(self.size, csr, n_bins, node, n_nodes, default_bin)
             out, oe, cnt = histogram_sparse_words(self.public_key, self.words, self.exps, *args, shape)
             oe = np.where(cnt == 0, 0, oe).astype(np.int32)
             return self._like(out, oe, 0, shape), cnt.reshape(shape)
-        b, nd, shape = histogram_args(self.size, bins, n_bins, node, n_nodes)
-        out, oe, cnt = histogram_words(self.public_key, self.words, self.exps, b, int(n_bins), nd, int(n_nodes))
-        oe = np.where(cnt == 0, 0, oe).astype(np.int32)
-        return self._like(out, oe, 0, shape), cnt.reshape(shape)
+        b, nd, shape = histogram_args(self.size // C, bins, n_bins, node, n_nodes)
+        out_shape = histogram_out_shape(shape, C)
+        out, oe, cnt = histogram_words(self.public_key, self.words, self.exps, b, int(n_bins), nd, int(n_nodes), C)
+        oe = np.where(np.repeat(cnt, C) == 0, 0, oe).astype(np.int32)
+        return self._like(out, oe, 0, out_shape), cnt.reshape(shape)
 
     def cumsum(self, axis: int = -1, reverse: bool = False) -> "CiphertextBuffer":
         """Running sums along `axis` (reverse: from the end), same shape, in ONE pai_cumsum call: element j is the
@@ -590,6 +597,27 @@ def histogram_args(N: int, bins, n_bins, node, n_nodes):
     return bins, node, (int(n_nodes), F, int(n_bins))
 
 
+def histogram_cols(shape, bins) -> int:
+    """C for a buffer of shape (N, C), C >= 2, over bins of N rows: C ciphertext columns per sample. 1 for every other
+    buffer: its ciphertexts in flat order are the samples (so shape (N, 1) is a flat buffer, as ever). TypeError for
+    sparse bins under several columns, before they are converted."""
+    rows = (tuple(getattr(bins, "shape", ())) + (None,))[0]
+    if len(shape) != 2 or shape[1] < 2 or shape[0] != rows:
+        return 1
+    if not isinstance(bins, np.ndarray) and hasattr(bins, "tocsr"):
+        raise TypeError("histogram: a buffer of several columns takes dense bins, not sparse ones")
+    return int(shape[1])
+
+
+def histogram_out_shape(shape, cols: int):
+    """The cells' shape with the column axis last, and the library's limit on cells x columns."""
+    if cols == 1:
+        return shape
+    if shape[0] * shape[1] * shape[2] * cols > 1 << 24:
+        raise ValueError("histogram: more than 2^24 cells x columns")
+    return tuple(shape) + (cols,)
+
+
 def histogram_cells(bins, n_bins: int, node, n_nodes: int):
     """Host side of the cell rule: the flat cell (v F + f) n_bins + b of every (sample, feature) pair, -1 where the
     sample is in no cell of that feature; shape [N, F]."""
@@ -601,28 +629,32 @@ def histogram_cells(bins, n_bins: int, node, n_nodes: int):
     return np.where(ok, cell, -1)
 
 
-def histogram_words(pk, words, exps, bins, n_bins: int, node, n_nodes: int):
-    """(words [cells, W], exponents [cells], counts int64 [cells]) of the histogram over checked arguments: pai_histogram
-    on the GPU, products of Python integers without one. Empty cells: ciphertext 1, exponent EMPTY_EXP."""
+def histogram_words(pk, words, exps, bins, n_bins: int, node, n_nodes: int, cols: int = 1):
+    """(words [cells cols, W], exponents [cells cols], counts int64 [cells]) of the histogram over checked arguments:
+    pai_histogram (cols = 1) or pai_histogram_cols (words [N cols, W]: `cols` ciphertexts per sample, output
+    (cell, column) at cell cols + column) on the GPU, products of Python integers without one. Empty cells: ciphertext
+    1, exponent EMPTY_EXP, in every column."""
     from . import _runtime
     if _device_words(words):
         from . import device_buffer
-        return device_buffer.histogram_dev(pk, words, exps, bins, n_bins, node, n_nodes)
+        return device_buffer.histogram_dev(pk, words, exps, bins, n_bins, node, n_nodes, cols)
     if _runtime.gpu_available():
-        return _runtime.context(pk).histogram(words, exps, bins, n_bins, node, n_nodes)
+        return _runtime.context(pk).histogram(words, exps, bins, n_bins, node, n_nodes, cols if cols > 1 else None)
     W = words.shape[1]
     cells = n_nodes * bins.shape[1] * n_bins
     cell = histogram_cells(bins, n_bins, node, n_nodes)
     cts, nsq = _ints(words), pk.nsquare
-    E = np.full(cells, EMPTY_EXP, dtype=np.int64)
+    ex = np.asarray(exps, dtype=np.int64).reshape(-1, cols)
+    E = np.full((cells, cols), EMPTY_EXP, dtype=np.int64)
     ii, ff = np.nonzero(cell >= 0)
-    np.maximum.at(E, cell[ii, ff], np.asarray(exps, dtype=np.int64)[ii])
+    np.maximum.at(E, cell[ii, ff], ex[ii])
     cnt = np.bincount(cell[ii, ff], minlength=cells).astype(np.int64)
-    acc = [1] * cells
+    acc = [1] * (cells * cols)
     for i, f in zip(ii.tolist(), ff.tolist()):
         s = int(cell[i, f])
-        acc[s] = acc[s] * pow(cts[i], 16 ** (int(E[s]) - int(exps[i])), nsq) % nsq
-    return _runtime.ints_to_words(acc, W).reshape(cells, W), E.astype(np.int32), cnt
+        for c in range(cols):
+            acc[s * cols + c] = acc[s * cols + c] * pow(cts[i * cols + c], 16 ** int(E[s, c] - ex[i, c]), nsq) % nsq
+    return _runtime.ints_to_words(acc, W).reshape(cells * cols, W), E.astype(np.int32).reshape(-1), cnt
 
 
 def sparse_csr(b):

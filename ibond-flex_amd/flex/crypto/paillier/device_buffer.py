@@ -36,7 +36,7 @@ import numpy as np
 
 from . import _native
 from .cipher_buffer import (EMPTY_EXP, BufferOps, CiphertextBuffer, _plain, axis_split, histogram_args,
-                            histogram_sparse_args, need_gpu, segment_dot_args, sparse_csr)
+                            histogram_cols, histogram_out_shape, histogram_sparse_args, need_gpu, segment_dot_args, sparse_csr)
 from .encrypted_number import PaillierEncryptedNumber
 
 
@@ -322,9 +322,10 @@ def histogram_resident_args(N: int, bins, n_bins, node, n_nodes):
     return bins, node, shape
 
 
-def histogram_dev(pk, words: DeviceWords, exps, bins, n_bins: int, node, n_nodes: int):
+def histogram_dev(pk, words: DeviceWords, exps, bins, n_bins: int, node, n_nodes: int, cols: int = 1):
     """pai_histogram_dev over the checked arguments of cipher_buffer.histogram_args: (words [cells, W], exponents,
-    counts int64 on the host). Only the bins and the node ids go up, and not even those when they are DeviceArrays."""
+    counts int64 on the host). Only the bins and the node ids go up, and not even those when they are DeviceArrays.
+    cols = C >= 2: pai_histogram_cols_dev over words [N C, W], (words [cells C, W], exponents, counts [cells])."""
     (N, W), dev = words.shape, words.device
     for a in (bins, node):
         if isinstance(a, DeviceArray) and a.device != dev:
@@ -340,10 +341,13 @@ def histogram_dev(pk, words: DeviceWords, exps, bins, n_bins: int, node, n_nodes
         dn = node.mem
     else:
         dn = _native.device_upload(np.ascontiguousarray(node, dtype=np.int32), dev) if node is not None else None
-    out, oe, cnt = DeviceWords.empty(cells, W, dev), _i32(dev, cells), _native.DeviceMem(cells * 8, dev)
-    ctx.dev_call("pai_histogram_dev", words.ptr, ex.ptr, N,
-                 _native.PAI_BIN_U16 if bins.dtype.itemsize == 2 else _native.PAI_BIN_U8, db.ptr, F, F,
-                 dn.ptr if dn is not None else None, int(n_nodes), int(n_bins), out.ptr, oe.ptr, cnt.ptr)
+    out, oe, cnt = DeviceWords.empty(cells * cols, W, dev), _i32(dev, cells * cols), _native.DeviceMem(cells * 8, dev)
+    tail = (_native.PAI_BIN_U16 if bins.dtype.itemsize == 2 else _native.PAI_BIN_U8, db.ptr, F, F,
+            dn.ptr if dn is not None else None, int(n_nodes), int(n_bins), out.ptr, oe.ptr, cnt.ptr)
+    if cols > 1:
+        ctx.dev_call("pai_histogram_cols_dev", words.ptr, ex.ptr, N // cols, cols, *tail)
+    else:
+        ctx.dev_call("pai_histogram_dev", words.ptr, ex.ptr, N, *tail)
     return out, oe, cnt.download(np.int64, cells)
 
 
@@ -716,21 +720,22 @@ class DeviceCiphertextBuffer(BufferOps):
         of shape (n_nodes, F, n_bins), int64 counts on the host). The empty cells' exponents are set to 0 on the
         exponents alone. Dense bins (uint8 / uint16, C-contiguous [N, F]) and node (int32 [N]) may be DeviceArrays: their
         pointers are passed through and nothing is uploaded for them, so a training run uploads its bins once. Sparse
-        bins stay host operands."""
+        bins stay host operands. A buffer of shape (N, C), C >= 2, over bins of N rows: pai_histogram_cols_dev, shape
+        (n_nodes, F, n_bins, C), as CiphertextBuffer.histogram."""
+        C = histogram_cols(self.shape, bins)
         csr = None if isinstance(bins, DeviceArray) else sparse_csr(bins)
         if csr is not None:
             if isinstance(node, DeviceArray):
                 raise TypeError("histogram: sparse bins take host node ids")
             *args, shape = histogram_sparse_args(self.size, csr, n_bins, node, n_nodes, default_bin)
             out, oe, cnt = histogram_sparse_dev(self.public_key, self.words, self._ex, *args, shape)
-        elif isinstance(bins, DeviceArray) or isinstance(node, DeviceArray):
-            b, nd, shape = histogram_resident_args(self.size, bins, n_bins, node, n_nodes)
-            out, oe, cnt = histogram_dev(self.public_key, self.words, self._ex, b, int(n_bins), nd, int(n_nodes))
         else:
-            b, nd, shape = histogram_args(self.size, bins, n_bins, node, n_nodes)
-            out, oe, cnt = histogram_dev(self.public_key, self.words, self._ex, b, int(n_bins), nd, int(n_nodes))
-        e = np.where(cnt == 0, 0, oe.download(np.int32, cnt.size)).astype(np.int32)
-        return self._like(out, e, 0, shape), cnt.reshape(shape)
+            resident = isinstance(bins, DeviceArray) or isinstance(node, DeviceArray)
+            b, nd, shape = (histogram_resident_args if resident else histogram_args)(self.size // C, bins, n_bins, node, n_nodes)
+            histogram_out_shape(shape, C)          # (the limit on cells x columns, before anything is allocated)
+            out, oe, cnt = histogram_dev(self.public_key, self.words, self._ex, b, int(n_bins), nd, int(n_nodes), C)
+        e = np.where(np.repeat(cnt, C) == 0, 0, oe.download(np.int32, cnt.size * C)).astype(np.int32)
+        return self._like(out, e, 0, histogram_out_shape(shape, C)), cnt.reshape(shape)
 
     def cumsum(self, axis: int = -1, reverse: bool = False) -> "DeviceCiphertextBuffer":
         """CiphertextBuffer.cumsum on the device (pai_cumsum_dev): launches only."""

@@ -200,11 +200,15 @@ def _histogram_operand(x, who: str):
     return pk, words, exps
 
 
-def _histogram_cells(pk, words, exps, bins, n_bins, node, n_nodes, default_bin):
+def _histogram_cells(pk, words, exps, bins, n_bins, node, n_nodes, default_bin, cols=1):
     """(words, exponents, counts, shape) of the histogram's cells: sparse bins (anything that offers .tocsr()) through
-    pai_histogram_sparse, a numpy matrix through pai_histogram."""
+    pai_histogram_sparse, a numpy matrix through pai_histogram, or through pai_histogram_cols when the operand holds
+    `cols` >= 2 ciphertexts per sample."""
     from .cipher_buffer import histogram_args, histogram_sparse_args, histogram_sparse_words, histogram_words, sparse_csr
     csr = sparse_csr(bins)
+    if cols > 1:
+        b, nd, shape = histogram_args(words.shape[0] // cols, bins, n_bins, node, n_nodes)
+        return histogram_words(pk, words, exps, b, shape[2], nd, shape[0], cols) + (shape,)
     if csr is not None:
         *args, shape = histogram_sparse_args(words.shape[0], csr, n_bins, node, n_nodes, default_bin)
         return histogram_sparse_words(pk, words, exps, *args, shape) + (shape,)
@@ -222,14 +226,18 @@ def histogram(x, bins, n_bins, node=None, n_nodes=1, default_bin=0):
     Without a GPU the same runs on Python integers.
     Sparse bins (anything that offers .tocsr()) take ONE pai_histogram_sparse call over the stored entries; every entry
     that is not stored has bin default_bin (a scalar or one per feature), and the default cell is the node's total minus
-    the feature's other stored entries (``T - S`` of the reference's operators, CiphertextBuffer.histogram)."""
+    the feature's other stored entries (``T - S`` of the reference's operators, CiphertextBuffer.histogram).
+    An x of shape (N, C), C >= 2, over dense bins of N rows holds C ciphertexts per sample: ONE pai_histogram_cols call
+    over shared member lists, result of shape (n_nodes, F, n_bins, C), counts of shape (n_nodes, F, n_bins)."""
     from .cipher_array import materialize
+    from .cipher_buffer import histogram_cols, histogram_out_shape
     if _on_device(x):
         return x.histogram(bins, n_bins, node=node, n_nodes=n_nodes, default_bin=default_bin)
+    C = histogram_cols(np.shape(x), bins)
     pk, words, exps = _histogram_operand(x, "histogram")
-    out, oe, cnt, shape = _histogram_cells(pk, words, exps, bins, n_bins, node, n_nodes, default_bin)
-    oe = np.where(cnt == 0, 0, oe).astype(np.int32)
-    return materialize(pk, out, oe, shape, obfuscated=False), cnt.reshape(shape)
+    out, oe, cnt, shape = _histogram_cells(pk, words, exps, bins, n_bins, node, n_nodes, default_bin, C)
+    oe = np.where(np.repeat(cnt, C) == 0, 0, oe).astype(np.int32)
+    return materialize(pk, out, oe, histogram_out_shape(shape, C), obfuscated=False), cnt.reshape(shape)
 
 
 def histogram_packed(x, bins, n_bins, layout, max_abs, node=None, n_nodes=1, default_bin=0):

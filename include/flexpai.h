@@ -408,6 +408,30 @@ enum { PAI_BIN_U8 = 0, PAI_BIN_U16 = 1 };
 int pai_histogram(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int bin_dtype, const void* bins,
                   size_t F, size_t bin_stride, const int32_t* node, size_t nodes, size_t B, uint32_t* ct_out,
                   int32_t* exp_out, int64_t* count_out);
+/* pai_histogram over C ciphertext columns per sample in one call (unpacked g and h, the C gradients of multi-class
+ * boosting, several label columns of IV_FFS): ct is [N][C][W] row-major and exp [N][C]. Cell (v, f, b), column c is at
+ * index ((v F + f) B + b) C + c of ct_out / exp_out: the output is (nodes, F, B, C), columns last, so pai_cumsum runs
+ * along B with inner = C on it as it is. count_out (nullable) stays nodes F B entries: the members of a cell do not
+ * depend on the column.
+ *   BITS: for every c, ct_out[..., c] and exp_out[..., c] equal bit for bit what pai_histogram returns for the
+ *   contiguous copy of column c. So E is the largest exponent of THAT COLUMN's members in the cell, the value is
+ *   prod c_i^(16^(E - e_i)) mod n^2, canonical; an empty cell is ciphertext 1 with exponent INT32_MIN in every column;
+ *   a node id outside [0, nodes) and a bin id >= B put the sample in no cell and are no errors; runs, feature blocks and
+ *   the host variant's chunks change no bit. C = 1 is pai_histogram.
+ *   PAI_ERR_ARG before any launch: everything pai_histogram refuses, C = 0, nodes F B C above 2^24, N C at or above
+ *   2^31.
+ * The member lists depend on bins and node alone, so k_hist_count, the read-back of the counts and k_hist_scatter run
+ * once for all columns. k_hist_acc_c sums the runs: a work item is (run, column), a block takes the columns of
+ * consecutive runs and keeps those runs' member ids in LDS, and every lane group reads its operands straight from
+ * ct + (i C + c) W. The partials [run][C] of a feature block are summed per (cell, column) by the segmented add over
+ * index lists that k_hist_seg_cols writes on the device. The scratch budget (256 MiB) covers a feature block's member
+ * lists and its C partials per run. The host-buffer variant moves whole rows of C ciphertexts in chunks of 65536 / C
+ * samples and combines the chunks' cell sums with one k-way add.
+ * The _dev variant synchronises `stream` once, to read the cell counts; the closing add is planned on the device, so
+ * the count does not depend on C (nor on the cells' sizes). */
+int pai_histogram_cols(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, size_t C, int bin_dtype,
+                       const void* bins, size_t F, size_t bin_stride, const int32_t* node, size_t nodes, size_t B,
+                       uint32_t* ct_out, int32_t* exp_out, int64_t* count_out);
 /* pai_histogram over a sparse bin matrix, at a cost that follows the stored entries. The matrix is CSR: indptr holds
  * N + 1 offsets that start at 0 and never decrease, indices the feature of every stored entry (inside [0, F), strictly
  * increasing inside a row), data its bin id (PAI_BIN_U8 / PAI_BIN_U16). Every (i, f) that is not stored has bin
@@ -509,6 +533,9 @@ int pai_segment_dot_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp
 int pai_histogram_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int bin_dtype,
                       const void* d_bins, size_t F, size_t bin_stride, const int32_t* d_node, size_t nodes, size_t B,
                       uint32_t* d_out, int32_t* d_exp_out, int64_t* d_count_out, void* stream);
+int pai_histogram_cols_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, size_t C, int bin_dtype,
+                           const void* d_bins, size_t F, size_t bin_stride, const int32_t* d_node, size_t nodes,
+                           size_t B, uint32_t* d_out, int32_t* d_exp_out, int64_t* d_count_out, void* stream);
 int pai_histogram_sparse_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_indptr,
                              const int32_t* d_indices, int bin_dtype, const void* d_data, size_t F,
                              const int32_t* d_default_bin, const int32_t* d_node, size_t nodes, size_t B,
