@@ -52,6 +52,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_sgs.hpp"
 #include "engine_grp.hpp"
 #include "engine_mul.hpp"
+#include "engine_big.hpp"
 #include "engine_mm.hpp"
 #include "engine_sd.hpp"
 #include "engine_hist.hpp"
@@ -262,6 +263,7 @@ struct pai_ctx {
   size_t take_bytes = 0;
   uint32_t* d_nsq32 = nullptr;  // n^2 in 32-bit words (pai_check_below_dev), uploaded at its first call
   void* d_plain = nullptr;      // ciphertext + plaintext: the two k_add operands and their exponents
+  uint32_t* d_big_maxint = nullptr;   // max_int = n // 3 - 1 as S_e limbs, for the PAI_BIG range tests (ensure_big)
   size_t plain_bytes = 0;
   // re-randomisation (pai_obfuscate_dev): the zero plaintexts, scratch exponents and statuses of the encryption that
   // yields r^n, and, for in-place calls, r^n of one slice of obf_chunk elements (PAI_OPT_OBF_CHUNK)
@@ -4466,6 +4468,217 @@ int pai_add_plain_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, si
   p.max_bits = c->nb - 3;
   HIPCHK(plain_launch(c->tpi_e, p, (long long)N, c->cus, st));
   return add_dev(c, ops, oexp, 2, (long long)N, d_out, d_exp_out, st);
+}
+
+// ------------------------------------------------------------------ wide integers (PAI_BIG, kernels_big.hpp)
+// max_int as limbs, once per context: both kernels compare magnitudes against it limb for limb
+static int ensure_big(pai_ctx* c) {
+  if (c->d_big_maxint) return 0;
+  return upload_to(c->allocs, sub(div_small(c->n, 3), HBig(1)).limbs(c->S_e, LB), &c->d_big_maxint);
+}
+
+static bool big_operand_ok(const pai_ctx* c, const void* x, size_t xw, size_t x_stride) {
+  return x && xw >= 1 && xw <= (size_t)c->ct_words / 2 && x_stride <= 1;
+}
+
+static int launch_big_c0(pai_ctx* c, const BigOperand& v, const int32_t* d_exp, size_t N, uint32_t* c0, int32_t* e0,
+                         int32_t* status, hipStream_t st) {
+  int rc = ensure_big(c);
+  if (rc) return rc;
+  BigC0Params p{};
+  p.v = v;
+  p.exp = d_exp;
+  p.n = (long long)N;
+  p.c0 = c0;
+  p.e0 = e0;
+  p.status = status;
+  p.N = c->d_N;
+  p.nl = c->d_nl;
+  p.maxint = c->d_big_maxint;
+  p.ct_words = c->ct_words;
+  p.nb = c->nb;
+  HIPCHK(big_c0_launch(c->tpi_e, p, c->cus, st));
+  return 0;
+}
+
+// k_big_c0 writes the PAI_OBF_NONE ciphertexts into d_ct; r^n then meets them exactly as it meets any ciphertext that
+// is re-randomised in place (pai_obfuscate_dev: the route of an int64-zero encryption of these N elements, slices of
+// PAI_OPT_OBF_CHUNK, one k_obf_mul each; pooled obfuscators joined and multiplied the same way). No sampler, chain or
+// break-even counter learns of the operand type.
+int pai_encrypt_big_dev(pai_ctx* c, const uint32_t* d_x, const uint8_t* d_neg, size_t xw, size_t N, int obf_mode,
+                        const uint32_t* d_r_words, size_t r_stride_words, size_t r_words, const uint8_t* rng_key32,
+                        uint64_t index_base, uint32_t* d_ct, int32_t* d_exp, int32_t* d_status, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (N == 0) return 0;
+  if (!big_operand_ok(c, d_x, xw, 1) || !d_ct || !d_exp) return fail(PAI_ERR_ARG, "pai_encrypt_big_dev: bad arguments");
+  if (obf_mode < 0 || obf_mode > PAI_OBF_POOL) return fail(PAI_ERR_ARG, "pai_encrypt_big_dev: bad obf_mode");
+  if (obf_mode == PAI_OBF_GIVEN && (!d_r_words || r_words == 0 || r_words > (size_t)c->ct_words))
+    return fail(PAI_ERR_ARG, "pai_encrypt_big_dev: r must be given with 0 < r_words <= ct_words");
+  if (obf_mode == PAI_OBF_RNG && !rng_key32) return fail(PAI_ERR_ARG, "pai_encrypt_big_dev: rng key required");
+  int rc;
+  if (obf_mode == PAI_OBF_POOL && (rc = pool_check_take(c, N, "pai_encrypt_big_dev"))) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  if ((rc = launch_big_c0(c, BigOperand{d_x, d_neg, (int)xw, 1}, nullptr, N, d_ct, d_exp, d_status, (hipStream_t)stream)))
+    return rc;
+  if (obf_mode == PAI_OBF_NONE) return 0;
+  return pai_obfuscate_dev(c, d_ct, N, obf_mode, d_r_words, r_stride_words, r_words, rng_key32, index_base, d_ct, stream);
+}
+
+// E(x) + v: k_big_c0 with the shift 4 max(e_x, 0) writes (c0, E) as the second operand of the 2-way k_add, like k_plain
+int pai_add_plain_big_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const uint32_t* d_x,
+                          const uint8_t* d_neg, size_t xw, size_t x_stride, uint32_t* d_out, int32_t* d_exp_out,
+                          int32_t* d_status, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (N == 0) return 0;
+  if (!d_ct || !d_exp || !d_out || !d_exp_out || !big_operand_ok(c, d_x, xw, x_stride))
+    return fail(PAI_ERR_ARG, "pai_add_plain_big_dev: bad arguments");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t W = c->ct_words, cbytes = align16(2 * N * W * 4);
+  int rc = ensure_buf(&c->d_plain, &c->plain_bytes, cbytes + 2 * N * 4);
+  if (rc) return rc;
+  uint32_t* ops = (uint32_t*)c->d_plain;
+  int32_t* oexp = (int32_t*)((char*)c->d_plain + cbytes);
+  HIPCHK(hipMemcpyAsync(ops, d_ct, N * W * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(oexp, d_exp, N * 4, hipMemcpyDeviceToDevice, st));
+  if ((rc = launch_big_c0(c, BigOperand{d_x, d_neg, (int)xw, (long long)x_stride}, d_exp, N, ops + N * W, oexp + N, d_status,
+                          st)))
+    return rc;
+  return add_dev(c, ops, oexp, 2, (long long)N, d_out, d_exp_out, st);
+}
+
+// E(x) * k: k_mul_big with the window of the call's exponent width, then pai_mul's batch inversion of the flagged terms
+int pai_mul_big_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const uint32_t* d_x,
+                    const uint8_t* d_neg, size_t xw, size_t x_stride, uint32_t* d_out, int32_t* d_exp_out,
+                    int32_t* d_status, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (N == 0) return 0;
+  if (!d_ct || !d_exp || !d_out || !d_exp_out || !big_operand_ok(c, d_x, xw, x_stride))
+    return fail(PAI_ERR_ARG, "pai_mul_big_dev: bad arguments");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  int rc = ensure_buf(&c->d_mul, &c->mul_bytes, N);
+  if (rc || (rc = ensure_big(c))) return rc;
+  MulBigParams p{};
+  p.ct = d_ct;
+  p.exp = d_exp;
+  p.k = BigOperand{d_x, d_neg, (int)xw, (long long)x_stride};
+  p.win = big_window(std::min<int>(32 * (int)xw, c->nb));
+  p.n = (long long)N;
+  p.out = d_out;
+  p.out_exp = d_exp_out;
+  p.status = d_status;
+  p.neg = (uint8_t*)c->d_mul;
+  p.N = c->d_N;
+  p.R2 = c->d_R2;
+  p.oneR = c->d_oneR;
+  p.maxint = c->d_big_maxint;
+  p.mprime = c->mprime_N;
+  p.ct_words = c->ct_words;
+  int occ = 1;
+  if (mul_big_occupancy(c->tpi_e, p.k.xw, &occ)) return fail(PAI_ERR_KEY, "unsupported group size");
+  const int gpb = BLOCK / c->tpi_e;
+  const int grid = (int)std::max<long long>(1, std::min<long long>((p.n + gpb - 1) / gpb, (long long)occ * c->cus));
+  if ((rc = ensure_scratch(c, (size_t)grid * BLOCK * ((size_t)TROW << p.win) * 4))) return rc;
+  p.scratch = (uint32_t*)c->d_scratch;
+  HIPCHK(mul_big_launch(c->tpi_e, p, grid, st));
+  return batch_invert(c, d_out, (const uint8_t*)c->d_mul, (long long)N, st);
+}
+
+// Host buffers: the operands go up, the device entry runs on the null stream, the results come back
+struct BigHostOperand {
+  uint32_t* dx = nullptr;
+  uint8_t* dneg = nullptr;
+  int up(DevScope& ds, const uint32_t* x, const uint8_t* neg, size_t rows, size_t xw) {
+    dx = ds.alloc<uint32_t>(rows * xw);
+    if (neg) dneg = ds.alloc<uint8_t>(rows);
+    if (!dx || (neg && !dneg)) return fail(PAI_ERR_HIP, "PAI_BIG operand: device allocation failed");
+    HIPCHK(hipMemcpy(dx, x, rows * xw * 4, hipMemcpyHostToDevice));
+    if (neg) HIPCHK(hipMemcpy(dneg, neg, rows, hipMemcpyHostToDevice));
+    return 0;
+  }
+};
+
+int pai_encrypt_big(pai_ctx* c, const uint32_t* x, const uint8_t* neg, size_t xw, size_t N, int obf_mode,
+                    const uint8_t* r_le, size_t r_stride_bytes, size_t r_bytes, const uint8_t* rng_key32,
+                    uint64_t index_base, uint32_t* ct_out, int32_t* exp_out, int32_t* status_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  if (N == 0) return 0;
+  if (!big_operand_ok(c, x, xw, 1) || !ct_out || !exp_out) return fail(PAI_ERR_ARG, "pai_encrypt_big: bad arguments");
+  if (obf_mode == PAI_OBF_GIVEN && (!r_le || r_bytes == 0)) return fail(PAI_ERR_ARG, "pai_encrypt_big: r required");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t W = c->ct_words;
+  const size_t r_words = obf_mode == PAI_OBF_GIVEN ? (r_bytes + 3) / 4 : 0;
+  const size_t r_cnt = obf_mode == PAI_OBF_GIVEN ? (r_stride_bytes ? N : 1) : 0;
+  DevScope ds;
+  BigHostOperand v;
+  int rc = v.up(ds, x, neg, N, xw);
+  if (rc) return rc;
+  uint32_t* dct = ds.alloc<uint32_t>(N * W);
+  int32_t* dexp = ds.alloc<int32_t>(N);
+  int32_t* dst = ds.alloc<int32_t>(N);
+  uint32_t* dr = r_cnt ? ds.alloc<uint32_t>(r_cnt * r_words) : nullptr;
+  if (!dct || !dexp || !dst || (r_cnt && !dr)) return fail(PAI_ERR_HIP, "pai_encrypt_big: device allocation failed");
+  if (r_cnt) {
+    std::vector<uint32_t> hr(r_cnt * r_words, 0);
+    for (size_t i = 0; i < r_cnt; ++i) std::memcpy(&hr[i * r_words], r_le + i * r_stride_bytes, r_bytes);
+    HIPCHK(hipMemcpy(dr, hr.data(), hr.size() * 4, hipMemcpyHostToDevice));
+  }
+  rc = pai_encrypt_big_dev(c, v.dx, v.dneg, xw, N, obf_mode, dr, r_stride_bytes ? r_words : 0, r_words, rng_key32, index_base,
+                           dct, dexp, dst, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(ct_out, dct, N * W * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(exp_out, dexp, N * 4, hipMemcpyDeviceToHost));
+  if (status_out) HIPCHK(hipMemcpy(status_out, dst, N * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+static int big_scalar_host(pai_ctx* c, bool mul, const uint32_t* ct, const int32_t* exp, size_t N, const uint32_t* x,
+                           const uint8_t* neg, size_t xw, size_t x_stride, uint32_t* ct_out, int32_t* exp_out,
+                           int32_t* status_out) {
+  const char* who = mul ? "pai_mul_big" : "pai_add_plain_big";
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  if (N == 0) return 0;
+  if (!ct || !exp || !ct_out || !exp_out || !big_operand_ok(c, x, xw, x_stride))
+    return fail(PAI_ERR_ARG, std::string(who) + ": bad arguments");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t W = c->ct_words;
+  DevScope ds;
+  BigHostOperand v;
+  int rc = v.up(ds, x, neg, x_stride ? N : 1, xw);
+  if (rc) return rc;
+  uint32_t* dct = ds.alloc<uint32_t>(N * W);
+  int32_t* dexp = ds.alloc<int32_t>(N);
+  uint32_t* dout = ds.alloc<uint32_t>(N * W);
+  int32_t* dexo = ds.alloc<int32_t>(N);
+  int32_t* dst = ds.alloc<int32_t>(N);
+  if (!dct || !dexp || !dout || !dexo || !dst) return fail(PAI_ERR_HIP, std::string(who) + ": device allocation failed");
+  HIPCHK(hipMemcpy(dct, ct, N * W * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dexp, exp, N * 4, hipMemcpyHostToDevice));
+  rc = mul ? pai_mul_big_dev(c, dct, dexp, N, v.dx, v.dneg, xw, x_stride, dout, dexo, dst, nullptr)
+           : pai_add_plain_big_dev(c, dct, dexp, N, v.dx, v.dneg, xw, x_stride, dout, dexo, dst, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(ct_out, dout, N * W * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(exp_out, dexo, N * 4, hipMemcpyDeviceToHost));
+  if (status_out) HIPCHK(hipMemcpy(status_out, dst, N * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pai_mul_big(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, const uint32_t* x, const uint8_t* neg,
+                size_t xw, size_t x_stride, uint32_t* ct_out, int32_t* exp_out, int32_t* status_out) {
+  return big_scalar_host(c, true, ct, exp, N, x, neg, xw, x_stride, ct_out, exp_out, status_out);
+}
+
+int pai_add_plain_big(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, const uint32_t* x, const uint8_t* neg,
+                      size_t xw, size_t x_stride, uint32_t* ct_out, int32_t* exp_out, int32_t* status_out) {
+  return big_scalar_host(c, false, ct, exp, N, x, neg, xw, x_stride, ct_out, exp_out, status_out);
 }
 
 // Segmented k-way add (per-bin sums of IV_FFS, hetero_bin.py:28-36): a reduction tree of

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import operator
 import os
 import sys
 import threading
@@ -22,6 +23,7 @@ LIB_PATH = os.environ.get("FLEXPAI_LIB") or os.path.join(_HERE, "libflexpai.so")
 XCHECK_LIB_PATH = os.path.join(_HERE, "libflexpai_xcheck.so")
 
 PAI_F32, PAI_F64, PAI_I64 = 0, 1, 2
+PAI_BIG = 3         # wide integers: [N][xw] magnitude words and a sign byte each (big_operand, the pai_*_big entry points)
 PAI_OBF_NONE, PAI_OBF_GIVEN, PAI_OBF_RNG = 0, 1, 2
 PAI_OBF_POOL = 3     # the call's obfuscators come from the context's pool (pai_pool_*), in order, each exactly once
 PAI_EXP_AUTO, PAI_EXP_FIXED = 0, 1
@@ -50,6 +52,8 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_ctx_public_fb_policy",
             "pai_encrypt", "pai_add", "pai_decrypt", "pai_encrypt_dev", "pai_add_dev", "pai_decrypt_dev",
             "pai_mul", "pai_mul_dev", "pai_matmul", "pai_matmul_dev", "pai_add_plain", "pai_add_plain_dev",
+            "pai_encrypt_big", "pai_encrypt_big_dev", "pai_mul_big", "pai_mul_big_dev", "pai_add_plain_big",
+            "pai_add_plain_big_dev",
             "pai_segment_add", "pai_segment_add_dev", "pai_comm_unique_id", "pai_comm_create", "pai_comm_destroy",
             "pai_allgather_dev", "pai_allgather_shards_dev", "pai_release_table_cache", "pai_debug_encrypt_route",
             "pai_next_prime", "pai_prime_last_times", "pai_prime_test", "pai_debug_prime_sieve",
@@ -64,6 +68,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_dev_alloc", "pai_dev_free", "pai_dev_upload", "pai_dev_download", "pai_dev_copy", "pai_dev_io_stats",
             "pai_dev_release_staging", "pai_take_dev", "pai_check_below_dev",
             "pai_take_idx_dev", "pai_segment_add_idx_dev")
+BIG = tuple(n for n in EXPORTED if "_big" in n)     # PAI_BIG operands (include/flexpai.h)
 RESIDENT = EXPORTED[-11:-2]   # device-resident buffers (include/flexpai.h)
 DEVICE_INDEX = EXPORTED[-2:]  # take and segment sums over index lists that are device memory
 PAI_COMM_ID_BYTES = 128
@@ -181,8 +186,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         if device_index:
             lib.pai_take_idx_dev.argtypes = [P, P, P, S, P, S, I, P, P, P, P]
             lib.pai_segment_add_idx_dev.argtypes = [P, P, P, S, P, S, P, S, P, P, P, P]
+        big = hasattr(lib, "pai_mul_big")    # (absent from a library built from an earlier commit)
+        if big:
+            lib.pai_encrypt_big.argtypes = [P, P, P, S, S, I, P, S, S, P, U64, P, P, P]
+            lib.pai_encrypt_big_dev.argtypes = [P, P, P, S, S, I, P, S, S, P, U64, P, P, P, P]
+            lib.pai_mul_big.argtypes = lib.pai_add_plain_big.argtypes = [P, P, P, S, P, P, S, S, P, P, P]
+            lib.pai_mul_big_dev.argtypes = lib.pai_add_plain_big_dev.argtypes = [P, P, P, S, P, P, S, S, P, P, P, P]
         for name in EXPORTED:
-            if (not resident and name in RESIDENT) or (not device_index and name in DEVICE_INDEX):
+            if (not resident and name in RESIDENT) or (not device_index and name in DEVICE_INDEX) or (not big and name in BIG):
                 continue
             if name not in ("pai_ctx_destroy", "pai_last_error", "pai_comm_destroy", "pai_release_table_cache"):
                 getattr(lib, name).restype = ctypes.c_int
@@ -803,6 +814,38 @@ class Context:
                                     key, index_base, _ptr(ct), _ptr(ex), _ptr(st)))
         return ct, ex, st
 
+    def encrypt_big(self, x: np.ndarray, neg: np.ndarray, obf_mode: int = PAI_OBF_RNG, r: Optional[Sequence[int]] = None,
+                    r_scalar: Optional[int] = None, rng_key: Optional[bytes] = None, index_base: int = 0):
+        """pai_encrypt_big of a PAI_BIG operand (big_operand): (ct [N, W], exp [N], status [N]); r as for encrypt."""
+        N, xw = x.shape
+        ct = np.empty((N, self.ct_words), dtype=np.uint32)
+        ex = np.empty(N, dtype=np.int32)
+        st = np.empty(N, dtype=np.int32)
+        r_buf, r_stride, r_bytes = None, 0, 0
+        if obf_mode == PAI_OBF_GIVEN:
+            r_bytes = self.ct_words * 4
+            rs = [r_scalar] if r_scalar is not None else r
+            r_buf = np.frombuffer(b"".join(int_to_le(v, r_bytes) for v in rs), dtype=np.uint8).copy()
+            r_stride = 0 if r_scalar is not None else r_bytes
+        key = rng_key if rng_key is not None else os.urandom(32)
+        self.calls["pai_encrypt_big"] += 1
+        self._chk(self.lib.pai_encrypt_big(self._h, _ptr(x), _ptr(neg), xw, N, obf_mode,
+                                           _ptr(r_buf) if r_buf is not None else None, r_stride, r_bytes, key, index_base,
+                                           _ptr(ct), _ptr(ex), _ptr(st)))
+        return ct, ex, st
+
+    def _scalar_big(self, name: str, ct: np.ndarray, exp: np.ndarray, ints: np.ndarray):
+        """pai_mul_big / pai_add_plain_big with an object array of 1 or N integers."""
+        N = exp.size
+        x, neg, wide = big_operand(ints.reshape(-1), self.ct_words)
+        self.calls[name] += 1
+        out = np.empty((N, self.ct_words), dtype=np.uint32)
+        oe = np.empty(N, dtype=np.int32)
+        st = np.empty(N, dtype=np.int32)
+        self._chk(getattr(self.lib, name)(self._h, _ptr(ct), _ptr(exp), N, _ptr(x), _ptr(neg), x.shape[1],
+                                          1 if ints.size == N and N > 1 else 0, _ptr(out), _ptr(oe), _ptr(st)))
+        return out, oe, st if wide is None else np.where(wide, EL_ENC_RANGE, st).astype(np.int32)
+
     def obfuscate(self, ct: np.ndarray, obf_mode: int = PAI_OBF_RNG, r: Optional[Sequence[int]] = None,
                   r_scalar: Optional[int] = None, rng_key: Optional[bytes] = None, index_base: int = 0,
                   out: Optional[np.ndarray] = None) -> np.ndarray:
@@ -978,6 +1021,8 @@ class Context:
         self._check_words(ct, exp, N)
         if x.size not in (1, N):
             raise ValueError("scalar operand must have 1 or N elements")
+        if x.dtype == object:
+            return self._scalar_big("pai_mul_big", ct, exp, x)
         self.calls["pai_mul"] += 1
         out = np.empty((N, self.ct_words), dtype=np.uint32)
         oe = np.empty(N, dtype=np.int32)
@@ -996,6 +1041,8 @@ class Context:
         self._check_words(ct, exp, N)
         if x.size not in (1, N):
             raise ValueError("plain operand must have 1 or N elements")
+        if x.dtype == object:
+            return self._scalar_big("pai_add_plain_big", ct, exp, x)
         self.calls["pai_add_plain"] += 1
         out = np.empty((N, self.ct_words), dtype=np.uint32)
         oe = np.empty(N, dtype=np.int32)
@@ -1228,6 +1275,35 @@ def ints_to_words(vals, nwords: int) -> np.ndarray:
         nbytes = nwords * 4
         buf = b"".join(int(v).to_bytes(nbytes, "little") for v in vals)
     return np.frombuffer(buf, dtype="<u4").reshape(len(vals), nwords).copy()
+
+
+_py_int = np.frompyfunc(operator.index, 1, 1)
+
+
+def is_int_array(a) -> bool:
+    """A PAI_BIG operand: a non-empty object ndarray whose elements are all what FixedPointNumber.encode takes as an
+    integer without a precision (Python int, np.int16 / int32 / int64; no bool). Unsigned and other numpy integers keep
+    the per-element path, where encode raises the reference's TypeError."""
+    return (isinstance(a, np.ndarray) and a.dtype == object and a.size > 0
+            and all(type(v) is int or isinstance(v, (np.int16, np.int32, np.int64)) for v in a.reshape(-1)))
+
+
+def big_operand(ints: np.ndarray, ct_words: int):
+    """A flat object array of integers as a PAI_BIG operand: (magnitudes [N, xw] uint32, signs uint8 [N], wide). xw is
+    the word count of the longest magnitude, at most ct_words // 2; `wide` (None, or a bool mask) marks the values
+    beyond that width, which no key of this size encodes: their magnitude is sent as 0 and the caller gives them
+    EL_ENC_RANGE. The per-element work is numpy's object loops and ints_to_words, no Python loop."""
+    ints = _py_int(ints.reshape(-1))
+    mag = np.abs(ints)
+    neg = np.ascontiguousarray(ints < 0, dtype=np.uint8)
+    xw_max = ct_words // 2
+    bits = int(mag.max()).bit_length()
+    wide = None
+    if bits > 32 * xw_max:
+        wide = np.asarray(mag >= (1 << (32 * xw_max)), dtype=bool)
+        mag = np.where(wide, 0, mag)
+        bits = 32 * xw_max
+    return ints_to_words(mag, max(1, (bits + 31) // 32)), neg, wide
 
 
 # ---------------------------------------------------------------- key generation: the prime search on the device

@@ -41,6 +41,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
+from ._native import is_int_array
 from .encrypted_number import PaillierEncryptedNumber
 
 _CT = "_PaillierEncryptedNumber__ciphertext"
@@ -462,6 +463,11 @@ def _plain_array(y: np.ndarray):
     return None
 
 
+def _big_scalar(y) -> bool:
+    """A Python int beyond int64: a wide-integer operand (PAI_BIG), one object-array element for the device."""
+    return type(y) is int and not -(1 << 63) <= y < (1 << 63)
+
+
 def check_finite(x: np.ndarray) -> None:
     """Raise what FixedPointNumber.encode raises for the first NaN or infinity of a plain operand, in array order:
     ValueError for NaN, OverflowError for +-inf. For the calls that return no per-element status (pai_matmul) or whose
@@ -504,9 +510,7 @@ def mul_plain(a, y):
     if A is None:
         return NotImplemented
     if isinstance(y, np.ndarray):
-        if y.dtype == object:
-            return NotImplemented
-        x = _plain_array(y)
+        x = y if is_int_array(y) else (None if y.dtype == object else _plain_array(y))
         if x is None:
             return NotImplemented
         try:
@@ -518,20 +522,20 @@ def mul_plain(a, y):
             A = np.ascontiguousarray(Ab)
         xs = np.ascontiguousarray(xb).reshape(-1)
     else:
-        dt = _plain_scalar(y)
+        dt = object if _big_scalar(y) else _plain_scalar(y)
         if dt is None:
             return NotImplemented
         shape = A.shape
         xs = np.array([y], dtype=dt)
     words, exps, _ = pack(a if A is a else A, pk)
     ctx = _runtime.context(pk)
-    out, oe, st = ctx.mul(words, exps, xs)
+    out, oe, st = ctx.mul(words, exps, xs)      # (an object array of integers: pai_mul_big)
     bad = np.flatnonzero(st)
     if bad.size:
-        # a scalar the device does not encode (NaN, +-inf): the per-element operator on the first one raises the
-        # reference's exception, as numpy's object loop would at that element
+        # a scalar the device does not encode (NaN, +-inf, an integer beyond max_int): the per-element operator on the
+        # first one raises the reference's exception, as numpy's object loop would at that element
         i = int(bad[0])
-        np.asarray(A).reshape(-1)[i] * xs[i if xs.size > 1 else 0].item()
+        np.asarray(A).reshape(-1)[i] * np.asarray(xs[i if xs.size > 1 else 0]).item()
         raise ValueError(f"the scalar {xs[i if xs.size > 1 else 0]!r} at element {i} does not encode")
     # __mul__ returns fresh, not-yet-obfuscated numbers (encrypted_number.py:113)
     return materialize(pk, out, oe, shape, obfuscated=False)
@@ -594,8 +598,8 @@ _ADD_DEV = (np.dtype(np.float16), np.dtype(np.float32), np.dtype(np.float64),
 
 def _plain_operand(y) -> bool:
     if isinstance(y, np.ndarray):
-        return y.dtype in _ADD_DEV
-    return _plain_scalar(y) is not None
+        return y.dtype in _ADD_DEV or is_int_array(y)
+    return _plain_scalar(y) is not None or _big_scalar(y)
 
 
 def add_plain(a, y):
@@ -624,11 +628,11 @@ def add_plain(a, y):
         ys = yb.reshape(-1)
     else:
         shape = A.shape
-        xs = np.array([y], dtype=_plain_scalar(y))
+        xs = np.array([y], dtype=object if _big_scalar(y) else _plain_scalar(y))
         ys = None
     words, exps, _ = pack(a if A is a else A, pk)
     ctx = _runtime.context(pk)
-    out, oe, st = ctx.add_plain(words, exps, xs)
+    out, oe, st = ctx.add_plain(words, exps, xs)      # (an object array of integers: pai_add_plain_big)
     # __raw_add returns a fresh, not-yet-obfuscated number (encrypted_number.py:180-185)
     res = materialize(pk, out, oe, shape, obfuscated=False)
     bad = np.flatnonzero(st)

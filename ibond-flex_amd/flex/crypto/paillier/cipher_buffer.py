@@ -25,6 +25,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from ._native import is_int_array
 from .encrypted_number import PaillierEncryptedNumber
 
 
@@ -233,7 +234,7 @@ class CiphertextBuffer(BufferOps):
     def _coerce(self, other) -> Optional["CiphertextBuffer"]:
         if isinstance(other, CiphertextBuffer):
             b = other
-        elif isinstance(other, np.ndarray) and other.dtype == object:
+        elif isinstance(other, np.ndarray) and other.dtype == object and not is_int_array(other):
             b = CiphertextBuffer.from_array(other)
         else:
             return None
@@ -802,13 +803,15 @@ def histogram_sparse_words(pk, words, exps, indptr, indices, data, zs, node, sha
 
 
 def _plain(y, N: int) -> np.ndarray:
-    from .cipher_array import _plain_array, _plain_scalar
+    """The plain operand as the entry points take it: float32 / float64 / int64, or an object array of integers (a Python
+    int beyond int64, an object array of ints: PAI_BIG)."""
+    from .cipher_array import _big_scalar, _plain_array, _plain_scalar
     if isinstance(y, np.ndarray):
-        x = _plain_array(y.reshape(-1))
+        x = y.reshape(-1) if is_int_array(y) else _plain_array(y.reshape(-1))
         if x is None or x.size not in (1, N):
             raise TypeError(f"unsupported plain operand {y.dtype}{y.shape}")
         return x
-    dt = _plain_scalar(y)
+    dt = object if _big_scalar(y) else _plain_scalar(y)
     if dt is None:
         raise TypeError(f"unsupported plain operand {type(y)}")
     return np.array([y], dtype=dt)

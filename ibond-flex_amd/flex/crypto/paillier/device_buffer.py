@@ -196,8 +196,15 @@ def _scalar_call(name: str, pk, words: DeviceWords, exps, x: np.ndarray):
     x = np.ascontiguousarray(x)
     if x.size not in (1, N):
         raise ValueError("plain operand must have 1 or N elements")
-    dx = _native.device_upload(x, dev)
     out, oe, st = DeviceWords.empty(N, W, dev), _i32(dev, N), _i32(dev, N)
+    if x.dtype == object:                      # integers beyond int64: the PAI_BIG entry point of the same operator
+        mag, neg, wide = _native.big_operand(x, W)
+        dmag, dneg = _native.device_upload(mag, dev), _native.device_upload(neg, dev)
+        ctx.dev_call(name.replace("_dev", "_big_dev"), words.ptr, ex.ptr, N, dmag.ptr, dneg.ptr, mag.shape[1],
+                     1 if x.size == N and N > 1 else 0, out.ptr, oe.ptr, st.ptr)
+        status = st.download(np.int32, N)
+        return out, oe, status if wide is None else np.where(wide, _native.EL_ENC_RANGE, status)
+    dx = _native.device_upload(x, dev)
     ctx.dev_call(name, words.ptr, ex.ptr, N, _native.scalar_dtype(x), dx.ptr,
                  1 if x.size == N and N > 1 else 0, out.ptr, oe.ptr, st.ptr)
     return out, oe, st.download(np.int32, N)
@@ -486,6 +493,28 @@ def encrypt_dev(pk, x: np.ndarray, exp_mode: int, fixed_exp: int):
     return out, oe, st.download(np.int32, N)
 
 
+def encrypt_big_dev(pk, ints: np.ndarray):
+    """pai_encrypt_big_dev of a flat object array of integers, obfuscated like encrypt_dev: (words, exponents, statuses
+    on the host). Only the magnitudes and signs go up."""
+    from . import _runtime, obfuscator_pool
+    need_gpu()
+    ctx = _runtime.context(pk)
+    dev, W, N = ctx.device, ctx.ct_words, ints.size
+    mag, neg, wide = _native.big_operand(ints, W)
+    dmag, dneg = _native.device_upload(mag, dev), _native.device_upload(neg, dev)
+    out, oe, st = DeviceWords.empty(N, W, dev), _i32(dev, N), _i32(dev, N)
+    with obfuscator_pool.lock:
+        pooled = obfuscator_pool.device_pool(pk, N)
+        if pooled is not None:
+            pooled.dev_call("pai_encrypt_big_dev", dmag.ptr, dneg.ptr, mag.shape[1], N, _native.PAI_OBF_POOL, None, 0, 0,
+                            bytes(32), 0, out.ptr, oe.ptr, st.ptr)
+    if pooled is None:
+        ctx.dev_call("pai_encrypt_big_dev", dmag.ptr, dneg.ptr, mag.shape[1], N, _native.PAI_OBF_RNG, None, 0, 0,
+                     os.urandom(32), 0, out.ptr, oe.ptr, st.ptr)
+    status = st.download(np.int32, N)
+    return out, oe, status if wide is None else np.where(wide, _native.EL_ENC_RANGE, status)
+
+
 # ---------------------------------------------------------------------- the buffer
 class DeviceCiphertextBuffer(BufferOps):
     """public_key, shape, size and obfuscated (a host uint8 array) as in CiphertextBuffer; the words (`words`, a
@@ -600,7 +629,7 @@ class DeviceCiphertextBuffer(BufferOps):
         return DeviceCiphertextBuffer(self.public_key, words, exps, obfuscated, shape or self.shape)
 
     def _coerce(self, other) -> Optional["DeviceCiphertextBuffer"]:
-        if isinstance(other, np.ndarray) and other.dtype == object:
+        if isinstance(other, np.ndarray) and other.dtype == object and not _native.is_int_array(other):
             other = CiphertextBuffer.from_array(other)
         if not isinstance(other, (CiphertextBuffer, DeviceCiphertextBuffer)):
             return None

@@ -35,10 +35,19 @@ def _device_input(flat: np.ndarray):
             return np.array(vals, dtype=np.float64), None
         if all(isinstance(v, (np.float32, np.float16)) for v in vals):
             return np.array(vals, dtype=np.float32), None
-        if all((type(v) is int and -(1 << 63) <= v < (1 << 63)) or isinstance(v, _INT_DT) for v in vals):
-            return np.array(vals, dtype=np.int64), None
+        if all(type(v) is int or isinstance(v, _INT_DT) for v in vals):
+            if all(-(1 << 63) <= v < (1 << 63) for v in vals):
+                return np.array(vals, dtype=np.int64), None
+            return None, "wide"              # integers, some beyond int64: a PAI_BIG input (_encrypt_big)
         return None, "mixed"
     return None, type(flat.reshape(-1)[0]) if flat.size else dt.type
+
+
+def _big_input(bad, precision) -> bool:
+    """_device_input found integers beyond int64 (`bad` is "wide"): one pai_encrypt_big call serves them when there is no
+    precision (an int then encodes at exponent 0) and a GPU."""
+    from . import _runtime
+    return bad == "wide" and precision is None and _runtime.gpu_available()
 
 
 class PaillierEncryptor(object):
@@ -71,7 +80,8 @@ class PaillierEncryptor(object):
         # without a GPU, obfuscators prepared ahead of time that cover the array serve it element by element
         host_pool = (x is not None and random_value is None
                      and obfuscator_pool.obfuscators_ready(self.pub_key) >= flat.size and not _runtime.gpu_available())
-        if x is None or host_pool:
+        big = _big_input(bad, precision)
+        if (x is None and not big) or host_pool:
             # mixed object arrays and non-numeric dtypes: per-element semantics of the reference
             # (raises the same TypeError for unsupported element types)
             el = [self._encrypt(v, precision, random_value) for v in flat]
@@ -82,7 +92,9 @@ class PaillierEncryptor(object):
         if precision is not None:
             exp_mode, fixed_exp = _native.PAI_EXP_FIXED, math.floor(math.log(precision, FixedPointNumber.BASE))
         ctx = _runtime.context(self.pub_key)
-        if random_value is None:
+        if big:                              # integers beyond int64: ONE pai_encrypt_big call
+            ct, ex, st, obfuscated = self._encrypt_big(flat, random_value)
+        elif random_value is None:
             with obfuscator_pool.lock:       # obfuscators prepared ahead of time, when they cover the whole array
                 pooled = obfuscator_pool.device_pool(self.pub_key, x.size)
                 if pooled is not None:
@@ -108,6 +120,27 @@ class PaillierEncryptor(object):
             out = PaillierArray(objs.reshape(s))
         return out
 
+    def _encrypt_big(self, flat: np.ndarray, random_value: int = None):
+        """ONE pai_encrypt_big call over an object array of integers: (words, exponents, statuses, obfuscated), with
+        _encrypt_numpy's choice of obfuscator (pooled, device CSPRNG, the caller's r, none)."""
+        from . import _native, _runtime, obfuscator_pool
+        ctx = _runtime.context(self.pub_key)
+        x, neg, wide = _native.big_operand(flat, ctx.ct_words)
+        if random_value is None:
+            with obfuscator_pool.lock:
+                pooled = obfuscator_pool.device_pool(self.pub_key, flat.size)
+                if pooled is not None:
+                    ct, ex, st = pooled.encrypt_big(x, neg, _native.PAI_OBF_POOL)
+            if pooled is None:
+                ct, ex, st = ctx.encrypt_big(x, neg, _native.PAI_OBF_RNG)
+        elif random_value:
+            ct, ex, st = ctx.encrypt_big(x, neg, _native.PAI_OBF_GIVEN, r_scalar=int(random_value) % self.pub_key.nsquare)
+        else:
+            ct, ex, st = ctx.encrypt_big(x, neg, _native.PAI_OBF_NONE)
+        if wide is not None:
+            st = np.where(wide, _native.EL_ENC_RANGE, st)
+        return ct, ex, st, random_value is None
+
     def encrypt_to_buffer(self, values: np.ndarray, precision: int = None, device: bool = False):
         """Encrypt an array into a CiphertextBuffer (cipher_buffer.py): the device words, exponents and
         obfuscation flags, no PaillierEncryptedNumber per element. Same ciphertext distribution as
@@ -118,28 +151,33 @@ class PaillierEncryptor(object):
         from .cipher_buffer import CiphertextBuffer
         values = np.asarray(values)
         s = values.shape
-        x, _ = _device_input(values.reshape(-1))
-        if x is None:
+        x, bad = _device_input(values.reshape(-1))
+        big = values.reshape(-1) if _big_input(bad, precision) else None
+        if x is None and big is None:
             raise TypeError(f"encrypt_to_buffer: unsupported input dtype {values.dtype}")
         exp_mode, fixed_exp = _native.PAI_EXP_AUTO, 0
         if precision is not None:
             exp_mode, fixed_exp = _native.PAI_EXP_FIXED, math.floor(math.log(precision, FixedPointNumber.BASE))
         if device:
-            from .device_buffer import DeviceCiphertextBuffer, encrypt_dev
-            words, ex, st = encrypt_dev(self.pub_key, x, exp_mode, fixed_exp)
+            from .device_buffer import DeviceCiphertextBuffer, encrypt_big_dev, encrypt_dev
+            words, ex, st = (encrypt_big_dev(self.pub_key, big) if big is not None else
+                             encrypt_dev(self.pub_key, x, exp_mode, fixed_exp))
             for i in np.nonzero(st != _native.EL_OK)[0].tolist():
                 # beyond the device's 64-bit fixed-point range: the host encoder (raises like the reference)
                 e = self._encrypt(values.reshape(-1)[i], precision)
                 words.mem.upload(_runtime.ints_to_words([e.ciphertext(False)], words.shape[1])[0], i * words.shape[1] * 4)
                 ex.upload(np.array([e.exponent], dtype=np.int32), i * 4)
             return DeviceCiphertextBuffer(self.pub_key, words, ex, 1, s)
-        ctx = _runtime.context(self.pub_key)
-        with obfuscator_pool.lock:           # obfuscators prepared ahead of time, when they cover the whole array
-            pooled = obfuscator_pool.device_pool(self.pub_key, x.size)
-            if pooled is not None:
-                ct, ex, st = pooled.encrypt(x, exp_mode, fixed_exp, _native.PAI_OBF_POOL)
-        if pooled is None:
-            ct, ex, st = ctx.encrypt(x, exp_mode, fixed_exp, _native.PAI_OBF_RNG)
+        if big is not None:
+            ct, ex, st, _ = self._encrypt_big(big)
+        else:
+            ctx = _runtime.context(self.pub_key)
+            with obfuscator_pool.lock:       # obfuscators prepared ahead of time, when they cover the whole array
+                pooled = obfuscator_pool.device_pool(self.pub_key, x.size)
+                if pooled is not None:
+                    ct, ex, st = pooled.encrypt(x, exp_mode, fixed_exp, _native.PAI_OBF_POOL)
+            if pooled is None:
+                ct, ex, st = ctx.encrypt(x, exp_mode, fixed_exp, _native.PAI_OBF_RNG)
         bad_idx = np.nonzero(st != _native.EL_OK)[0]
         if bad_idx.size:
             # beyond the device's 64-bit fixed-point range: the host encoder (raises like the reference)

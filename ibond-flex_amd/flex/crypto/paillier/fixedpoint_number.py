@@ -53,7 +53,9 @@ class FixedPointNumber(object):
         """fixedpoint_number.py:46-90"""
         if isinstance(scalar, (np.unsignedinteger, np.bool_)):
             raise TypeError("Don't know the precision of type %s." % type(scalar))
-        if abs(float(scalar)) < 1e-200:
+        # (a Python int compares exactly, of any width, like the reference's np.abs(scalar): float() of one beyond
+        # 2^1024 would raise an OverflowError the reference does not)
+        if abs(scalar if isinstance(scalar, int) else float(scalar)) < 1e-200:
             scalar = 0
         if n is None:
             n = cls.Q

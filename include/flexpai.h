@@ -91,6 +91,12 @@ typedef struct pai_comm pai_comm;
 #define PAI_F32 0
 #define PAI_F64 1
 #define PAI_I64 2
+/* A wide integer (a Python int beyond 64 bits) as the pai_*_big entry points take it: element i is the magnitude
+ * x[i * xw .. i * xw + xw), xw little-endian 32-bit words with one xw for the call (1 <= xw <= ct_words / 2), and the
+ * sign neg[i] (uint8, 1: negative; a null neg means no element is negative). It is an integer, so it encodes at
+ * exponent 0 like FixedPointNumber.encode of an int. Not a dtype of pai_encrypt, pai_mul, pai_add_plain, pai_matmul,
+ * pai_segment_dot or the packed entry points, which keep PAI_F32 / PAI_F64 / PAI_I64. */
+#define PAI_BIG 3
 
 /* obfuscation modes (SURVEY.md §8b randomness contract) */
 #define PAI_OBF_NONE 0   /* random_value == 0 : c = 1 + n*m                      (encryptor.py:61-67) */
@@ -359,6 +365,24 @@ int pai_mul(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int 
  * Python ints), so int64 * 16^E never wraps. */
 int pai_add_plain(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int dtype, const void* x,
                   size_t x_stride, uint32_t* ct_out, int32_t* exp_out, int32_t* status_out);
+/* PAI_BIG operands (above). status_out (nullable) is PAI_EL_ENC_RANGE exactly where the reference's encode raises
+ * ValueError: |v| > max_int = n // 3 - 1, compared limb for limb on the device (for pai_add_plain_big: |v| 16^E with
+ * E = max(exp_i, 0), the encode with max_exponent = exp_i). Such an element is encrypted as 0, multiplied by 1 or added
+ * as 0, and the caller redoes it. A value that fits int64 gives the bits of the PAI_I64 call with the same r.
+ *   pai_encrypt_big     c = (1 + n M) r^n mod n^2, M = v mod n, exponent 0. obf_mode, r_le, rng_key32 and index_base as
+ *                       for pai_encrypt, PAI_OBF_POOL included; r^n comes by the route pai_obfuscate takes for these N
+ *                       elements (csrc/encrypt_route.hpp) and is multiplied in by the same kernel.
+ *   pai_mul_big         ct_i^|k| mod n^2 for |k| of up to nb - 2 bits, inverted where k < 0 (one batch inversion, as
+ *                       pai_mul); exponent exp_i. x_stride 0: one scalar for all elements, 1: one per element.
+ *   pai_add_plain_big   ct_i (+) v, exponent max(exp_i, 0); x_stride as above. */
+int pai_encrypt_big(pai_ctx* ctx, const uint32_t* x, const uint8_t* neg, size_t xw, size_t N, int obf_mode,
+                    const uint8_t* r_le, size_t r_stride_bytes, size_t r_bytes, const uint8_t* rng_key32,
+                    uint64_t index_base, uint32_t* ct_out, int32_t* exp_out, int32_t* status_out);
+int pai_mul_big(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, const uint32_t* x, const uint8_t* neg,
+                size_t xw, size_t x_stride, uint32_t* ct_out, int32_t* exp_out, int32_t* status_out);
+int pai_add_plain_big(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, const uint32_t* x,
+                      const uint8_t* neg, size_t xw, size_t x_stride, uint32_t* ct_out, int32_t* exp_out,
+                      int32_t* status_out);
 /* Segmented k-way add: out_s = prod over t in [seg_off[s], seg_off[s+1]) of ct[index[t]] aligned to the
  * segment's maximum exponent (same as pai_add over the members). index and seg_off (nseg + 1 offsets,
  * seg_off[0] = 0, non-decreasing) are host arrays in both variants. An empty segment yields ciphertext 1
@@ -523,6 +547,17 @@ int pai_mul_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t
 int pai_add_plain_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int dtype,
                       const void* d_x, size_t x_stride, uint32_t* d_out, int32_t* d_exp_out, int32_t* d_status,
                       void* stream);
+/* The PAI_BIG entry points on device buffers (d_x, d_neg device memory; r as for pai_encrypt_dev). pai_mul_big_dev
+ * synchronises `stream` once, like pai_mul_dev; the others are as asynchronous as pai_obfuscate_dev and pai_add_dev. */
+int pai_encrypt_big_dev(pai_ctx* ctx, const uint32_t* d_x, const uint8_t* d_neg, size_t xw, size_t N, int obf_mode,
+                        const uint32_t* d_r_words, size_t r_stride_words, size_t r_words, const uint8_t* rng_key32,
+                        uint64_t index_base, uint32_t* d_ct, int32_t* d_exp, int32_t* d_status, void* stream);
+int pai_mul_big_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const uint32_t* d_x,
+                    const uint8_t* d_neg, size_t xw, size_t x_stride, uint32_t* d_out, int32_t* d_exp_out,
+                    int32_t* d_status, void* stream);
+int pai_add_plain_big_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const uint32_t* d_x,
+                          const uint8_t* d_neg, size_t xw, size_t x_stride, uint32_t* d_out, int32_t* d_exp_out,
+                          int32_t* d_status, void* stream);
 int pai_segment_add_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* index,
                         const int64_t* seg_off, size_t nseg, uint32_t* d_out, int32_t* d_exp_out, void* stream);
 int pai_matmul_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t m, size_t K, int dtype,
