@@ -52,6 +52,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_sgs.hpp"
 #include "engine_grp.hpp"
 #include "engine_mul.hpp"
+#include "engine_inv.hpp"
 #include "engine_big.hpp"
 #include "engine_mm.hpp"
 #include "engine_sd.hpp"
@@ -153,6 +154,8 @@ struct pai_ctx {
   HBig n, N;
   uint32_t mprime_N = 0;
   uint32_t *d_N = nullptr, *d_R2 = nullptr, *d_nl = nullptr;
+  uint32_t *d_N2w = nullptr, *d_nw = nullptr;   // n^2 (ct_words) and n (pt_words) as 32-bit words: k_modinv's moduli
+  bool inv_device = true;   // PAI_OPT_INV_DEVICE
   uint32_t* d_pew_prog = nullptr;   // op list over n for k_pe_w (public-key encryption on 16-lane rows)
   int pew_nprog = 0;
   uint32_t* d_prog = nullptr;   // Montgomery program for x^n (run_program, kernels.hpp)
@@ -351,14 +354,6 @@ struct pai_ctx {
   void* d_inv = nullptr;        // batch-inversion prefix products and segment products
   size_t inv_bytes = 0;
   std::vector<uint32_t> inv_host;   // top of the inversion tree (host side of an async copy)
-  // the public-key chain's inversion without a host wait (batch_invert_async): the top value goes device -> pinned
-  // words, a host function in stream order inverts it mod n there, and the result (+ a no-inverse flag) goes back
-  struct AsyncInv {
-    HBig mod;
-    int W = 0;
-    uint32_t* pin = nullptr;     // [W] words of the top value, then its inverse; [W]: 1 = no inverse exists
-  };
-  AsyncInv* inv_async = nullptr;
   int cus = 0;
   // optional per-stage timing of the last encrypt call (PAI_OPT_STAGE_TIMING)
   bool timing = false;
@@ -450,10 +445,6 @@ pai_ctx::~pai_ctx() {
   if (d_shisterr) (void)hipFree(d_shisterr);
   if (d_scan) (void)hipFree(d_scan);
   if (d_inv) (void)hipFree(d_inv);
-  if (inv_async) {
-    if (inv_async->pin) (void)hipHostFree(inv_async->pin);
-    delete inv_async;
-  }
   if (d_plain) (void)hipFree(d_plain);
   if (d_obf) (void)hipFree(d_obf);
   if (d_pack) (void)hipFree(d_pack);
@@ -965,7 +956,9 @@ int pai_ctx_create(const uint8_t* n_le, size_t n_bytes, int device, pai_ctx** ou
   if ((rc = upload(c, rs, &c->d_RS)) || (rc = upload(c, c->N.limbs(c->S_e, LB), &c->d_N)) ||
       (rc = upload(c, R2.limbs(c->S_e, LB), &c->d_R2)) ||
       (rc = upload(c, n.limbs(c->S_e, LB), &c->d_nl)) || (rc = upload(c, prog, &c->d_prog)) ||
-      (rc = upload(c, oneR.limbs(c->S_e, LB), &c->d_oneR)) || (rc = (SetupTrace("  setup_pe"), setup_pe(c, n))) ||
+      (rc = upload(c, oneR.limbs(c->S_e, LB), &c->d_oneR)) ||
+      (rc = upload(c, c->N.words(c->ct_words), &c->d_N2w)) || (rc = upload(c, n.words(c->pt_words), &c->d_nw)) ||
+      (rc = (SetupTrace("  setup_pe"), setup_pe(c, n))) ||
       (rc = setup_pe1(c, n)) || (rc = setup_pe4(c, n))) {
     delete c;
     return rc;
@@ -2295,6 +2288,7 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       c->crt4_min = value;
       return 0;
     case PAI_OPT_MATMUL_FUSED: c->mm_fused = value != 0; return 0;
+    case PAI_OPT_INV_DEVICE: c->inv_device = value != 0; return 0;
     case PAI_OPT_SEGDOT_FUSED: c->sd_fused = value != 0; return 0;
     case PAI_OPT_POOL_FUSED: c->pool.fused = value != 0; return 0;
     case PAI_OPT_SCAN_TILE:
@@ -2342,6 +2336,7 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_ROWS_MAX: *value = (int)std::min<long long>(c->crtw_max, INT32_MAX); return 0;
     case PAI_OPT_CRT4_MIN: *value = (int)std::min<long long>(c->crt4_min, INT32_MAX); return 0;
     case PAI_OPT_MATMUL_FUSED: *value = c->mm_fused ? 1 : 0; return 0;
+    case PAI_OPT_INV_DEVICE: *value = c->inv_device ? 1 : 0; return 0;
     case PAI_OPT_MATMUL_PATH: *value = c->mm_path; return 0;
     case PAI_OPT_SEGDOT_FUSED: *value = c->sd_fused ? 1 : 0; return 0;
     case PAI_OPT_SEGDOT_PATH: *value = c->sd_path; return 0;
@@ -3032,7 +3027,11 @@ struct InvMod {
   const uint32_t *N, *R2, *oneR;
   uint32_t mprime;
   const HBig* mod;
+  const uint32_t* Nw;        // the modulus as W 32-bit words on the device (k_modinv)
 };
+static InvMod inv_mod_n2(const pai_ctx* c) {
+  return InvMod{c->tpi_e, c->ct_words, c->S_e, c->d_N, c->d_R2, c->d_oneR, c->mprime_N, &c->N, c->d_N2w};
+}
 static int batch_invert(pai_ctx* c, uint32_t* x, const uint8_t* flag, long long n, hipStream_t st, const InvMod& md);
 static int batch_invert(pai_ctx* c, uint32_t* x, const uint8_t* flag, long long n, hipStream_t st);
 static int batch_invert_async(pai_ctx* c, uint32_t* x, long long n, hipStream_t st, const InvMod& md, uint32_t** d_noinv);
@@ -3116,7 +3115,7 @@ static int launch_pe(pai_ctx* c, const EncParams& e, hipStream_t st) {
     HIPCHK(pe_launch_pre_aw(p, g, st, ev));
     uint32_t* noinv = nullptr;
     rc = batch_invert_async(c, p.aw, n, st,
-                            InvMod{2, c->pt_words, 2 * L, c->d_pe_n, c->d_pe_r2, c->d_pe_oneR, c->pe_mprime, &c->n}, &noinv);
+                            InvMod{2, c->pt_words, 2 * L, c->d_pe_n, c->d_pe_r2, c->d_pe_oneR, c->pe_mprime, &c->n, c->d_nw}, &noinv);
     if (rc) return rc;
     // an A_r that shares a factor with n (no inverse): the device flag sends this chunk down the general chain
     p.noinv = noinv;
@@ -4217,53 +4216,106 @@ static int inv_grid(pai_ctx* c, int tpi, long long nseg) {
   return (int)std::max<long long>(1, std::min<long long>((nseg + gpb - 1) / gpb, (long long)occ * c->cus));
 }
 
-// Batch inversion (Montgomery's trick, kernels_mul.hpp) of the flagged values of x [n][W] in place,
-// on `st`. Segment products are reduced level by level to ONE value, inverted on the host (the only
-// modular inversion mod n^2; gmpy_math.invert, gmpy_math.py:66-74), and expanded back down. The
-// host step synchronises `st` once. Not invertible -> PAI_ERR_NOINV ("no inverse exists").
-static int batch_invert(pai_ctx* c, uint32_t* x, const uint8_t* flag, long long n, hipStream_t st) {
-  return batch_invert(c, x, flag, n, st, InvMod{c->tpi_e, c->ct_words, c->S_e, c->d_N, c->d_R2, c->d_oneR, c->mprime_N, &c->N});
-}
-static int batch_invert(pai_ctx* c, uint32_t* x, const uint8_t* flag, long long n, hipStream_t st, const InvMod& md) {
-  const int S = md.S, W = md.W;
+// Batch inversion (Montgomery's trick, kernels_mul.hpp) of the flagged values of x [n][W] in place, on `st`. Segment
+// products are reduced level by level to at most INV_TOPS values, which k_modinv (kernels_inv.hpp) inverts, one wave
+// each, and expanded back down. A value without inverse sets the status word: the down-sweep is gated on it and writes
+// nothing, and the call returns PAI_ERR_NOINV ("no inverse exists") after reading the word back -- its one
+// synchronisation, at the end. With PAI_OPT_INV_DEVICE = 0 (or a modulus above MODINV_MAX_WORDS words) the levels go
+// down to ONE value, which is copied to the host and inverted there (gmpy_math.invert, gmpy_math.py:66-74), as before
+// k_modinv: kept for comparison.
+struct InvPlan {
+  std::vector<long long> ns;
+  std::vector<int> seg;
+  std::vector<size_t> pre_off, seg_off;
+  size_t flag_off = 0, bytes = 0;
+  int levels = 0;
+};
+static InvPlan inv_plan(long long n, int S, int W, long long tops) {
   // segment length per level: INV_SEG where there are values enough to fill the chip with segments, down to 4 on the
   // upper levels, whose few groups would otherwise walk chains of 64 dependent products (round 5: the 1M-value
   // inversion's levels above the first took ~22 of its 37 ms as 64-long chains over 16 k, 256 and 4 values)
-  std::vector<long long> ns{n};
-  std::vector<int> seg;
+  InvPlan pl;
+  pl.ns.push_back(n);
   do {
-    seg.push_back((int)std::max<long long>(4, std::min<long long>(INV_SEG, ns.back() / 4096)));
-    ns.push_back((ns.back() + seg.back() - 1) / seg.back());
-  } while (ns.back() > 1);
-  const int levels = (int)ns.size() - 1;
-  std::vector<size_t> pre_off(levels), seg_off(levels);
+    pl.seg.push_back((int)std::max<long long>(4, std::min<long long>(INV_SEG, pl.ns.back() / 4096)));
+    pl.ns.push_back((pl.ns.back() + pl.seg.back() - 1) / pl.seg.back());
+  } while (pl.ns.back() > tops);
+  pl.levels = (int)pl.ns.size() - 1;
+  pl.pre_off.resize(pl.levels);
+  pl.seg_off.resize(pl.levels);
   size_t off = 0;
-  for (int l = 0; l < levels; ++l) {
-    pre_off[l] = off;
-    off = align16(off + (size_t)ns[l] * S * 4);
-    seg_off[l] = off;
-    off = align16(off + (size_t)ns[l + 1] * W * 4);
+  for (int l = 0; l < pl.levels; ++l) {
+    pl.pre_off[l] = off;
+    off = align16(off + (size_t)pl.ns[l] * S * 4);
+    pl.seg_off[l] = off;
+    off = align16(off + (size_t)pl.ns[l + 1] * W * 4);
   }
-  int rc = ensure_buf(&c->d_inv, &c->inv_bytes, off);
+  pl.flag_off = off;
+  pl.bytes = off + 16;
+  return pl;
+}
+static InvParams inv_params(const InvPlan& pl, int l, char* base, uint32_t* x, const uint8_t* flag, const InvMod& md,
+                            const uint32_t* gate) {
+  InvParams p{};
+  p.x = l == 0 ? x : (uint32_t*)(base + pl.seg_off[l - 1]);
+  p.flag = l == 0 ? flag : nullptr;
+  p.n = pl.ns[l];
+  p.pre = (uint32_t*)(base + pl.pre_off[l]);
+  p.seg = (uint32_t*)(base + pl.seg_off[l]);
+  p.N = md.N;
+  p.R2 = md.R2;
+  p.oneR = md.oneR;
+  p.mprime = md.mprime;
+  p.ct_words = md.W;
+  p.seg_len = pl.seg[l];
+  p.gate = gate;
+  return p;
+}
+// up-sweep, k_modinv on the tops, gated down-sweep: no host step, no allocation beyond the context's inversion buffer
+static int batch_invert_dev(pai_ctx* c, uint32_t* x, const uint8_t* flag, long long n, hipStream_t st, const InvMod& md,
+                            uint32_t** d_noinv) {
+  const InvPlan pl = inv_plan(n, md.S, md.W, INV_TOPS);
+  int rc = ensure_buf(&c->d_inv, &c->inv_bytes, pl.bytes);
   if (rc) return rc;
   char* base = (char*)c->d_inv;
-  auto params = [&](int l) {
-    InvParams p{};
-    p.x = l == 0 ? x : (uint32_t*)(base + seg_off[l - 1]);
-    p.flag = l == 0 ? flag : nullptr;
-    p.n = ns[l];
-    p.pre = (uint32_t*)(base + pre_off[l]);
-    p.seg = (uint32_t*)(base + seg_off[l]);
-    p.N = md.N;
-    p.R2 = md.R2;
-    p.oneR = md.oneR;
-    p.mprime = md.mprime;
-    p.ct_words = W;
-    p.seg_len = seg[l];
-    return p;
-  };
-  for (int l = 0; l < levels; ++l) HIPCHK(inv_launch(md.tpi, true, params(l), inv_grid(c, md.tpi, ns[l + 1]), st));
-  uint32_t* top = (uint32_t*)(base + seg_off[levels - 1]);
+  uint32_t* word = (uint32_t*)(base + pl.flag_off);
+  for (int l = 0; l < pl.levels; ++l)
+    HIPCHK(inv_launch(md.tpi, true, inv_params(pl, l, base, x, flag, md, word), inv_grid(c, md.tpi, pl.ns[l + 1]), st));
+  ModinvParams mp{};
+  mp.x = mp.out = (uint32_t*)(base + pl.seg_off[pl.levels - 1]);
+  mp.m = md.Nw;
+  mp.any_noinv = word;
+  mp.W = md.W;
+  mp.rounds = modinv_rounds((int)md.mod->bits());
+  mp.ninv31 = modinv_neg_minv31(md.mod->w[0]);
+  HIPCHK(modinv_launch(mp, (int)pl.ns[pl.levels], st));
+  for (int l = pl.levels - 1; l >= 0; --l)
+    HIPCHK(inv_launch(md.tpi, false, inv_params(pl, l, base, x, flag, md, word), inv_grid(c, md.tpi, pl.ns[l + 1]), st));
+  *d_noinv = word;
+  return 0;
+}
+static int batch_invert(pai_ctx* c, uint32_t* x, const uint8_t* flag, long long n, hipStream_t st) {
+  return batch_invert(c, x, flag, n, st, inv_mod_n2(c));
+}
+static int batch_invert(pai_ctx* c, uint32_t* x, const uint8_t* flag, long long n, hipStream_t st, const InvMod& md) {
+  const int W = md.W;
+  if (c->inv_device && W <= MODINV_MAX_WORDS) {
+    uint32_t* word = nullptr;
+    int rc = batch_invert_dev(c, x, flag, n, st, md, &word);
+    if (rc) return rc;
+    c->inv_host.assign(1, 0);
+    HIPCHK(hipMemcpyAsync(c->inv_host.data(), word, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (c->inv_host[0]) return fail(PAI_ERR_NOINV, "invert() no inverse exists");
+    return 0;
+  }
+  const InvPlan pl = inv_plan(n, md.S, W, 1);
+  int rc = ensure_buf(&c->d_inv, &c->inv_bytes, pl.bytes);
+  if (rc) return rc;
+  char* base = (char*)c->d_inv;
+  for (int l = 0; l < pl.levels; ++l)
+    HIPCHK(inv_launch(md.tpi, true, inv_params(pl, l, base, x, flag, md, nullptr), inv_grid(c, md.tpi, pl.ns[l + 1]), st));
+  uint32_t* top = (uint32_t*)(base + pl.seg_off[pl.levels - 1]);
   c->inv_host.assign(W, 0);
   HIPCHK(hipMemcpyAsync(c->inv_host.data(), top, (size_t)W * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -4274,95 +4326,18 @@ static int batch_invert(pai_ctx* c, uint32_t* x, const uint8_t* flag, long long 
   if (inv.is_zero()) return fail(PAI_ERR_NOINV, "invert() no inverse exists");
   c->inv_host = inv.words(W);
   HIPCHK(hipMemcpyAsync(top, c->inv_host.data(), (size_t)W * 4, hipMemcpyHostToDevice, st));
-  for (int l = levels - 1; l >= 0; --l) HIPCHK(inv_launch(md.tpi, false, params(l), inv_grid(c, md.tpi, ns[l + 1]), st));
+  for (int l = pl.levels - 1; l >= 0; --l)
+    HIPCHK(inv_launch(md.tpi, false, inv_params(pl, l, base, x, flag, md, nullptr), inv_grid(c, md.tpi, pl.ns[l + 1]), st));
   return 0;
 }
 
-// The public-key encryption's batch inversion (launch_pe) without blocking the caller: batch_invert's levels, but the top
-// value is inverted by a host function queued on `st` (hipLaunchHostFunc: it runs when the stream reaches it, on the
-// runtime's thread, touching only the pinned words) instead of after a hipStreamSynchronize, so pai_encrypt_dev stays
-// asynchronous and capturable. An A_r that shares a factor with n (no inverse, probability ~2^-1023 for
-// random r; r = 0, n, 5p given explicitly) sets *d_noinv = 1, and the kernels choose the chain on the device:
-// k_pe_iota / k_pe_pow_f exit, the general k_pe_pow runs (kernels_pe.hpp, PeParams::noinv).
-static void inv_top_host(void* u) {
-  auto* a = (pai_ctx::AsyncInv*)u;
-  try {
-    HBig v;
-    v.w.assign(a->pin, a->pin + a->W);
-    v.trim();
-    const HBig inv = inv_mod(v, a->mod);
-    if (inv.is_zero()) {
-      a->pin[a->W] = 1u;
-      return;
-    }
-    const std::vector<uint32_t> w = inv.words(a->W);
-    std::memcpy(a->pin, w.data(), (size_t)a->W * 4);
-    a->pin[a->W] = 0u;
-  } catch (...) {
-    a->pin[a->W] = 1u;   // the general chain, same ciphertexts
-  }
-}
-
+// The public-key encryption's batch inversion (launch_pe) and pai_neg_dev's, without a host step: kernels on `st` only,
+// whatever PAI_OPT_INV_DEVICE says. An A_r that shares a factor with n (no inverse, probability ~2^-1023 for random r;
+// r = 0, n, 5p given explicitly) sets *d_noinv = 1, and the kernels choose the chain on the device: k_pe_iota /
+// k_pe_pow_f exit, the general k_pe_pow runs (kernels_pe.hpp, PeParams::noinv).
 static int batch_invert_async(pai_ctx* c, uint32_t* x, long long n, hipStream_t st, const InvMod& md, uint32_t** d_noinv) {
-  const int S = md.S, W = md.W;
-  std::vector<long long> ns{n};
-  std::vector<int> seg;
-  do {
-    seg.push_back((int)std::max<long long>(4, std::min<long long>(INV_SEG, ns.back() / 4096)));
-    ns.push_back((ns.back() + seg.back() - 1) / seg.back());
-  } while (ns.back() > 1);
-  const int levels = (int)ns.size() - 1;
-  std::vector<size_t> pre_off(levels), seg_off(levels);
-  size_t off = 0;
-  for (int l = 0; l < levels; ++l) {
-    pre_off[l] = off;
-    off = align16(off + (size_t)ns[l] * S * 4);
-    seg_off[l] = off;
-    off = align16(off + (size_t)ns[l + 1] * W * 4);
-  }
-  const size_t flag_off = off;
-  off += 16;
-  int rc = ensure_buf(&c->d_inv, &c->inv_bytes, off);
-  if (rc) return rc;
-  if (!c->inv_async || c->inv_async->W != W || !(c->inv_async->mod.w == md.mod->w)) {
-    if (!c->inv_async) c->inv_async = new pai_ctx::AsyncInv;
-    if (c->inv_async->pin && c->inv_async->W < W) {
-      HIPCHK(hipStreamSynchronize(st));   // (once per context: a previous call's host function may still read it)
-      (void)hipHostFree(c->inv_async->pin);
-      c->inv_async->pin = nullptr;
-    }
-    if (!c->inv_async->pin) HIPCHK(hipHostMalloc((void**)&c->inv_async->pin, (size_t)(W + 4) * 4, hipHostMallocDefault));
-    c->inv_async->W = W;
-    c->inv_async->mod = *md.mod;
-  }
-  char* base = (char*)c->d_inv;
-  auto params = [&](int l) {
-    InvParams p{};
-    p.x = l == 0 ? x : (uint32_t*)(base + seg_off[l - 1]);
-    p.flag = nullptr;
-    p.n = ns[l];
-    p.pre = (uint32_t*)(base + pre_off[l]);
-    p.seg = (uint32_t*)(base + seg_off[l]);
-    p.N = md.N;
-    p.R2 = md.R2;
-    p.oneR = md.oneR;
-    p.mprime = md.mprime;
-    p.ct_words = W;
-    p.seg_len = seg[l];
-    return p;
-  };
-  for (int l = 0; l < levels; ++l) HIPCHK(inv_launch(md.tpi, true, params(l), inv_grid(c, md.tpi, ns[l + 1]), st));
-  uint32_t* top = (uint32_t*)(base + seg_off[levels - 1]);
-  uint32_t* flag = (uint32_t*)(base + flag_off);
-  uint32_t* pin = c->inv_async->pin;
-  HIPCHK(hipMemcpyAsync(pin, top, (size_t)W * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipLaunchHostFunc(st, inv_top_host, c->inv_async));
-  HIPCHK(hipMemcpyAsync(top, pin, (size_t)W * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(flag, pin + W, 4, hipMemcpyHostToDevice, st));
-  // (with no inverse the words copied back are the top value itself: the levels below produce values nobody reads)
-  for (int l = levels - 1; l >= 0; --l) HIPCHK(inv_launch(md.tpi, false, params(l), inv_grid(c, md.tpi, ns[l + 1]), st));
-  *d_noinv = flag;
-  return 0;
+  if (md.W > MODINV_MAX_WORDS) return fail(PAI_ERR_KEY, "batch inversion on the device: modulus above 8192 bits");
+  return batch_invert_dev(c, x, nullptr, n, st, md, d_noinv);
 }
 
 // k_mul over n terms (p: index maps, scalars; outputs set by the caller)
@@ -4433,6 +4408,30 @@ int pai_mul_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N
   p.neg = (uint8_t*)c->d_mul;
   if ((rc = launch_mul(c, p, st))) return rc;
   return batch_invert(c, d_out, (const uint8_t*)c->d_mul, (long long)N, st);
+}
+
+// Homomorphic negation: out_i = ct_i^-1 mod n^2, pai_mul by the integer -1 bit for bit (k_mul's factor for the scalar
+// -1 is the ciphertext itself, flagged for the inversion), as one batch inversion with no host step.
+int pai_neg_dev(pai_ctx* c, const uint32_t* d_ct, size_t N, uint32_t* d_out, uint32_t* d_status, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  const size_t W = c->ct_words;
+  if (!d_status || (N && (!d_ct || !d_out))) return fail(PAI_ERR_ARG, "pai_neg_dev: bad arguments");
+  if (N && d_out != d_ct && d_out < d_ct + N * W && d_ct < d_out + N * W)
+    return fail(PAI_ERR_ARG, "pai_neg_dev: d_out must be d_ct or not overlap it");
+  if (W > MODINV_MAX_WORDS) return fail(PAI_ERR_KEY, "pai_neg_dev: keys above 4096 bits are not supported");
+  CtxLock lk(c, (hipStream_t)stream);
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (N == 0) {
+    HIPCHK(modinv_clear(d_status, st));
+    return 0;
+  }
+  if (d_out != d_ct) HIPCHK(hipMemcpyAsync(d_out, d_ct, N * W * 4, hipMemcpyDeviceToDevice, st));
+  uint32_t* word = nullptr;
+  int rc = batch_invert_async(c, d_out, (long long)N, st, inv_mod_n2(c), &word);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(d_status, word, 4, hipMemcpyDeviceToDevice, st));
+  return 0;
 }
 
 // E(x) + y over arrays (encrypted_number.py:139-164): k_plain encodes y_i with max_exponent e_i into
@@ -5313,6 +5312,74 @@ int pai_mul(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, int dt
   HIPCHK(hipMemcpy(ct_out, dout, N * W * 4, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(exp_out, dexo, N * 4, hipMemcpyDeviceToHost));
   if (status_out) HIPCHK(hipMemcpy(status_out, dst, N * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pai_neg(pai_ctx* c, const uint32_t* ct, size_t N, uint32_t* ct_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  if (N == 0) return 0;
+  if (!ct || !ct_out) return fail(PAI_ERR_ARG, "pai_neg: bad arguments");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t W = c->ct_words;
+  DevScope ds;
+  uint32_t* dct = ds.alloc<uint32_t>(N * W);
+  uint32_t* dst = ds.alloc<uint32_t>(1);
+  if (!dct || !dst) return fail(PAI_ERR_HIP, "pai_neg: device allocation failed");
+  HIPCHK(hipMemcpy(dct, ct, N * W * 4, hipMemcpyHostToDevice));
+  int rc = pai_neg_dev(c, dct, N, dct, dst, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  uint32_t status = 0;
+  HIPCHK(hipMemcpy(&status, dst, 4, hipMemcpyDeviceToHost));
+  if (status) return fail(PAI_ERR_NOINV, "invert() no inverse exists");
+  HIPCHK(hipMemcpy(ct_out, dct, N * W * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// k_modinv on caller-supplied residues (below m) and one odd modulus; no context
+int pai_debug_modinv(const uint32_t* x, const uint32_t* m, size_t words, size_t count, uint32_t* out, uint32_t* status) {
+  if (!x || !m || !out || !status || words < 1 || words > MODINV_MAX_WORDS || count < 1 || count > (1u << 20))
+    return fail(PAI_ERR_ARG, "pai_debug_modinv: bad arguments");
+  HBig mod;
+  mod.w.assign(m, m + words);
+  mod.trim();
+  if (mod.is_zero() || !(m[0] & 1u)) return fail(PAI_ERR_ARG, "pai_debug_modinv: the modulus must be odd");
+  for (size_t i = 0; i < count; ++i) {
+    HBig v;
+    v.w.assign(x + i * words, x + (i + 1) * words);
+    v.trim();
+    if (cmp(v, mod) >= 0)
+      return fail(PAI_ERR_ARG, "pai_debug_modinv: a residue is not below the modulus");
+  }
+  DevScope ds;
+  uint32_t* dx = ds.alloc<uint32_t>(count * words);
+  uint32_t* dm = ds.alloc<uint32_t>(words);
+  uint32_t* dout = ds.alloc<uint32_t>(count * words);
+  uint32_t* dst = ds.alloc<uint32_t>(count);
+  if (!dx || !dm || !dout || !dst) return fail(PAI_ERR_HIP, "pai_debug_modinv: device allocation failed");
+  HIPCHK(hipMemcpy(dx, x, count * words * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dm, m, words * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dout, out, count * words * 4, hipMemcpyHostToDevice));
+  ModinvParams p{};
+  p.x = dx;
+  p.m = dm;
+  p.out = dout;
+  p.status = dst;
+  p.W = (int)words;
+  p.rounds = modinv_rounds((int)mod.bits());
+  p.ninv31 = modinv_neg_minv31(m[0]);
+  HIPCHK(modinv_launch(p, (int)count, nullptr));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out, dout, count * words * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(status, dst, count * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// registers per lane and blocks per CU of k_modinv at `words` words, as the runtime reports them
+int pai_debug_modinv_info(size_t words, int* vgprs, int* blocks_per_cu) {
+  if (!vgprs || !blocks_per_cu || words < 1 || words > MODINV_MAX_WORDS) return fail(PAI_ERR_ARG, "pai_debug_modinv_info: bad arguments");
+  HIPCHK(modinv_attributes((int)words, vgprs, blocks_per_cu));
   return 0;
 }
 

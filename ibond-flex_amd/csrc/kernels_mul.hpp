@@ -17,6 +17,7 @@
 
 namespace fpai {
 
+constexpr int INV_TOPS = 64;  // the batch inversion stops building levels at this many values: k_modinv inverts them, a wave each
 constexpr int INV_SEG = 64;   // values per segment of the batch inversion's first level (flexpai.hip batch_invert)
 
 struct MulParams {
@@ -246,6 +247,7 @@ struct InvParams {
   uint32_t mprime;
   int ct_words;
   int seg_len;            // values per segment at this level (<= INV_SEG)
+  const uint32_t* gate;   // down-sweep only (nullable): a non-zero word (k_modinv's any_noinv) and nothing is written
 };
 
 // x~ = (flagged ? x : 1) R mod n^2
@@ -299,6 +301,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_inv_up(InvParams p) {
 
 template <int TPI>
 __global__ __launch_bounds__(BLOCK, 2) void k_inv_down(InvParams p) {
+  if (p.gate && *p.gate) return;
   constexpr int S = TPI * L;
   constexpr int GPB = BLOCK / TPI;
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];

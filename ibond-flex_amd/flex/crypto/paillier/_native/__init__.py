@@ -40,6 +40,7 @@ PAI_OPT_POOL_FUSED = 22
 PAI_BIN_U8, PAI_BIN_U16 = 0, 1
 PAI_OPT_SCAN_TILE, PAI_OPT_SCAN_PATH = 23, 24
 PAI_OPT_FOLD_ROWS, PAI_OPT_FOLD_PATH = 25, 26
+PAI_OPT_INV_DEVICE = 27
 PAI_SCAN_REVERSE = 1
 HIST_RUN = 64          # PAI_HIST_RUN: members of a histogram cell that one k_hist_acc instance sums
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
@@ -51,7 +52,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_ctx_public_fb_prepare", "pai_ctx_public_fb_set_bases", "pai_ctx_public_fb_info",
             "pai_ctx_public_fb_policy",
             "pai_encrypt", "pai_add", "pai_decrypt", "pai_encrypt_dev", "pai_add_dev", "pai_decrypt_dev",
-            "pai_mul", "pai_mul_dev", "pai_matmul", "pai_matmul_dev", "pai_add_plain", "pai_add_plain_dev",
+            "pai_mul", "pai_mul_dev", "pai_neg", "pai_neg_dev", "pai_debug_modinv", "pai_debug_modinv_info", "pai_matmul", "pai_matmul_dev", "pai_add_plain", "pai_add_plain_dev",
             "pai_encrypt_big", "pai_encrypt_big_dev", "pai_mul_big", "pai_mul_big_dev", "pai_add_plain_big",
             "pai_add_plain_big_dev",
             "pai_segment_add", "pai_segment_add_dev", "pai_comm_unique_id", "pai_comm_create", "pai_comm_destroy",
@@ -68,6 +69,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_dev_alloc", "pai_dev_free", "pai_dev_upload", "pai_dev_download", "pai_dev_copy", "pai_dev_io_stats",
             "pai_dev_release_staging", "pai_take_dev", "pai_check_below_dev",
             "pai_take_idx_dev", "pai_segment_add_idx_dev")
+MODINV = ("pai_neg", "pai_neg_dev", "pai_debug_modinv", "pai_debug_modinv_info")
 BIG = tuple(n for n in EXPORTED if "_big" in n)     # PAI_BIG operands (include/flexpai.h)
 RESIDENT = EXPORTED[-11:-2]   # device-resident buffers (include/flexpai.h)
 DEVICE_INDEX = EXPORTED[-2:]  # take and segment sums over index lists that are device memory
@@ -141,6 +143,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pai_repack_dev.argtypes = [P, P, S, P, I, P, P]
         lib.pai_mul.argtypes = [P, P, P, S, I, P, S, P, P, P]
         lib.pai_mul_dev.argtypes = [P, P, P, S, I, P, S, P, P, P, P]
+        modinv = hasattr(lib, "pai_neg")           # (absent from a library built from an earlier commit: tools/inv_ab.py)
+        if modinv:
+            lib.pai_neg.argtypes = [P, P, S, P]
+            lib.pai_neg_dev.argtypes = [P, P, S, P, P, P]
+            lib.pai_debug_modinv.argtypes = [P, P, S, S, P, P]
+            lib.pai_debug_modinv_info.argtypes = [S, P, P]
         lib.pai_add_plain.argtypes = [P, P, P, S, I, P, S, P, P, P]
         lib.pai_add_plain_dev.argtypes = [P, P, P, S, I, P, S, P, P, P, P]
         lib.pai_segment_add.argtypes = [P, P, P, S, P, P, S, P, P]
@@ -193,7 +201,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.pai_mul_big.argtypes = lib.pai_add_plain_big.argtypes = [P, P, P, S, P, P, S, S, P, P, P]
             lib.pai_mul_big_dev.argtypes = lib.pai_add_plain_big_dev.argtypes = [P, P, P, S, P, P, S, S, P, P, P, P]
         for name in EXPORTED:
-            if (not resident and name in RESIDENT) or (not device_index and name in DEVICE_INDEX) or (not big and name in BIG):
+            if (not resident and name in RESIDENT) or (not device_index and name in DEVICE_INDEX) or (not big and name in BIG) or \
+                    (not modinv and name in MODINV):
                 continue
             if name not in ("pai_ctx_destroy", "pai_last_error", "pai_comm_destroy", "pai_release_table_cache"):
                 getattr(lib, name).restype = ctypes.c_int
@@ -540,6 +549,10 @@ class Context:
     def set_matmul_fused(self, enabled: bool):
         """False keeps matmul on k_mul + batch inversion + k_add over all K m d terms; same bits."""
         self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_MATMUL_FUSED, 1 if enabled else 0))
+
+    def set_inv_device(self, enabled: bool):
+        """False sends the batch inversion behind negative scalars through the host step (PAI_OPT_INV_DEVICE); same bits."""
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_INV_DEVICE, 1 if enabled else 0))
 
     @property
     def matmul_path(self) -> int:
@@ -1031,6 +1044,15 @@ class Context:
                                 _ptr(out), _ptr(oe), _ptr(st)))
         return out, oe, st
 
+    def neg(self, ct: np.ndarray) -> np.ndarray:
+        """pai_neg: ct_i^-1 mod n^2, the words of ct_i * -1 (exponents unchanged). ZeroDivisionError where a ciphertext
+        has no inverse."""
+        ct = np.ascontiguousarray(ct, dtype=np.uint32).reshape(-1, self.ct_words)
+        self.calls["pai_neg"] += 1
+        out = np.empty_like(ct)
+        self._chk(self.lib.pai_neg(self._h, _ptr(ct), ct.shape[0], _ptr(out)))
+        return out
+
     def add_plain(self, ct: np.ndarray, exp: np.ndarray, x: np.ndarray):
         """Element-wise ct_i (+) x_i (x of size 1: one scalar for every element); returns (ciphertext
         words, exponents, statuses). PaillierEncryptedNumber.__add__(scalar) semantics."""
@@ -1320,6 +1342,29 @@ def prime_stats() -> dict:
 
 def count_host_fallback(n: int = 1) -> None:
     _prime_stats["host_fallbacks"] += n
+
+
+def modinv(xs, m: int, words: int, fill: int = 0):
+    """pai_debug_modinv: (inverses, statuses) of the residues xs modulo the odd m on `words` 32-bit words each, by
+    k_modinv. A residue without inverse has status 1 and keeps the row pattern `fill` (one word, repeated)."""
+    global _runtime_started
+    lib = load_library()
+    xs = list(xs)
+    x = ints_to_words(xs, words)
+    mw = ints_to_words([m], words)
+    out = np.full((len(xs), words), fill, dtype=np.uint32)
+    st = np.full(len(xs), 0xffffffff, dtype=np.uint32)
+    _runtime_started = True
+    _check(lib.pai_debug_modinv(_ptr(x), _ptr(mw), words, len(xs), _ptr(out), _ptr(st)), lib)
+    return out, st
+
+
+def modinv_info(words: int):
+    """(registers per lane, blocks per CU) of k_modinv at `words` words, as the runtime reports them."""
+    lib = load_library()
+    v, b = ctypes.c_int(), ctypes.c_int()
+    _check(lib.pai_debug_modinv_info(words, ctypes.byref(v), ctypes.byref(b)), lib)
+    return v.value, b.value
 
 
 def prime_sieve(x: int, bits: int, window: int = 0):

@@ -182,6 +182,10 @@ class PaillierArray(np.ndarray):
             return np.ndarray.__rsub__(np.asarray(self), other)
         return res
 
+    def __neg__(self):
+        # PaillierEncryptedNumber * -1 for every element (one batch inversion on the GPU)
+        return self * -1
+
     def __mul__(self, other):
         res = mul_plain(self, other)
         if res is NotImplemented:

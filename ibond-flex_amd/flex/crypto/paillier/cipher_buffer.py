@@ -43,7 +43,7 @@ def _on_device(x) -> bool:
 class BufferOps(object):
     """What CiphertextBuffer and DeviceCiphertextBuffer (device_buffer.py) share: the operators that are written in
     terms of other operators, and indexing. A subclass provides public_key, shape, size, _coerce, _add_plain, __mul__,
-    segment_dot, _dense_dot and _gather."""
+    segment_dot, _dense_dot, _gather and _neg."""
     __slots__ = ()
 
     def __len__(self) -> int:
@@ -86,6 +86,11 @@ class BufferOps(object):
 
     def __rmul__(self, y):
         return self * y
+
+    def __neg__(self):
+        """self * -1 bit for bit (exponents unchanged, not re-randomised) as a call of its own: pai_neg / pai_neg_dev,
+        one batch inversion with no host step. ZeroDivisionError where a ciphertext has no inverse mod n^2."""
+        return self._neg()
 
     def __truediv__(self, s):
         return self * (1 / s)
@@ -274,6 +279,9 @@ class CiphertextBuffer(BufferOps):
             PaillierEncryptedNumber(self.public_key, _ints(self.words[i:i + 1])[0], int(self.exps[i])) * _item(y, i)
             raise ValueError(f"the scalar {_item(y, i)!r} at element {i} does not encode")
         return self._like(out, oe)
+
+    def _neg(self):
+        return self._like(self._ctx().neg(self.words), self.exps)
 
     def segment_dot(self, index, seg_off, weights) -> "CiphertextBuffer":
         """Segmented weighted sums, shape (nseg,): out[s] = sum over t in [seg_off[s], seg_off[s+1]) of

@@ -215,6 +215,16 @@ def mul_dev(pk, words: DeviceWords, exps, x: np.ndarray):
     return _scalar_call("pai_mul_dev", pk, words, exps, x)
 
 
+def neg_dev(pk, words: DeviceWords):
+    """pai_neg_dev: (words, status word on the host). The entry point itself waits for nothing; the 4-byte download of
+    the status word here is where this layer learns of a ciphertext without inverse."""
+    (N, W), dev = words.shape, words.device
+    ctx = context_on(pk, dev)
+    out, st = DeviceWords.empty(N, W, dev), _native.DeviceMem(4, dev)
+    ctx.dev_call("pai_neg_dev", words.ptr, N, out.ptr, st.ptr)
+    return out, int(st.download(np.uint32, 1)[0])
+
+
 def add_plain_dev(pk, words: DeviceWords, exps, x: np.ndarray):
     """pai_add_plain_dev: (words, exponents, statuses on the host)."""
     return _scalar_call("pai_add_plain_dev", pk, words, exps, x)
@@ -661,6 +671,13 @@ class DeviceCiphertextBuffer(BufferOps):
         if np.any(st):
             return (self.to_host() * y).to_device()
         return self._like(out, oe)
+
+    def _neg(self):
+        # the status word is read (4 bytes) before the result is handed out: ZeroDivisionError is raised here, as by * -1
+        out, status = neg_dev(self.public_key, self.words)
+        if status:
+            raise ZeroDivisionError("invert() no inverse exists")
+        return self._like(out, self._ex)
 
     def segment_dot(self, index, seg_off, weights) -> "DeviceCiphertextBuffer":
         """CiphertextBuffer.segment_dot on the device (pai_segment_dot_dev)."""

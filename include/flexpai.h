@@ -228,6 +228,12 @@ typedef struct pai_comm pai_comm;
                                   * for every value */
 #define PAI_OPT_FOLD_PATH 26     /* read-only: the path of this context's last pai_pack_ciphertexts[_dev] or
                                   * pai_repack[_dev] call: 0 = none yet, 1 = lane groups, 2 = rows               */
+#define PAI_OPT_INV_DEVICE 27    /* 1 (default): the batch inversion behind negative scalars (pai_mul, pai_matmul,
+                                    pai_segment_dot, pai_histogram_sparse) reduces to at most 64 values and inverts
+                                    them on the device (k_modinv, csrc/kernels_inv.hpp), reading back one status word;
+                                    0: it reduces to one value and inverts it on the host, as before k_modinv -- same
+                                    bits, kept for comparison. pai_neg[_dev] and pai_encrypt_dev's public-key chain
+                                    use the device kernel either way */
 /* The automatic choice of PAI_OPT_FOLD_ROWS: the largest output count at which the row kernel was more than 5 % faster
  * than the group kernel in the same-process A/B of tools/fold_ab.py on an MI355X (profiles/fold_ab.json),
  * per key size (n^2 of 74 / 148 / 296 limbs). 0: that key size stays on lane groups. Measured at 64, 1 024, 4 096, 16 384
@@ -365,6 +371,11 @@ int pai_mul(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int 
  * Python ints), so int64 * 16^E never wraps. */
 int pai_add_plain(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int dtype, const void* x,
                   size_t x_stride, uint32_t* ct_out, int32_t* exp_out, int32_t* status_out);
+/* Homomorphic negation: ct_out_i = ct_i^-1 mod n^2, bit for bit pai_mul by the integer -1 (whose encoding has
+ * exponent 0, so the exponents are the caller's, unchanged, and are not passed). One batch inversion for the array,
+ * inverted on the device; the output is not re-randomised; ct_out may be ct. A ciphertext without inverse mod n^2
+ * (it shares a factor with n) ends the call with PAI_ERR_NOINV and nothing written. */
+int pai_neg(pai_ctx* ctx, const uint32_t* ct, size_t N, uint32_t* ct_out);
 /* PAI_BIG operands (above). status_out (nullable) is PAI_EL_ENC_RANGE exactly where the reference's encode raises
  * ValueError: |v| > max_int = n // 3 - 1, compared limb for limb on the device (for pai_add_plain_big: |v| 16^E with
  * E = max(exp_i, 0), the encode with max_exponent = exp_i). Such an element is encrypted as 0, multiplied by 1 or added
@@ -524,9 +535,12 @@ int pai_matmul(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t m, s
  * pai_matmul_dev synchronise `stream` once, for the single host-side inversion of the batch; the fused pai_matmul_dev
  * synchronises once to read which rows of x hold a negative scalar, and a second time, for the inversion, only when
  * one does). pai_encrypt_dev never
- * waits on the host: the public-key chain's batch inversion (chunks of >= 16384 elements) inverts its one top value
- * in a host function queued on `stream` (hipLaunchHostFunc), so the call stays asynchronous and capturable; only
- * the first device-RNG call that BUILDS a key's fixed-base tables synchronises the device (per-key setup). */
+ * waits on the host: the public-key chain's batch inversion (chunks of >= 16384 elements) inverts its top values on
+ * the device (k_modinv), with kernels on `stream` only: no host function, no pinned buffer, nothing shared with a host
+ * thread, and no allocation once the context's inversion buffer has its size (it grows on the first call of a larger
+ * chunk). Calls on two streams of one context are ordered by the context and give the bits of the same calls made one
+ * after the other. Only the first device-RNG call that BUILDS a key's fixed-base tables synchronises the device
+ * (per-key setup). */
 int pai_encrypt_dev(pai_ctx* ctx, int dtype, const void* d_x, size_t N, int exp_mode, int32_t fixed_exp,
                     int obf_mode, const uint32_t* d_r_words, size_t r_stride_words, size_t r_words,
                     const uint8_t* rng_key32, uint64_t index_base,
@@ -547,6 +561,11 @@ int pai_mul_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t
 int pai_add_plain_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int dtype,
                       const void* d_x, size_t x_stride, uint32_t* d_out, int32_t* d_exp_out, int32_t* d_status,
                       void* stream);
+/* pai_neg on device buffers. Never waits on the host: d_status[0] (required, one word of device memory) is 0 on
+ * success and 1 when some ciphertext has no inverse; in that case no inverse is written (the down-sweep kernels are
+ * gated on the word; an out-of-place d_out then holds the copy of d_ct). The call returns PAI_OK either way: the
+ * caller reads the word when it wants to know. d_out is d_ct or does not overlap it. */
+int pai_neg_dev(pai_ctx* ctx, const uint32_t* d_ct, size_t N, uint32_t* d_out, uint32_t* d_status, void* stream);
 /* The PAI_BIG entry points on device buffers (d_x, d_neg device memory; r as for pai_encrypt_dev). pai_mul_big_dev
  * synchronises `stream` once, like pai_mul_dev; the others are as asynchronous as pai_obfuscate_dev and pai_add_dev. */
 int pai_encrypt_big_dev(pai_ctx* ctx, const uint32_t* d_x, const uint8_t* d_neg, size_t xw, size_t N, int obf_mode,
@@ -859,6 +878,13 @@ typedef struct pai_route_facts {
 /* sampler: the tables the call is eligible for (used once wanted and built); chain: the per-element kernels otherwise */
 int pai_debug_encrypt_route(const pai_route_facts* facts, int obf_mode, long long n, int r_words, int* sampler,
                             int* chain);
+/* k_modinv alone, without a context: out_i = x_i^-1 mod m for `count` residues x_i < m of `words` 32-bit words each
+ * (1 .. 256) and one odd modulus. status[i] is 0 with the inverse in [0, m) written to row i of out, or 1 where
+ * gcd(x_i, m) != 1, with that row of out as the caller left it. Host pointers; synchronous, on the current device. */
+int pai_debug_modinv(const uint32_t* x, const uint32_t* m, size_t words, size_t count, uint32_t* out,
+                     uint32_t* status);
+/* Registers per lane of k_modinv at `words` words and its blocks (of one wave) per CU, as the runtime reports them. */
+int pai_debug_modinv_info(size_t words, int* vgprs, int* blocks_per_cu);
 
 #ifdef __cplusplus
 }
