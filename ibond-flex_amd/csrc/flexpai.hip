@@ -55,6 +55,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_inv.hpp"
 #include "engine_big.hpp"
 #include "engine_mm.hpp"
+#include "engine_pip.hpp"
 #include "engine_sd.hpp"
 #include "engine_hist.hpp"
 #include "engine_shist.hpp"
@@ -295,7 +296,13 @@ struct pai_ctx {
   } pool;
   // fused matrix product (kernels_mm.hpp): PAI_OPT_MATMUL_FUSED / PAI_OPT_MATMUL_PATH
   bool mm_fused = true;
-  int mm_path = 0;              // last pai_matmul[_dev] call: 0 none yet, 1 term path, 2 fused
+  int mm_path = 0;              // last pai_matmul[_dev] call: 0 none yet, 1 term path, 2 fused, 3 bucket method
+  // bucket method (kernels_pip.hpp): PAI_OPT_MATMUL_BUCKET
+  bool mm_bucket = false;
+  void* d_pip = nullptr;        // per call: E, flags, the summary words, P and N of every output
+  size_t pip_bytes = 0;
+  void* d_pipw = nullptr;       // per block of outputs: member lists, unit offsets, runs, partials, window sums
+  size_t pipw_bytes = 0;
   void* d_mmtab = nullptr;      // window tables of one block of ciphertexts (at most the table budget)
   size_t mmtab_bytes = 0;
   void* d_mmwork = nullptr;     // neg_row [K], the inversion's flags [m K]
@@ -435,6 +442,8 @@ pai_ctx::~pai_ctx() {
   if (d_mmtab) (void)hipFree(d_mmtab);
   if (d_mmwork) (void)hipFree(d_mmwork);
   if (d_mminv) (void)hipFree(d_mminv);
+  if (d_pip) (void)hipFree(d_pip);
+  if (d_pipw) (void)hipFree(d_pipw);
   if (d_sdmeta) (void)hipFree(d_sdmeta);
   if (d_sdbuf) (void)hipFree(d_sdbuf);
   if (d_sdpart) (void)hipFree(d_sdpart);
@@ -2288,6 +2297,7 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       c->crt4_min = value;
       return 0;
     case PAI_OPT_MATMUL_FUSED: c->mm_fused = value != 0; return 0;
+    case PAI_OPT_MATMUL_BUCKET: c->mm_bucket = value != 0; return 0;
     case PAI_OPT_INV_DEVICE: c->inv_device = value != 0; return 0;
     case PAI_OPT_SEGDOT_FUSED: c->sd_fused = value != 0; return 0;
     case PAI_OPT_POOL_FUSED: c->pool.fused = value != 0; return 0;
@@ -2336,6 +2346,7 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_ROWS_MAX: *value = (int)std::min<long long>(c->crtw_max, INT32_MAX); return 0;
     case PAI_OPT_CRT4_MIN: *value = (int)std::min<long long>(c->crt4_min, INT32_MAX); return 0;
     case PAI_OPT_MATMUL_FUSED: *value = c->mm_fused ? 1 : 0; return 0;
+    case PAI_OPT_MATMUL_BUCKET: *value = c->mm_bucket ? 1 : 0; return 0;
     case PAI_OPT_INV_DEVICE: *value = c->inv_device ? 1 : 0; return 0;
     case PAI_OPT_MATMUL_PATH: *value = c->mm_path; return 0;
     case PAI_OPT_SEGDOT_FUSED: *value = c->sd_fused ? 1 : 0; return 0;
@@ -4890,6 +4901,131 @@ static int matmul_fused(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, 
   return 0;
 }
 
+// The bucket method of pai_matmul_dev (kernels_pip.hpp, PAI_OPT_MATMUL_BUCKET = 1): calls of d < MM_MIN_D columns whose
+// effective exponents |M| 16^(E - e) all fit PIP_CAP_BITS. k_pip_scan finds E, the negative-term flags and the widest
+// exponent of every output; the call reads that one word back (its first synchronisation: a call outside the class
+// leaves with *took = 0 and nothing written). Then, per block of outputs that fits PIP_WORK_BYTES: plan, bucket runs,
+// window sums, Horner -- P and N of every output, canonical, in k_add's layout. The N of the outputs with a negative term
+// are inverted by the batch inversion (PAI_ERR_NOINV exactly where the term path raises it: a ciphertext without inverse
+// under a negative non-zero scalar; nothing has been written to the outputs by then) and k_add forms out = P N^-1 at E.
+constexpr size_t PIP_WORK_BYTES = (size_t)512 << 20;
+
+static int matmul_bucket(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t m, size_t K, int dtype,
+                         const void* d_x, size_t d, uint32_t* d_out, int32_t* d_exp_out, hipStream_t st, bool* took) {
+  *took = false;
+  const size_t W = c->ct_words, Np = m * d, S = (size_t)c->tpi_e * L;
+  const int w = pip_window((long long)K);
+  if ((K >> 24) != 0 || Np >= (size_t)INT32_MAX / 2) return 0;     // 32-bit member and unit indices: the term path
+  // fixed part: E [Np], flags [Np], summary words, P and N [2][Np][W], their exponents [2][Np]
+  const size_t o_E = 0, o_neg = align16(o_E + Np * 4), o_sum = align16(o_neg + Np), o_pn = align16(o_sum + 16),
+               o_pne = align16(o_pn + 2 * Np * W * 4), fixed = align16(o_pne + 2 * Np * 4);
+  int rc = ensure_buf(&c->d_pip, &c->pip_bytes, fixed);
+  if (rc) return rc;
+  char* fb = (char*)c->d_pip;
+  int32_t* E = (int32_t*)(fb + o_E);
+  uint8_t* neg = (uint8_t*)(fb + o_neg);
+  int* summary = (int*)(fb + o_sum);                               // [0] widest exponent, [1] units of the current block
+  uint32_t* pn = (uint32_t*)(fb + o_pn);
+  int32_t* pne = (int32_t*)(fb + o_pne);
+  HIPCHK(hipMemsetAsync(summary, 0, 16, st));
+  PipScanParams sp{};
+  sp.exp = d_exp;
+  sp.x = d_x;
+  sp.dtype = dtype;
+  sp.K = (long long)K;
+  sp.d = (long long)d;
+  sp.Np = (long long)Np;
+  sp.E = E;
+  sp.neg = neg;
+  sp.summary = summary;
+  HIPCHK(pip_scan_launch(sp, c->cus, st));
+  int bits = 0;
+  HIPCHK(hipMemcpyAsync(&bits, summary, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (bits > PIP_CAP_BITS) return 0;
+  *took = true;
+  c->mm_path = 3;
+  const int nwin = std::max(1, (bits + w - 1) / w);
+  const size_t cells = ((size_t)2 * nwin) << w, Ms = (size_t)pip_member_slots((long long)K, w),
+               Us = (size_t)pip_unit_slots((long long)K, w, nwin), ninst = (size_t)2 * nwin;
+  // per output: members, unit offsets, runs, partials, the running products and sums of its windows, their flags
+  const size_t per_out = Ms * 4 + (cells + 1) * 4 + Us * (16 + S * 4) + ninst * (2 * S * 4 + 1) + 64;
+  size_t nob = std::max<size_t>(1, std::min(Np, PIP_WORK_BYTES / per_out));
+  nob = std::min(nob, (size_t)(INT32_MAX / 2) / std::max(Ms, Us));
+  if (nob == 0) return fail(PAI_ERR_ARG, "pai_matmul_dev: row too long for the bucket method");
+  const size_t o_mem = 0, o_uoff = align16(o_mem + nob * Ms * 4), o_runs = align16(o_uoff + nob * (cells + 1) * 4),
+               o_part = align16(o_runs + nob * Us * 16), o_run = align16(o_part + nob * Us * S * 4),
+               o_wsum = align16(o_run + nob * ninst * S * 4), o_wflag = align16(o_wsum + nob * ninst * S * 4),
+               work = align16(o_wflag + nob * ninst);
+  if ((rc = ensure_buf(&c->d_pipw, &c->pipw_bytes, work))) return rc;
+  char* wb = (char*)c->d_pipw;
+  for (size_t o0 = 0; o0 < Np; o0 += nob) {
+    const size_t nb = std::min(nob, Np - o0);
+    HIPCHK(hipMemsetAsync(summary + 1, 0, 4, st));
+    HIPCHK(hipMemsetAsync(wb + o_mem, 0, nb * Ms * 4, st));        // a slot the second pass misses reads row 0, not garbage
+    PipPlanParams pp{};
+    pp.exp = d_exp;
+    pp.x = d_x;
+    pp.dtype = dtype;
+    pp.K = (long long)K;
+    pp.d = (long long)d;
+    pp.o0 = (long long)o0;
+    pp.nob = (long long)nb;
+    pp.E = E;
+    pp.w = w;
+    pp.nwin = nwin;
+    pp.Ms = (long long)Ms;
+    pp.members = (int32_t*)(wb + o_mem);
+    pp.uoff = (int32_t*)(wb + o_uoff);
+    pp.runs = (int4*)(wb + o_runs);
+    pp.nunits = (unsigned*)(summary + 1);
+    HIPCHK(pip_plan_launch(pp, c->cus, st));
+    PipAccParams ap{};
+    ap.ct = d_ct;
+    ap.K = (long long)K;
+    ap.members = pp.members;
+    ap.runs = pp.runs;
+    ap.nunits = pp.nunits;
+    ap.part = (uint32_t*)(wb + o_part);
+    ap.N = c->d_N;
+    ap.RS = c->d_RS;
+    ap.mprime = c->mprime_N;
+    ap.ct_words = c->ct_words;
+    HIPCHK(pip_acc_launch(c->tpi_e, ap, (long long)(nb * Us), c->cus, st));
+    PipRedParams rp{};
+    rp.uoff = pp.uoff;
+    rp.nob = (long long)nb;
+    rp.w = w;
+    rp.nwin = nwin;
+    rp.part = ap.part;
+    rp.run = (uint32_t*)(wb + o_run);
+    rp.wsum = (uint32_t*)(wb + o_wsum);
+    rp.wflag = (uint8_t*)(wb + o_wflag);
+    rp.N = c->d_N;
+    rp.oneR = c->d_oneR;
+    rp.mprime = c->mprime_N;
+    HIPCHK(pip_red_launch(c->tpi_e, rp, c->cus, st));
+    PipHornerParams hp{};
+    hp.wsum = rp.wsum;
+    hp.wflag = rp.wflag;
+    hp.E = E;
+    hp.o0 = (long long)o0;
+    hp.nob = (long long)nb;
+    hp.Np = (long long)Np;
+    hp.w = w;
+    hp.nwin = nwin;
+    hp.pn = pn;
+    hp.pnexp = pne;
+    hp.N = c->d_N;
+    hp.oneR = c->d_oneR;
+    hp.mprime = c->mprime_N;
+    hp.ct_words = c->ct_words;
+    HIPCHK(pip_horner_launch(c->tpi_e, hp, c->cus, st));
+  }
+  if ((rc = batch_invert(c, pn + Np * W, neg, (long long)Np, st))) return rc;
+  return add_dev(c, pn, pne, 2, (long long)Np, d_out, d_exp_out, st);
+}
+
 int pai_matmul_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t m, size_t K, int dtype,
                    const void* d_x, size_t d, uint32_t* d_out, int32_t* d_exp_out, void* stream) {
   if (!c) return fail(PAI_ERR_ARG, "null ctx");
@@ -4901,6 +5037,11 @@ int pai_matmul_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_
   hipStream_t st = (hipStream_t)stream;
   const size_t W = c->ct_words, Np = m * d, T = K * Np;
   const int C = MATMUL_CHUNK;
+  if (c->mm_bucket && d < MM_MIN_D) {   // bucket method (kernels_pip.hpp) where the exponents fit its cap
+    bool took = false;
+    const int rcb = matmul_bucket(c, d_ct, d_exp, m, K, dtype, d_x, d, d_out, d_exp_out, st, &took);
+    if (rcb || took) return rcb;
+  }
   // fused (kernels_mm.hpp): the term buffer holds the ceil(K / MM_KC) chunk partials instead of the K terms
   const bool fused = mm_take_fused(c, m, K, d);
   c->mm_path = fused ? 2 : 1;

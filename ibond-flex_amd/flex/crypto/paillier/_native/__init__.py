@@ -41,6 +41,7 @@ PAI_BIN_U8, PAI_BIN_U16 = 0, 1
 PAI_OPT_SCAN_TILE, PAI_OPT_SCAN_PATH = 23, 24
 PAI_OPT_FOLD_ROWS, PAI_OPT_FOLD_PATH = 25, 26
 PAI_OPT_INV_DEVICE = 27
+PAI_OPT_MATMUL_BUCKET = 28
 PAI_SCAN_REVERSE = 1
 HIST_RUN = 64          # PAI_HIST_RUN: members of a histogram cell that one k_hist_acc instance sums
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
@@ -555,8 +556,18 @@ class Context:
         self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_INV_DEVICE, 1 if enabled else 0))
 
     @property
+    def matmul_bucket(self) -> bool:
+        """True when matmul of fewer than 16 columns runs the bucket method (kernels_pip.hpp) wherever the effective
+        exponents fit its cap; off by default."""
+        return bool(self._get_option(PAI_OPT_MATMUL_BUCKET))
+
+    def set_matmul_bucket(self, enabled: bool):
+        """True sends narrow matmul calls through the bucket-method multi-exponentiation; same bits."""
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_MATMUL_BUCKET, 1 if enabled else 0))
+
+    @property
     def matmul_path(self) -> int:
-        """The path of this context's last matmul call: 0 = none yet, 1 = term path, 2 = fused."""
+        """The path of this context's last matmul call: 0 = none yet, 1 = term path, 2 = fused, 3 = bucket method."""
         return int(self._get_option(PAI_OPT_MATMUL_PATH))
 
     @property

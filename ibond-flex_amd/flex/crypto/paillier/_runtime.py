@@ -101,6 +101,8 @@ def context(public_key, private_key=None) -> "_native.Context":
         ctx = _ctxs.get(k)
         if ctx is None:
             ctx = _native.Context(public_key.n, dev)
+            if os.environ.get("FLEXPAI_MATMUL_BUCKET", "0").strip() == "1":
+                ctx.set_matmul_bucket(True)            # narrow dot products through the bucket method (kernels_pip.hpp)
             _ctxs[k] = ctx
             _evict_lru()
         else:

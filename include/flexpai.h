@@ -198,7 +198,7 @@ typedef struct pai_comm pai_comm;
                                   * exponentiation per term (k, i, j), one batch inversion over the terms and the k_add
                                   * tree over all of them. Read back: 1 when the fused path is in use. Same bits either way */
 #define PAI_OPT_MATMUL_PATH 17   /* read-only: the path of this context's last pai_matmul[_dev] call: 0 = none yet,
-                                  * 1 = term path, 2 = fused                                                     */
+                                  * 1 = term path, 2 = fused, 3 = bucket method (PAI_OPT_MATMUL_BUCKET)          */
 
 #define PAI_OPT_OBF_CHUNK 18     /* elements per slice of an in-place pai_obfuscate_dev (default 262 144, at least 64): the
                                   * call keeps r^n of one slice in a buffer of the context. Same bits for every value */
@@ -234,6 +234,13 @@ typedef struct pai_comm pai_comm;
                                     0: it reduces to one value and inverts it on the host, as before k_modinv -- same
                                     bits, kept for comparison. pai_neg[_dev] and pai_encrypt_dev's public-key chain
                                     use the device kernel either way */
+#define PAI_OPT_MATMUL_BUCKET 28 /* 0 (default): off. 1: pai_matmul[_dev] of fewer than 16 columns runs the bucket method
+                                  * (Pippenger multi-exponentiation, csrc/kernels_pip.hpp: k_pip_scan, k_pip_plan,
+                                  * k_pip_acc, k_pip_red, k_pip_horner, then one batch inversion over the outputs that
+                                  * have a negative term and one k_add) when every output's effective exponents
+                                  * |M| 16^(E - e) fit 512 bits; other calls take the path they take with 0. Window of
+                                  * 4 .. 8 bits from K (csrc/engine_pip.hpp). Same bits and the same PAI_ERR_NOINV
+                                  * either way; whether it is faster has been measured per shape */
 /* The automatic choice of PAI_OPT_FOLD_ROWS: the largest output count at which the row kernel was more than 5 % faster
  * than the group kernel in the same-process A/B of tools/fold_ab.py on an MI355X (profiles/fold_ab.json),
  * per key size (n^2 of 74 / 148 / 296 limbs). 0: that key size stays on lane groups. Measured at 64, 1 024, 4 096, 16 384

@@ -17,7 +17,13 @@ times, their spread, the ratio, whether the outputs are identical and the produc
 --always runs side a on the test build under $FLEXPAI_MM_ALWAYS=1, i.e. through the fused kernels whatever the shape
 (the same object code as the product's): that is how the dispatch's class (flexpai.hip mm_take_fused) was measured
 (profiles/mm_ab.json, profiles/mm_ab_sweep.json). Without it side a is the product library with its dispatch
-(profiles/mm_ab_default.json: "a_path" 1 = the call stayed on the term path)."""
+(profiles/mm_ab_default.json: "a_path" 1 = the call stayed on the term path).
+
+--bucket times the bucket method instead (kernels_pip.hpp): side a is the product library with PAI_OPT_MATMUL_BUCKET = 1,
+side b must be the parent commit's library (never this tree's own term path), the shapes are the narrow ones
+(BUCKET_SHAPES), every column of the scalars holds a negative entry, the model column is the bucket method's product
+count per output (csrc/engine_pip.hpp) next to the term path's 6 nw per term, and the output goes to
+profiles/mm_bucket_ab.json."""
 import argparse
 import hashlib
 import json
@@ -33,6 +39,17 @@ import torch  # noqa: E402
 import mm_model  # noqa: E402
 
 SHAPES = [(1024, 1, 4096, 64), (1024, 1, 4096, 1), (2048, 1, 4096, 64), (2048, 1, 4096, 1), (4096, 1, 1024, 16)]
+BUCKET_SHAPES = [(nb, m, K, d) for nb in (1024, 2048)
+                 for m, K, d in ((1, 1024, 1), (1, 4096, 1), (1, 65536, 1), (1, 4096, 8), (64, 4096, 1))] + [(4096, 1, 4096, 1)]
+BUCKET_WINDOWS = ((0, 4), (108, 5), (289, 6), (896, 8))     # csrc/engine_pip.hpp PIP_WINDOWS
+
+
+def bucket_products(K, bits=56):
+    """Products per output of the bucket method at float64 scalars of one exponent class (53-bit magnitudes and up to
+    3 bits of alignment): nwin K + 2 nwin 2^w + nwin w; and of the term path: 6 nw per term at nw = 14 windows of 4 bits."""
+    w = [ww for k0, ww in BUCKET_WINDOWS if K >= k0][-1]
+    nwin = -(-bits // w)
+    return {"w": w, "bucket": nwin * K + 2 * nwin * 2 ** w + nwin * w, "term": 6 * 14 * K}
 
 
 def sha256(path):
@@ -49,8 +66,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--shapes", default="", help="nb,m,K,d;nb,m,K,d;... instead of the default shapes")
     ap.add_argument("--always", action="store_true", help="side a: the test build with FLEXPAI_MM_ALWAYS=1")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mm_ab.json"))
+    ap.add_argument("--bucket", action="store_true", help="side a: the bucket method (PAI_OPT_MATMUL_BUCKET = 1)")
+    ap.add_argument("--out", default="")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "mm_bucket_ab.json" if args.bucket else "mm_ab.json")
     from flex.crypto.paillier import _native as N
     with open(os.path.join(ROOT, "tests", "golden", "paillier_golden.json")) as f:
         keys = json.load(f)["keys"]
@@ -62,23 +81,31 @@ def main():
     path_a = N.XCHECK_LIB_PATH if args.always else N.LIB_PATH
     lib_a = N.load_library(path_a)
     have_parent = os.path.exists(args.parent)
+    if args.bucket and not have_parent:
+        sys.exit("--bucket compares against the parent commit's library: build it and pass --parent")
     lib_b = N.load_library(args.parent) if have_parent else lib_a
     result = {"b_kind": "parent library" if have_parent else "same library, PAI_OPT_MATMUL_FUSED = 0",
               "rounds": args.rounds, "device": torch.cuda.get_device_name(dev), "shapes": []}
-    shapes = [tuple(int(v) for v in t.split(",")) for t in args.shapes.split(";") if t] or SHAPES
+    shapes = [tuple(int(v) for v in t.split(",")) for t in args.shapes.split(";") if t] or (BUCKET_SHAPES if args.bucket else SHAPES)
     result["a_kind"] = "test build, every call fused" if args.always else "product library, default dispatch"
+    if args.bucket:
+        result["a_kind"] = "product library, PAI_OPT_MATMUL_BUCKET = 1"
     for nb, m, K, d in shapes:
         n = int(keys[str(nb)]["n"], 16)
         ca = N.Context(n, 0, lib=lib_a)
         cb = N.Context(n, 0, lib=lib_b)
         if not have_parent:
             cb.set_matmul_fused(False)
+        if args.bucket:
+            ca.set_matmul_bucket(True)
         W = ca.ct_words
         g = torch.Generator(device=dev).manual_seed(nb + d)
         ct = torch.randint(0, 2 ** 31 - 1, (m * K, W), dtype=torch.int32, device=dev, generator=g)
         ct[:, W - 1] = 0                                   # < 2^(32 (W - 1)) < n^2
         ex = torch.randint(12, 15, (m * K,), dtype=torch.int32, device=dev, generator=g)
         x = torch.randn((K, d), dtype=torch.float64, device=dev, generator=g)
+        if args.bucket:
+            x[0] = -x[0].abs()                             # a negative entry in every column
         outs = {s: (torch.empty((m * d, W), dtype=torch.int32, device=dev), torch.empty(m * d, dtype=torch.int32, device=dev))
                 for s in "ab"}
         side = {"a": (lib_a, ca), "b": (lib_b, cb)}
@@ -110,7 +137,10 @@ def main():
                       "spread": round((max(ms[s]) - min(ms[s])) / med, 4)}
         row["speedup_b_over_a"] = round(row["b"]["median_ms"] / row["a"]["median_ms"], 3)
         row["faster_beyond_spread"] = bool(min(ms["b"]) > max(ms["a"]))
-        row["model_product_ratio"] = mm_model.counts(m, K, d, 14, neg)["ratio_term_over_fused"]
+        if args.bucket:
+            row["model_products_per_output"] = bucket_products(K)
+        else:
+            row["model_product_ratio"] = mm_model.counts(m, K, d, 14, neg)["ratio_term_over_fused"]
         result["shapes"].append(row)
         print(json.dumps(row), flush=True)
         del ca, cb
