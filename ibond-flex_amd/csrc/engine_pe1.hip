@@ -27,4 +27,11 @@ hipError_t pe1_launch(const Pe1Params& p, const DecPairPreParams& pre, int gx, i
   return hipSuccess;
 }
 
+hipError_t pe1_launch_fin(const Pe1Params& p, int cus, hipStream_t st) {
+  const long long lb = (p.n + LANE_BLOCK - 1) / LANE_BLOCK;
+  hipLaunchKernelGGL(k_pe1_fin<PE1_S>, dim3((int)std::max<long long>(1, std::min<long long>(lb, 8ll * cus))), dim3(LANE_BLOCK),
+                     0, st, p);
+  return hipGetLastError();
+}
+
 }  // namespace fpai

@@ -48,6 +48,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_grp_pair.hpp"
 #include "engine_pe.hpp"
 #include "engine_pfb.hpp"
+#include "engine_pfb1.hpp"
 #include "engine_sgp.hpp"
 #include "engine_sgs.hpp"
 #include "engine_grp.hpp"
@@ -139,6 +140,7 @@ struct PfbTables {
   int K = 0, K0 = 0, W_used = 0;   // digit positions (K0 of them e_0's), window
   PfbConst* d_pfb = nullptr;
   SgpHalf* d_sgp = nullptr;        // the split-pair sampler over the public tables (kernels_sgp.hpp)
+  Pfb1Const* d_pfb1 = nullptr;     // 1024-bit keys: Montgomery pair rows for k_pfb1 (kernels_pfb1.hpp)
   std::vector<void*> mem, tables;
   void release() {
     free_device(mem, tables);
@@ -242,7 +244,7 @@ struct pai_ctx {
   // Built lazily past the break-even count (or pai_ctx_public_fb_prepare); never needed for correctness.
   int pfb_state = FB_UNTRIED;
   std::string pfb_reason;
-  bool pfb_enabled = true;
+  int pfb_enabled = 1;         // PAI_OPT_PUBLIC_FB: 0 off, 1 the 2048-bit sampler, 2 the 1024-bit one (k_pfb1) as well
   int pfb_W = 0;                // requested window; 0 = not chosen yet
   std::vector<HBig> pfb_bases;  // g_0 .. g_PFB_SHORT (chosen at the first build unless set)
   PfbTables pfb;
@@ -1442,6 +1444,7 @@ static long long fb_break_even(const pai_ctx* c, uint64_t rows, int row_bytes) {
 
 static bool fb_wanted(pai_ctx* c, long long n);
 static bool pfb_supported(const pai_ctx* c);
+static bool pfb1_key(const pai_ctx* c);
 
 static int fb_unavailable(pai_ctx* c, const std::string& why) {
   c->fb.release();
@@ -2316,7 +2319,16 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
     case PAI_OPT_STAGE_TIMING: c->timing = value != 0; stage_reset(c); return 0;
     case PAI_OPT_LANE_DECRYPT: c->dec_lane_enabled = value != 0; return 0;
     case PAI_OPT_FIXED_BASE: c->fb_enabled = value != 0; return 0;
-    case PAI_OPT_PUBLIC_FB: c->pfb_enabled = value != 0; return 0;
+    case PAI_OPT_PUBLIC_FB: {
+      const int v = value == 2 ? 2 : value != 0;
+      if (pfb1_key(c) && (v == 2) != (c->pfb_enabled == 2)) {   // the 1024-bit sampler switched on or off: start afresh
+        HIPCHK(hipSetDevice(c->device));
+        c->pfb.release();
+        c->pfb_state = pai_ctx::FB_UNTRIED;
+      }
+      c->pfb_enabled = v;
+      return 0;
+    }
     case PAI_OPT_PFB_WINDOW:
       if (!pfb_window_ok(value)) return fail(PAI_ERR_ARG, "public fixed-base window must be 12, 16 or 20");
       if (value == c->pfb_W) return 0;
@@ -2366,7 +2378,7 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_FB_WINDOW: *value = c->fb.W_used ? c->fb.W_used : c->fb_W ? c->fb_W : fb_default_window(); return 0;
     case PAI_OPT_FB_READY: *value = c->fb_state == pai_ctx::FB_READY ? 1 : 0; return 0;
     case PAI_OPT_PUBLIC_FB:
-      *value = (pfb_supported(c) && c->pfb_enabled && c->pfb_state != pai_ctx::FB_UNAVAILABLE) ? 1 : 0;
+      *value = (pfb_supported(c) && c->pfb_enabled && c->pfb_state != pai_ctx::FB_UNAVAILABLE) ? c->pfb_enabled : 0;
       return 0;
     case PAI_OPT_PFB_READY: *value = c->pfb_state == pai_ctx::FB_READY ? 1 : 0; return 0;
     case PAI_OPT_PFB_WINDOW: *value = c->pfb.W_used ? c->pfb.W_used : c->pfb_W ? c->pfb_W : pfb_default_window(); return 0;
@@ -2524,7 +2536,7 @@ static pai_route_facts route_facts(const pai_ctx* c) {
   f.has_priv = c->has_priv;
   f.crt_enabled = c->crt_enabled;
   f.fb_enabled = c->fb_enabled;
-  f.pfb_enabled = c->pfb_enabled;
+  f.pfb_enabled = c->pfb_enabled != 0;
   f.crt_ok = c->crt_ok;
   f.crt_sa = c->crt_sa;
   f.fbg_ok = c->fbg_ok;
@@ -2716,7 +2728,12 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
 // and gets r^n mod n^2 as a product of table rows (distribution argument, break-even). The rows and
 // k_pe_fin's output are 64-word pairs, so of setup_pe's 1537..2048 bits only the keys of 128 ciphertext words (n of
 // 2033..2048 bits) qualify, as for k_pe_* in encrypt_route.hpp.
+// Under PAI_OPT_PUBLIC_FB = 2 the keys of 64 ciphertext words (n of 1009..1024 bits) qualify too: k_pfb1 over Montgomery
+// pair rows of 2 x 32 words, k_pe1_fin's 37-limb pairs (kernels_pfb1.hpp). Opt-in: the default leaves them on k_pe1_*.
+static bool pfb1_key(const pai_ctx* c) { return c->pe1_ok && c->ct_words == 2 * PFB1_PW; }
+
 static bool pfb_supported(const pai_ctx* c) {
+  if (c->pfb_enabled == 2 && pfb1_key(c)) return true;
   return c->pe_ok && c->ct_words == 2 * PFB_PW && (size_t)c->nb + 24 <= (size_t)LB * PFB_S;
 }
 
@@ -2728,7 +2745,7 @@ static void pfb_digit_counts(const pai_ctx* c, int W, int* K0, int* KS) {
 static uint64_t pfb_bytes(const pai_ctx* c, int W) {
   int K0, KS;
   pfb_digit_counts(c, W, &K0, &KS);
-  return (uint64_t)(K0 + PFB_SHORT * KS) * (1ull << W) * PFB_ROW4 * 16ull;
+  return (uint64_t)(K0 + PFB_SHORT * KS) * (1ull << W) * (pfb1_key(c) ? PFB1_ROW4 : PFB_ROW4) * 16ull;
 }
 
 static int pfb_choose_window(pai_ctx* c) {
@@ -2852,10 +2869,46 @@ static int pfb_upload(pai_ctx* c, int W, int K0, int KS, RowScratch& sc, uint4**
   return 0;
 }
 
+// The 1024-bit tables (kernels_pfb1.hpp): n, the pair of R mod n^2, the pairs of g_j R and n's words up; the digit
+// bases, the half-digit powers (scratch, freed here) and the rows are all made on the device.
+static int build_pfb1(pai_ctx* c, int W, int K0, int KS) {
+  const HBig &n = c->n, &n2 = c->N;
+  const size_t RS = (size_t)LB * PFB1_S;
+  const int K = K0 + PFB_SHORT * KS, LO = W / 2;
+  const size_t nent = ((size_t)1 << LO) + ((size_t)1 << (W - LO));
+  PfbTables& pfb = c->pfb;
+  std::vector<uint32_t> gR;
+  for (const HBig& g : c->pfb_bases) append(gR, pair_split(mul_pow2_mod(g, RS, n2), n, PFB1_S));
+  uint32_t *dn, *done, *dgR, *dnw, *dbases = nullptr, *dlohi = nullptr;
+  int rc;
+  if ((rc = upload_to(pfb.mem, n.limbs(PFB1_S, LB), &dn)) ||
+      (rc = upload_to(pfb.mem, pair_split(mul_pow2_mod(HBig(1), RS, n2), n, PFB1_S), &done)) ||
+      (rc = upload_to(pfb.mem, gR, &dgR)) || (rc = upload_to(pfb.mem, n.words(PFB1_PW), &dnw)))
+    return rc;
+  uint4* table = (uint4*)TableArena::get().alloc(c->device, ((size_t)K << W) * PFB1_ROW4 * sizeof(uint4));
+  if (!table) return fail(PAI_ERR_HIP, "table allocation failed");
+  pfb.tables.push_back(table);
+  if (hipMalloc(&dbases, (size_t)K * 2 * PFB1_S * 4) == hipSuccess && hipMalloc(&dlohi, (size_t)K * nent * 2 * PFB1_S * 4) == hipSuccess) {
+    const Pfb1Const pc{dn, done, dgR, dnw, dbases, dlohi, table, mont_prime(n, LB), (int)n.bits(), (int)c->pfb_bases.size(),
+                       K, W, K0, KS};
+    SetupTrace tr("  pfb1 chain, lohi, fill");
+    if (!(rc = upload_to(pfb.mem, std::vector<Pfb1Const>{pc}, &pfb.d_pfb1)) &&
+        (pfb1_build(pfb.d_pfb1, pc.nbases, K, W, table, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+      rc = fail(PAI_ERR_HIP, "table construction failed");
+  } else {
+    rc = fail(PAI_ERR_HIP, "table allocation failed");
+  }
+  if (dbases) (void)hipFree(dbases);
+  if (dlohi) (void)hipFree(dlohi);
+  return rc;
+}
+
 static int ensure_pfb(pai_ctx* c) {
   if (c->pfb_state == pai_ctx::FB_READY) return 1;
   if (c->pfb_state == pai_ctx::FB_UNAVAILABLE) return 0;
-  if (!pfb_supported(c)) return pfb_unavailable(c, "the public fixed-base kernels need an n of 2033..2048 bits (128 ciphertext words)");
+  if (!pfb_supported(c))
+    return pfb_unavailable(c, "the public fixed-base kernels need an n of 2033..2048 bits (128 ciphertext words), or of "
+                              "1009..1024 bits (64 words) under PAI_OPT_PUBLIC_FB = 2");
   const int W = pfb_choose_window(c);
   if (!W) return pfb_unavailable(c, "tables do not fit the device memory budget");
   SetupTrace tr_all("ensure_pfb");
@@ -2868,6 +2921,14 @@ static int ensure_pfb(pai_ctx* c) {
   }
   PfbTables& pfb = c->pfb;
   pfb.release();
+  if (pfb1_key(c)) {
+    if (build_pfb1(c, W, K0, KS)) return pfb_unavailable(c, pai_last_error());
+    pfb.K = K;
+    pfb.K0 = K0;
+    pfb.W_used = W;
+    c->pfb_state = pai_ctx::FB_READY;
+    return 1;
+  }
   RowScratch sc;
   uint4* table = nullptr;
   if (pfb_upload(c, W, K0, KS, sc, &table)) return pfb_unavailable(c, pai_last_error());
@@ -2900,6 +2961,16 @@ static long long pfb_threshold(pai_ctx* c) {
   if (!W) return 0;
   int K0, KS;
   pfb_digit_counts(c, W, &K0, &KS);
+  if (pfb1_key(c)) {
+    // The 1024-bit tables, one MI355X, 1M elements (tools/gpu/pfb1_rate.py, profiles/pfb1_rate.json): the build takes
+    // 0.068 s at W = 12 (1.42 M rows) and 0.082 s at W = 16 (17.0 M rows) -- 0.067 s + 0.88 ns per row -- and an element
+    // then costs 1 / 12.0 M s (W = 12) or 1 / 15.3 M s (W = 16) on k_pfb1 instead of 1 / 4.43 M s on k_pe1_*: the
+    // break-even is ~480 k elements at W = 12 and ~510 k at the default W = 16. W = 20 is not measured: it is priced at
+    // W = 16's rate and the per-row build cost.
+    const double build_s = 0.067 + (double)(K0 + PFB_SHORT * KS) * (double)(1ull << W) * 0.88e-9;
+    const double save_s = 1.0 / 4.43e6 - 1.0 / (W >= 16 ? 15.3e6 : 12.0e6);
+    return (long long)(build_s / save_s) + 1;
+  }
   const double build_s = 0.114 + (double)(K0 + PFB_SHORT * KS) * (double)(1ull << W) * 1.91e-9;
   const double rate = W >= 20 ? 4.78e6 : W >= 16 ? 3.93e6 : 3.00e6;
   const double save_s = 1.0 / 5.52e5 - 1.0 / rate;
@@ -2913,8 +2984,50 @@ static bool pfb_wanted(pai_ctx* c, long long n) {
   return c->pfb_seen >= pfb_threshold(c);
 }
 
+// 1024-bit keys: digits, k_pfb1, k_pe1_fin per chunk of CRT_CHUNK elements
+static int launch_pfb1(pai_ctx* c, const EncParams& e, hipStream_t st) {
+  const long long N = e.n;
+  const long long chunk = std::min(N, CRT_CHUNK);
+  int occ = 1;
+  pfb1_occupancy(&occ);
+  const size_t dbytes = (size_t)c->pfb.K * 4, xbytes = (size_t)2 * PFB1_S * 4;
+  int rc;
+  if ((rc = ensure_work(c, (dbytes + xbytes) * chunk))) return rc;
+  uint32_t* digits = (uint32_t*)c->d_work;
+  uint32_t* xw = (uint32_t*)((char*)c->d_work + dbytes * chunk);
+  for (long long off = 0; off < N; off += chunk) {
+    const long long n = std::min(chunk, N - off);
+    const EncSlice sl = enc_slice(e, off);
+    PfbDigitParams pd{};
+    pd.n = n;
+    std::memcpy(pd.rng_key, sl.rnd.rng_key, sizeof(pd.rng_key));
+    pd.index_base = sl.rnd.index_base;
+    pd.K = c->pfb.K;
+    pd.W = c->pfb.W_used;
+    pd.digits = digits;
+    const int gD = (int)std::max<long long>(1, std::min<long long>((long long)8 * c->cus, (n + PFB_DIG_BLOCK - 1) / PFB_DIG_BLOCK));
+    stage_mark(c, 0, st);
+    HIPCHK(pfb_launch_digits(pd, gD, st));
+    stage_mark(c, 1, st);
+    const long long lb = (n + LANE_BLOCK - 1) / LANE_BLOCK;
+    HIPCHK(pfb1_launch(Pfb1Params{c->pfb.d_pfb1, n, digits, xw}, (int)std::min<long long>(lb, (long long)occ * c->cus), st));
+    stage_mark(c, 2, st);
+    Pe1Params pf{};
+    set_flat(pf, sl);
+    pf.n = n;
+    pf.nl = c->d_pe1_n;
+    pf.r2n = c->d_pe1_r2n;
+    pf.mprime = c->pe1_mprime;
+    pf.xw = xw;
+    HIPCHK(pe1_launch_fin(pf, c->cus, st));
+    stage_mark(c, 3, st);
+  }
+  return 0;
+}
+
 // digits, k_pfb, k_pe_fin per chunk of CRT_CHUNK elements
 static int launch_pfb(pai_ctx* c, const EncParams& e, hipStream_t st) {
+  if (c->pfb.d_pfb1) return launch_pfb1(c, e, st);
   const long long N = e.n;
   const long long chunk = std::min(N, CRT_CHUNK);
 #if FLEXPAI_XCHECK

@@ -709,8 +709,10 @@ class Context:
         """True when device-RNG encryption without the private key may use the public fixed bases."""
         return bool(self._get_option(PAI_OPT_PUBLIC_FB))
 
-    def set_public_fixed_base(self, enabled: bool):
-        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_PUBLIC_FB, 1 if enabled else 0))
+    def set_public_fixed_base(self, enabled):
+        """False / True as before; 2 also enables the 1024-bit sampler (k_pfb1) for an n of 1009..1024 bits, which
+        then engages once prepare_public_fixed_base() has built its tables (include/flexpai.h)."""
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_PUBLIC_FB, 2 if enabled == 2 else 1 if enabled else 0))
 
     @property
     def pfb_ready(self) -> bool:

@@ -164,8 +164,14 @@ typedef struct pai_comm pai_comm;
                                     run k_pe_*, the others k_encrypt. The whole order: csrc/encrypt_route.hpp  */
 #define PAI_OPT_PUBLIC_FB 10     /* 1 (default): PAI_OBF_RNG encryption WITHOUT the private key (2048-bit n) samples
                                   * r^n through the public fixed bases (kernels_pfb.hpp) once the break-even count
-                                  * is reached (pai_ctx_public_fb_policy); get: 1 when the path is enabled and not
-                                  * known unavailable                                                          */
+                                  * is reached (pai_ctx_public_fb_policy); get: the value set (1 or 2) when the path
+                                  * is enabled and not known unavailable, else 0.
+                                  * 2 (opt-in): the same, and an n of 1009..1024 bits (64 ciphertext words) gets the
+                                  * same sampler on Montgomery pair rows of 256 B (kernels_pfb1.hpp: k_pfb1): same
+                                  * bases, exponents, windows and calls as at 2048 bits, same r; measured break-even
+                                  * ~510 k elements at the default window 16 (pai_ctx_public_fb_policy). At other
+                                  * key sizes 2 acts as 1; 0 and 1 leave a 1024-bit context on k_pe1_*, bit for bit
+                                  * as before                                                                  */
 #define PAI_OPT_PFB_READY 11     /* read-only: 1 when the public fixed-base tables are resident               */
 #define PAI_OPT_PFB_WINDOW 12    /* digit window of the public tables: 12, 16 or 20 (the windows pinned to the
                                   * reference's goldens; default 16: 324 rows of 512 B per element, 10.9 GB of

@@ -1,0 +1,73 @@
+#!/usr/bin/env python3
+"""Break-even inputs of the 1024-bit public fixed-base sampler (kernels_pfb1.hpp) on one device: a public-key-only
+party's 1M float32 elements under device RNG (device-resident buffers, warm, median of 5 calls after one discarded) on
+k_pe1_* (PAI_OPT_PUBLIC_FB = 1, the default) and on k_pfb1 (= 2) at the windows 12 and 16, with the stage times and
+the wall time of pai_ctx_public_fb_prepare (first build of the process, then a rebuild on pooled memory). One JSON line."""
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "ibond-flex_amd")]
+
+import torch  # noqa: E402
+
+
+def main():
+    from flex.crypto.paillier import _native as N
+    from flex.crypto.paillier.keypair import generate_paillier_keypair
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n = 1 << 20
+    pk, _ = generate_paillier_keypair(1024, seed=5)
+    x = torch.randn(n, dtype=torch.float32, device=dev)
+    ct = torch.empty((n, 64), dtype=torch.int32, device=dev)
+    ex = torch.empty(n, dtype=torch.int32, device=dev)
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    lib = N.load_library()
+    row = {"nb": 1024, "n": n, "device": torch.cuda.get_device_name(dev)}
+
+    def rate(c):
+        times = []
+        for _ in range(6):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rc = lib.pai_encrypt_dev(c.handle, N.PAI_F32, x.data_ptr(), n, 0, 0, N.PAI_OBF_RNG, None, 0, 0, bytes(32), 0,
+                                     ct.data_ptr(), ex.data_ptr(), st.data_ptr(), stream.cuda_stream)
+            assert rc == 0, lib.pai_last_error()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        ms = statistics.median(times[1:])
+        return {"ms": round(ms * 1e3, 2), "min_ms": round(min(times[1:]) * 1e3, 2), "max_ms": round(max(times[1:]) * 1e3, 2),
+                "encrypts_per_s": round(n / ms), "stages_ms": [round(v, 2) for v in c.stage_times()]}
+
+    c = N.Context(pk.n, 0)
+    c.set_stage_timing(True)
+    row["k_pe1"] = rate(c)
+    c.close()
+    for w in (12, 16):
+        c = N.Context(pk.n, 0)
+        c.set_public_fixed_base(2)
+        c.set_pfb_window(w)
+        c.set_stage_timing(True)
+        builds = []
+        for _ in range(2):
+            c.set_pfb_window(16 if w == 12 else 12)   # drops the tables
+            c.set_pfb_window(w)
+            t0 = time.perf_counter()
+            c.prepare_public_fixed_base()
+            builds.append(round(time.perf_counter() - t0, 4))
+        r = rate(c)
+        r["build_s"] = builds
+        _, K, W, _ = c.public_fixed_base_info()
+        r["rows"] = K << W
+        row[f"k_pfb1_w{w}"] = r
+        c.close()
+    print(json.dumps(row), flush=True)
+
+
+if __name__ == "__main__":
+    main()
