@@ -58,6 +58,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_mm.hpp"
 #include "engine_pip.hpp"
 #include "engine_sd.hpp"
+#include "engine_sdi.hpp"
 #include "engine_hist.hpp"
 #include "engine_shist.hpp"
 #include "engine_scan.hpp"
@@ -7454,6 +7455,143 @@ int pai_segment_add_idx_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_e
                             size_t total, const int64_t* d_seg_off, size_t nseg, uint32_t* d_out, int32_t* d_exp_out,
                             int64_t* d_bad, void* stream) {
   return segment_add_idx_dev(c, d_ct, d_exp, N, d_index, total, total, d_seg_off, nseg, d_out, d_exp_out, d_bad, stream);
+}
+
+// pai_segment_dot over device lists (kernels_sdi.hpp). Level 0 of the tree of segment_add_idx_dev is k_sdi_rows: the rows
+// of k_seg_rows, asked for without an index so that they name POSITIONS of the lists, become the partial products P (the
+// non-negative terms) and N (the magnitudes of the negative ones) of at most 16 entries, both at the row's E. The levels
+// above reduce the P rows and the N rows with the same gather rows (two k_add launches per level; a row's exponent is
+// the same in both trees). The segments' N are inverted by one batch inversion without a host step, P N^-1 is a 2-way
+// k_add at equal exponents, and k_sdi_out hands the sums out unless a check word or the inversion's word is set.
+int pai_segment_dot_idx_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_index,
+                            size_t total, const int64_t* d_seg_off, size_t nseg, int dtype, const void* d_x,
+                            uint32_t* d_out, int32_t* d_exp_out, int32_t* d_status, int64_t* d_bad, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (!d_bad || !d_seg_off || dtype < 0 || dtype > 2) return fail(PAI_ERR_ARG, "pai_segment_dot_idx_dev: bad arguments");
+  if ((nseg > 0 && (!d_out || !d_exp_out)) || (total > 0 && (!d_index || !d_ct || !d_exp || !d_x)))
+    return fail(PAI_ERR_ARG, "pai_segment_dot_idx_dev: null pointer");
+  if (N >= ((size_t)1 << 40) || total >= ((size_t)1 << 40) || nseg >= ((size_t)1 << 30) ||
+      total / SEG_CHUNK + nseg >= ((size_t)1 << 31))
+    return fail(PAI_ERR_ARG, "pai_segment_dot_idx_dev: too many rows");
+  const size_t W = c->ct_words, esz = dtype == PAI_F32 ? 4 : 8, nst = d_status ? total * 4 : 0;
+  if (W > MODINV_MAX_WORDS) return fail(PAI_ERR_KEY, "pai_segment_dot_idx_dev: keys above 4096 bits are not supported");
+  const struct { const void* p; size_t n; } in[] = {{d_ct, N * W * 4}, {d_exp, N * 4}, {d_index, total * 8},
+                                                    {d_seg_off, (nseg + 1) * 8}, {d_x, total * esz}, {d_bad, 32}},
+                                            out[] = {{d_out, nseg * W * 4}, {d_exp_out, nseg * 4}, {d_status, nst}};
+  for (const auto& o : out)
+    for (const auto& i : in)
+      if (i.n && o.n && ranges_overlap(i.p, i.n, o.p, o.n))
+        return fail(PAI_ERR_ARG, "pai_segment_dot_idx_dev: the output overlaps the input");
+  if ((nseg && ranges_overlap(d_out, nseg * W * 4, d_exp_out, nseg * 4)) ||
+      (nseg && nst && (ranges_overlap(d_out, nseg * W * 4, d_status, nst) || ranges_overlap(d_exp_out, nseg * 4, d_status, nst))) ||
+      (total && (ranges_overlap(d_bad, 32, d_index, total * 8) || ranges_overlap(d_bad, 32, d_x, total * esz))) ||
+      ranges_overlap(d_bad, 32, d_seg_off, (nseg + 1) * 8))
+    return fail(PAI_ERR_ARG, "pai_segment_dot_idx_dev: the output overlaps the input");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(d_bad, 0xFF, 32, st));
+  CheckIdxParams cp{(const long long*)d_index, (long long)total, 0, (long long)N, (const long long*)d_seg_off,
+                    (long long)nseg, (unsigned long long*)d_bad};
+  HIPCHK(check_idx_launch(cp, c->cus, st));
+  if (nseg == 0) return 0;
+  const int C = SEG_CHUNK;
+  int levels = 1;
+  for (size_t cap = C; cap < total; cap *= C) ++levels;
+  const size_t P = total / C + nseg;   // no level has more rows
+  // scratch: [P rows | N rows] x 2, their exponents x 2, the segments' [P | N] and exponents, P N^-1, statuses, plan
+  size_t o = 0;
+  size_t o_part[2][2], o_pe[2];
+  for (int b = 0; b < 2; ++b)
+    for (int s = 0; s < 2; ++s) o_part[b][s] = o, o = align16(o + P * W * 4);
+  for (int b = 0; b < 2; ++b) o_pe[b] = o, o = align16(o + P * 4);
+  const size_t o_fin = o, o_fe = align16(o_fin + 2 * nseg * W * 4), o_prod = align16(o_fe + 2 * nseg * 4),
+               o_pre = align16(o_prod + nseg * W * 4), o_st = align16(o_pre + nseg * 4),
+               o_off = align16(o_st + std::max<size_t>(total, 1) * 4),
+               o_g = align16(o_off + (size_t)(levels - 1) * (nseg + 1) * 8), need = align16(o_g + std::max(P, nseg) * C * 8);
+  int rc = ensure_buf(&c->d_seg, &c->seg_bytes, need);
+  if (rc) return rc;
+  char* b = (char*)c->d_seg;
+  uint32_t* fin = (uint32_t*)(b + o_fin);
+  int32_t* fe = (int32_t*)(b + o_fe);
+  long long* d_off = (long long*)(b + o_off);
+  long long* d_g = (long long*)(b + o_g);
+  const long long* gate = (const long long*)d_bad;
+  if (levels > 1) {
+    SegPlanParams sp{(const long long*)d_seg_off, (long long)nseg, levels, d_off, gate};
+    HIPCHK(seg_offsets_launch(sp, st));
+  }
+  size_t cap = total;   // bound on the rows that enter level k, without the nseg term
+  for (int k = 0; k < levels; ++k) {
+    const bool last = k == levels - 1;
+    cap /= C;
+    const long long rows = last ? (long long)nseg : (long long)(cap + nseg);
+    SegRowsParams rp{};
+    rp.in_off = k == 0 ? (const long long*)d_seg_off : d_off + (size_t)(k - 1) * (nseg + 1);
+    rp.index = nullptr;
+    rp.out_off = last ? nullptr : d_off + (size_t)k * (nseg + 1);
+    rp.nseg = (long long)nseg;
+    rp.rows = rows;
+    rp.gidx = d_g;
+    rp.gate = gate;
+    HIPCHK(seg_rows_launch(rp, c->cus, st));
+    uint32_t* oP = last ? fin : (uint32_t*)(b + o_part[k & 1][0]);
+    uint32_t* oN = last ? fin + nseg * W : (uint32_t*)(b + o_part[k & 1][1]);
+    int32_t* oe = last ? fe : (int32_t*)(b + o_pe[k & 1]);
+    if (k == 0) {
+      SdiRowsParams p{};
+      p.ct = d_ct;
+      p.exp = d_exp;
+      p.index = (const long long*)d_index;
+      p.x = d_x;
+      p.dtype = dtype;
+      p.gidx = d_g;
+      p.rows = rows;
+      p.outP = oP;
+      p.outN = oN;
+      p.pexp = oe;
+      p.pexp2 = last ? fe + nseg : nullptr;
+      p.status = (int32_t*)(b + o_st);
+      p.bad = (unsigned long long*)d_bad;
+      p.gate = gate;
+      p.N = c->d_N;
+      p.R2 = c->d_R2;
+      p.oneR = c->d_oneR;
+      p.mprime = c->mprime_N;
+      p.ct_words = c->ct_words;
+      HIPCHK(sdi_rows_launch(c->tpi_e, p, c->cus, st));
+      continue;
+    }
+    const int32_t* ie = (const int32_t*)(b + o_pe[(k - 1) & 1]);
+    AddParams ap = add_params((const uint32_t*)(b + o_part[(k - 1) & 1][0]), ie, C, rows, oP, oe, d_g);
+    ap.gate = gate;
+    if ((rc = run_add(c, ap, st))) return rc;
+    AddParams an = add_params((const uint32_t*)(b + o_part[(k - 1) & 1][1]), ie, C, rows, oN, last ? fe + nseg : oe, d_g);
+    an.gate = gate;
+    if ((rc = run_add(c, an, st))) return rc;
+  }
+  SdiFinParams fp{};
+  fp.gate = gate;
+  fp.nrows = fin + nseg * W;
+  fp.prod = (const uint32_t*)(b + o_prod);
+  fp.pexp = (const int32_t*)(b + o_pre);
+  fp.st = (const int32_t*)(b + o_st);
+  fp.nseg = (long long)nseg;
+  fp.total = (long long)total;
+  fp.W = (int)W;
+  fp.out = d_out;
+  fp.out_exp = d_exp_out;
+  fp.status = d_status;
+  fp.bad = (long long*)d_bad;
+  HIPCHK(sdi_fill_launch(fp, c->cus, st));
+  uint32_t* word = nullptr;
+  if ((rc = batch_invert_async(c, fin + nseg * W, (long long)nseg, st, inv_mod_n2(c), &word))) return rc;
+  AddParams mp = add_params(fin, fe, 2, (long long)nseg, (uint32_t*)(b + o_prod), (int32_t*)(b + o_pre));
+  mp.gate = gate;
+  if ((rc = run_add(c, mp, st))) return rc;
+  fp.noinv = word;
+  HIPCHK(sdi_out_launch(fp, c->cus, st));
+  return 0;
 }
 
 // The wire-ingest range check on the device (k_check_below): one read-back of one word.

@@ -62,7 +62,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_obfuscate", "pai_obfuscate_dev",
             "pai_pack_max_slots", "pai_encrypt_packed", "pai_encrypt_packed_dev", "pai_decrypt_packed",
             "pai_decrypt_packed_dev", "pai_pack_ciphertexts", "pai_pack_ciphertexts_dev", "pai_repack", "pai_repack_dev",
-            "pai_segment_dot", "pai_segment_dot_dev", "pai_histogram", "pai_histogram_dev",
+            "pai_segment_dot", "pai_segment_dot_dev", "pai_segment_dot_idx_dev", "pai_histogram", "pai_histogram_dev",
             "pai_histogram_cols", "pai_histogram_cols_dev",
             "pai_histogram_sparse", "pai_histogram_sparse_dev",
             "pai_cumsum", "pai_cumsum_dev",
@@ -74,6 +74,7 @@ MODINV = ("pai_neg", "pai_neg_dev", "pai_debug_modinv", "pai_debug_modinv_info")
 BIG = tuple(n for n in EXPORTED if "_big" in n)     # PAI_BIG operands (include/flexpai.h)
 RESIDENT = EXPORTED[-11:-2]   # device-resident buffers (include/flexpai.h)
 DEVICE_INDEX = EXPORTED[-2:]  # take and segment sums over index lists that are device memory
+SEGDOT_INDEX = ("pai_segment_dot_idx_dev",)   # segmented weighted sums over device lists and weights
 PAI_COMM_ID_BYTES = 128
 
 _lib = None
@@ -195,6 +196,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         if device_index:
             lib.pai_take_idx_dev.argtypes = [P, P, P, S, P, S, I, P, P, P, P]
             lib.pai_segment_add_idx_dev.argtypes = [P, P, P, S, P, S, P, S, P, P, P, P]
+        segdot_index = hasattr(lib, "pai_segment_dot_idx_dev")
+        if segdot_index:
+            lib.pai_segment_dot_idx_dev.argtypes = [P, P, P, S, P, S, P, S, I, P, P, P, P, P, P]
         big = hasattr(lib, "pai_mul_big")    # (absent from a library built from an earlier commit)
         if big:
             lib.pai_encrypt_big.argtypes = [P, P, P, S, S, I, P, S, S, P, U64, P, P, P]
@@ -203,7 +207,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.pai_mul_big_dev.argtypes = lib.pai_add_plain_big_dev.argtypes = [P, P, P, S, P, P, S, S, P, P, P, P]
         for name in EXPORTED:
             if (not resident and name in RESIDENT) or (not device_index and name in DEVICE_INDEX) or (not big and name in BIG) or \
-                    (not modinv and name in MODINV):
+                    (not modinv and name in MODINV) or (not segdot_index and name in SEGDOT_INDEX):
                 continue
             if name not in ("pai_ctx_destroy", "pai_last_error", "pai_comm_destroy", "pai_release_table_cache"):
                 getattr(lib, name).restype = ctypes.c_int
@@ -790,6 +794,14 @@ class Context:
         d_bad names two device int64 words (the smallest bad index position, the smallest bad offset position, or -1)."""
         self.dev_call("pai_segment_add_idx_dev", d_ct, d_exp, int(N), d_index, int(total), d_seg_off, int(nseg), d_out,
                       d_exp_out, d_bad)
+
+    def segment_dot_idx_dev(self, d_ct: int, d_exp: int, N: int, d_index: int, total: int, d_seg_off: int, nseg: int,
+                            dtype: int, d_x: int, d_out: int, d_exp_out: int, d_status: int, d_bad: int) -> None:
+        """pai_segment_dot_idx_dev: per-segment weighted sums over an int64 index, nseg + 1 int64 offsets and `total`
+        scalars in device memory; d_bad names four device int64 words (bad index position, bad offset position, 1 for a
+        ciphertext without inverse under a negative scalar, the first scalar that does not encode; -1 each when fine)."""
+        self.dev_call("pai_segment_dot_idx_dev", d_ct, d_exp, int(N), d_index, int(total), d_seg_off, int(nseg), int(dtype),
+                      d_x, d_out, d_exp_out, d_status, d_bad)
 
     def check_below_dev(self, d_ct: int, N: int) -> int:
         """pai_check_below_dev: the smallest i with ct[i] >= n^2, or -1."""

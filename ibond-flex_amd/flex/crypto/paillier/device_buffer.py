@@ -306,6 +306,24 @@ def segment_dot_dev(pk, words: DeviceWords, exps, idx: np.ndarray, off: np.ndarr
     return out, oe, st.download(np.int32, idx.size)
 
 
+def segment_dot_idx_dev(pk, words: DeviceWords, exps, idx: DeviceArray, off: DeviceArray, x: DeviceArray):
+    """pai_segment_dot_idx_dev over DeviceArrays (int64 lists, float32 / float64 / int64 weights): (words [nseg, W],
+    exponents, statuses [total] on the device, the four check words on the host). Nothing goes up; the 32 bytes of the
+    check words come down."""
+    (N, W), dev = words.shape, words.device
+    if idx.device != dev or off.device != dev or x.device != dev:
+        raise ValueError(f"the buffer lives on device {dev}, the lists and weights on devices {idx.device}, "
+                         f"{off.device} and {x.device}")
+    ctx = context_on(pk, dev)
+    ex = _exp_mem(exps, N, dev)
+    nseg = off.size - 1
+    out, oe, st = DeviceWords.empty(nseg, W, dev), _i32(dev, nseg), _i32(dev, max(idx.size, 1))
+    bad = _native.DeviceMem(32, dev)
+    ctx.segment_dot_idx_dev(words.ptr, ex.ptr, N, idx.ptr, idx.size, off.ptr, nseg, _native.scalar_dtype(x), x.ptr,
+                            out.ptr, oe.ptr, st.ptr, bad.ptr)
+    return out, oe, st, tuple(int(v) for v in bad.download(np.int64, 4))
+
+
 def histogram_resident_args(N: int, bins, n_bins, node, n_nodes):
     """histogram_args when bins or node is a DeviceArray: what the host can check of a resident operand is its dtype and
     its shape (uint8 / uint16 C-contiguous [N, F]; int32 [N]); its values are the kernel's business (a node id outside
@@ -680,7 +698,20 @@ class DeviceCiphertextBuffer(BufferOps):
         return self._like(out, self._ex)
 
     def segment_dot(self, index, seg_off, weights) -> "DeviceCiphertextBuffer":
-        """CiphertextBuffer.segment_dot on the device (pai_segment_dot_dev)."""
+        """CiphertextBuffer.segment_dot on the device (pai_segment_dot_dev). When index, seg_off and weights are all
+        DeviceArrays (int64 lists; float32, float64 or int64 weights, on the buffer's device) the call is
+        pai_segment_dot_idx_dev: the lists and weights are read where they are, nothing waits on the host but the 32 bytes
+        of the device-side checks, which raise what the host-list call raises, and the bits are the host-list call's.
+        Nothing goes up unless a segment is empty (its exponent becomes 0 here, so the nseg exponents go back up). A mix
+        of host and device operands is a TypeError."""
+        ops = (("index", index), ("seg_off", seg_off), ("weights", weights))
+        resident = [isinstance(v, DeviceArray) for _, v in ops]
+        if any(resident):
+            if not all(resident):
+                name = next(n for (n, _), r in zip(ops, resident) if not r)
+                raise TypeError(f"segment_dot: {name} is a host array while another operand is a DeviceArray; pass all "
+                                f"three on the device (device_array) or all three on the host")
+            return self._segment_dot_resident(index, seg_off, weights)
         idx, off, w = segment_dot_args(self.size, index, seg_off, weights)
         out, oe, st = segment_dot_dev(self.public_key, self.words, self._ex, idx, off, w)
         bad = np.flatnonzero(st)
@@ -690,6 +721,39 @@ class DeviceCiphertextBuffer(BufferOps):
         nseg = off.size - 1
         e = np.where(np.diff(off) == 0, 0, oe.download(np.int32, nseg)).astype(np.int32)
         return self._like(out, e, 0, (nseg,))
+
+    def _segment_dot_resident(self, idx: DeviceArray, off: DeviceArray, w: DeviceArray) -> "DeviceCiphertextBuffer":
+        for name, a in (("index", idx), ("seg_off", off)):
+            if a.dtype != np.int64:
+                raise TypeError(f"segment_dot: a device {name} must be int64, not {a.dtype}")
+        if w.dtype not in (np.float32, np.float64, np.int64):
+            raise TypeError(f"segment_dot: unsupported device weight dtype {w.dtype}")
+        if idx.ndim != 1 or off.ndim != 1 or w.ndim != 1:
+            raise ValueError("segment_dot: index, seg_off and weights must be one-dimensional")
+        if off.size < 1:
+            raise ValueError("segment_dot: seg_off must start at 0 and must not decrease")
+        if w.size != idx.size:
+            raise ValueError(f"segment_dot: {idx.size} indices, {w.size} weights")
+        nseg = off.size - 1
+        out, oe, _, (bad_idx, bad_off, noinv, bad_w) = segment_dot_idx_dev(self.public_key, self.words, self._ex, idx, off, w)
+        if bad_off >= 0:              # the error paths may look: what they need comes down for the host check's message
+            h = off.to_host()
+            if h[0] != 0 or np.any(np.diff(h) < 0):
+                raise ValueError("segment_dot: seg_off must start at 0 and must not decrease")
+            raise ValueError(f"segment_dot: {idx.size} indices, {w.size} weights, seg_off ends at {int(h[-1])}")
+        if bad_idx >= 0:
+            raise IndexError(f"segment_dot: index out of range for {self.size} ciphertexts")
+        if bad_w >= 0:                # the host-list call refuses such a weight before it calls the library: same order
+            v = w.mem.download(w.dtype, 1, offset=bad_w * w.dtype.itemsize)[0]
+            raise (OverflowError if np.isinf(v) else ValueError)(
+                f"segment_dot: weight {v!r} at index {bad_w} does not encode")
+        if noinv >= 0:
+            raise ZeroDivisionError("invert() no inverse exists")
+        e = oe.download(np.int32, nseg)
+        if not np.any(e == EMPTY_EXP):
+            return self._like(out, oe, 0, (nseg,))       # the exponents stay where the call wrote them
+        # an empty segment's exponent is 0 in this layer: the fixed exponents go back up, as after segment_sum
+        return self._like(out, np.where(e == EMPTY_EXP, 0, e).astype(np.int32), 0, (nseg,))
 
     def _dense_dot(self, m: int, xs: np.ndarray, d: int, shape):
         out, oe = matmul_dev(self.public_key, self.words, self._ex, m, self.shape[-1], xs, d)

@@ -687,6 +687,28 @@ int pai_take_idx_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, s
 int pai_segment_add_idx_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_index,
                             size_t total, const int64_t* d_seg_off, size_t nseg, uint32_t* d_out, int32_t* d_exp_out,
                             int64_t* d_bad, void* stream);
+/* pai_segment_dot_dev for lists AND scalars that are device memory (csrc/kernels_sdi.hpp): out_s = the sum
+ * over segment s of ct[index[t]] * x[t]. d_index, d_seg_off and `total` as above; d_x holds `total` scalars of `dtype`
+ * (PAI_F32 / PAI_F64 / PAI_I64); d_status (nullable) receives `total` statuses, those of pai_mul. For valid lists d_out,
+ * d_exp_out and d_status equal pai_segment_dot_dev's for the same lists bit for bit: an empty segment is ciphertext 1 with
+ * exponent INT32_MIN, a stored zero counts towards its segment's exponent, a scalar that does not encode contributes the
+ * factor 1 at the exponent pai_mul gives it, with its status set.
+ * The contract is that of pai_segment_add_idx_dev (check kernel first, every kernel behind it gated, outputs untouched
+ * and PAI_OK on bad lists, no host wait, no copy to the host, scratch from the context sized from total and nseg alone,
+ * the same PAI_ERR_ARG cases and bounds, dtype outside 0 .. 2 among them; PAI_ERR_KEY for keys above 4096 bits), with
+ * d_bad naming FOUR device int64 words:
+ *     d_bad[0], d_bad[1]  as above;
+ *     d_bad[2]  1 when a ciphertext that meets a negative scalar has no inverse mod n^2 (what pai_segment_dot_dev
+ *               reports as PAI_ERR_NOINV and pai_neg_dev in its status word), or -1. Nothing can end the call for it
+ *               without a host wait, so it is reported here, and d_out, d_exp_out and d_status are then UNTOUCHED;
+ *     d_bad[3]  the smallest position t whose scalar does not encode (d_status[t] != 0), or -1: the any-flag that tells
+ *               a caller whether the statuses are worth a download. The outputs are written all the same.
+ * No ciphertext is inverted on its own and none is numbered: a row of at most 16 entries keeps the product of its
+ * non-negative terms and the product of the magnitudes of its negative ones, the two are reduced by the tree of
+ * pai_segment_add_idx_dev, and one batch inversion over the nseg negative products precedes the final product. */
+int pai_segment_dot_idx_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, const int64_t* d_index,
+                            size_t total, const int64_t* d_seg_off, size_t nseg, int dtype, const void* d_x,
+                            uint32_t* d_out, int32_t* d_exp_out, int32_t* d_status, int64_t* d_bad, void* stream);
 
 /* Packed plaintexts: many signed fixed-point values per ciphertext (no reference counterpart; opt-in, both peers must
  * be flexpai; csrc/kernels_pack.hpp). Every packed ciphertext is an ordinary reference ciphertext

@@ -15,12 +15,25 @@ case (1 = term path, 2 = fused). Writes the times, their spread, the ratios and 
 bit-identical to profiles/segdot_ab.json (--out) after every case, and prints each row.
 
     python tools/segdot_ab.py [--rounds 3] [--bits 1024,2048] [--quick] [--no-dense] [--out profiles/segdot_ab.json]
+
+--idx: the device-list route instead, for a caller whose index, offsets and weights are device memory (the same cases,
+--max-nnz drops the larger ones):
+i = pai_segment_dot_idx_dev on the lists where they are (kernels_sdi.hpp); "enqueue_ms" is the host time until the call
+    has returned, before anything is waited for,
+f = what that caller did before: index, offsets and weights come down (three torch .cpu() copies), then
+    pai_segment_dot_dev on its fused path,   t = the same on its term path.
+Wall times of a host clock around each side, ending in a stream synchronise (f and t work on the host in between, which
+is part of what they cost); one warm-up call per side, then --rounds rounds that alternate the sides. Writes the medians,
+the spread and whether i equals f and t bit for bit to profiles/segdot_idx_ab.json (--out).
+
+    python tools/segdot_ab.py --idx [--rounds 5] [--bits 1024,2048] [--max-nnz 262144] [--quick]
 """
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "ibond-flex_amd")]
@@ -58,14 +71,116 @@ def cases(quick):
     yield "csc_2pct", K, idx, off, np.nonzero(mask)[0].astype(np.int64)   # the entries' columns
 
 
+def idx_ab(args):
+    os.environ["FLEXPAI_SD_ALWAYS"] = "1"
+    from flex.crypto.paillier import _native as N
+    with open(os.path.join(ROOT, "tests", "golden", "paillier_golden.json")) as f:
+        keys = json.load(f)["keys"]
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    stream = torch.cuda.current_stream(dev)
+    lib = N.load_library(N.XCHECK_LIB_PATH)
+    plib = N.load_library(N.LIB_PATH)
+    result = {"i_kind": "pai_segment_dot_idx_dev, lists and weights on the device",
+              "f_kind": "index, offsets, weights downloaded, then pai_segment_dot_dev fused (test build, every call fused)",
+              "t_kind": "the same downloads, then pai_segment_dot_dev with PAI_OPT_SEGDOT_FUSED = 0",
+              "clock": "time.perf_counter around the side, ending in a stream synchronise", "rounds": args.rounds,
+              "device": torch.cuda.get_device_name(dev), "cases": []}
+
+    def save():
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+    for nb in (int(v) for v in args.bits.split(",")):
+        n = int(keys[str(nb)]["n"], 16)
+        ctx = N.Context(n, 0, lib=lib)
+        pctx = N.Context(n, 0, lib=plib)
+        W = ctx.ct_words
+        for name, U, idx, off, _ in cases(args.quick):
+            nnz, nseg = idx.size, off.size - 1
+            if args.max_nnz and nnz > args.max_nnz:
+                continue
+            g = torch.Generator(device=dev).manual_seed(nb + nnz)
+            ct = torch.randint(0, 2 ** 31 - 1, (U, W), dtype=torch.int32, device=dev, generator=g)
+            ct[:, W - 1] = 0                                   # < 2^(32 (W - 1)) < n^2
+            ex = torch.randint(12, 15, (U,), dtype=torch.int32, device=dev, generator=g)
+            x = torch.randn(nnz, dtype=torch.float64, device=dev, generator=g)
+            d_idx, d_off = torch.from_numpy(idx).to(dev), torch.from_numpy(off).to(dev)
+            bad = torch.zeros(4, dtype=torch.int64, device=dev)
+            outs = {s: (torch.empty((nseg, W), dtype=torch.int32, device=dev),
+                        torch.empty(nseg, dtype=torch.int32, device=dev)) for s in "ift"}
+            enq = []
+
+            def chk(rc):
+                assert rc == 0, lib.pai_last_error()
+
+            def run(s):
+                o, oe = outs[s]
+                if s == "i":
+                    t0 = time.perf_counter()
+                    chk(lib.pai_segment_dot_idx_dev(ctx.handle, ct.data_ptr(), ex.data_ptr(), U, d_idx.data_ptr(), nnz,
+                                                    d_off.data_ptr(), nseg, N.PAI_F64, x.data_ptr(), o.data_ptr(),
+                                                    oe.data_ptr(), None, bad.data_ptr(), stream.cuda_stream))
+                    enq.append((time.perf_counter() - t0) * 1e3)
+                    return
+                h_idx, h_off, _h_x = d_idx.cpu().numpy(), d_off.cpu().numpy(), x.cpu().numpy()
+                ctx.set_segdot_fused(s == "f")
+                chk(lib.pai_segment_dot_dev(ctx.handle, ct.data_ptr(), ex.data_ptr(), U, h_idx.ctypes.data, h_off.ctypes.data,
+                                            nseg, N.PAI_F64, x.data_ptr(), o.data_ptr(), oe.data_ptr(), None,
+                                            stream.cuda_stream))
+                assert ctx.segdot_path == (2 if s == "f" else 1)
+
+            def timed(s):
+                stream.synchronize()
+                t0 = time.perf_counter()
+                run(s)
+                stream.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+
+            for s in "ift":
+                timed(s)                                       # warm-up: buffers, code objects
+            assert bad.cpu().tolist()[:3] == [-1, -1, -1]
+            del enq[:]
+            ms = {s: [] for s in "ift"}
+            for _ in range(args.rounds):
+                for s in "ift":
+                    ms[s].append(timed(s))
+            row = {"nb": nb, "case": name, "distinct": U, "nnz": int(nnz), "nseg": int(nseg), "reuse": round(nnz / U, 2),
+                   "rows": int(sum(-(-int(v) // 16) for v in np.diff(off))),
+                   "identical": bool(all(torch.equal(outs["i"][k], outs[s][k]) for s in "ft" for k in (0, 1)))}
+            chk(plib.pai_segment_dot_dev(pctx.handle, ct.data_ptr(), ex.data_ptr(), U, idx.ctypes.data, off.ctypes.data,
+                                         nseg, N.PAI_F64, x.data_ptr(), outs["t"][0].data_ptr(), outs["t"][1].data_ptr(),
+                                         None, stream.cuda_stream))
+            row["default_path"] = pctx.segdot_path             # what the product library's dispatch takes: 1 term, 2 fused
+            for s in "ift":
+                med = statistics.median(ms[s])
+                row[s] = {"ms": [round(v, 3) for v in ms[s]], "median_ms": round(med, 3),
+                          "spread": round((max(ms[s]) - min(ms[s])) / med, 4)}
+            row["i"]["enqueue_median_ms"] = round(statistics.median(enq), 3)
+            for s in "ft":
+                row[s + "_over_i"] = round(row[s]["median_ms"] / row["i"]["median_ms"], 3)
+            result["cases"].append(row)
+            save()
+            print(json.dumps(row), flush=True)
+            del ct, ex, x, outs
+        del ctx, pctx
+    save()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--bits", default="1024,2048")
     ap.add_argument("--quick", action="store_true", help="two small cases: a smoke run of the tool")
     ap.add_argument("--no-dense", action="store_true", help="skip the densified pai_matmul_dev of csc_2pct")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "segdot_ab.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--idx", action="store_true", help="the device-list route against download + pai_segment_dot_dev")
+    ap.add_argument("--max-nnz", type=int, default=0, help="--idx: skip the cases with more entries (0: none)")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "segdot_idx_ab.json" if args.idx else "segdot_ab.json")
+    if args.idx:
+        return idx_ab(args)
     os.environ["FLEXPAI_SD_ALWAYS"] = "1"
     from flex.crypto.paillier import _native as N
     with open(os.path.join(ROOT, "tests", "golden", "paillier_golden.json")) as f:
