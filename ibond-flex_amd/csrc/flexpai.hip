@@ -56,6 +56,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_inv.hpp"
 #include "engine_big.hpp"
 #include "engine_mm.hpp"
+#include "engine_mulb.hpp"
 #include "engine_pip.hpp"
 #include "engine_sd.hpp"
 #include "engine_sdi.hpp"
@@ -313,6 +314,11 @@ struct pai_ctx {
   void* d_mminv = nullptr;      // copy of the ciphertexts with the flagged rows' inverted (only with negative scalars)
   size_t mminv_bytes = 0;
   std::vector<uint8_t> mm_neg, mm_flags;   // host sides of neg_row and of the flags
+  // broadcast multiply (kernels_mulb.hpp): PAI_OPT_MUL_BCAST / PAI_OPT_MUL_BCAST_PATH; the combs live in d_mmtab
+  int mulb_mode = 1;            // 0 term path, 1 automatic, 2 comb
+  int mulb_path = 0;            // last pai_mul_bcast[_dev] call: 0 none yet, 1 term path, 2 comb
+  void* d_mulb = nullptr;       // per call: |M| [N F], the rows' window counts [N]
+  size_t mulb_bytes = 0;
   // segmented weighted sums (kernels_sd.hpp): PAI_OPT_SEGDOT_FUSED / PAI_OPT_SEGDOT_PATH
   bool sd_fused = true;
   int sd_path = 0;              // last pai_segment_dot[_dev] call: 0 none yet, 1 term path, 2 fused
@@ -443,6 +449,7 @@ pai_ctx::~pai_ctx() {
   if (d_work) (void)hipFree(d_work);
   if (d_mul) (void)hipFree(d_mul);
   if (d_mmtab) (void)hipFree(d_mmtab);
+  if (d_mulb) (void)hipFree(d_mulb);
   if (d_mmwork) (void)hipFree(d_mmwork);
   if (d_mminv) (void)hipFree(d_mminv);
   if (d_pip) (void)hipFree(d_pip);
@@ -2302,6 +2309,11 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       return 0;
     case PAI_OPT_MATMUL_FUSED: c->mm_fused = value != 0; return 0;
     case PAI_OPT_MATMUL_BUCKET: c->mm_bucket = value != 0; return 0;
+    case PAI_OPT_MUL_BCAST:
+      if (value < 0 || value > 2) return fail(PAI_ERR_ARG, "PAI_OPT_MUL_BCAST must be 0, 1 or 2");
+      c->mulb_mode = value;
+      return 0;
+    case PAI_OPT_MUL_BCAST_PATH: return fail(PAI_ERR_ARG, "PAI_OPT_MUL_BCAST_PATH is read-only");
     case PAI_OPT_INV_DEVICE: c->inv_device = value != 0; return 0;
     case PAI_OPT_SEGDOT_FUSED: c->sd_fused = value != 0; return 0;
     case PAI_OPT_POOL_FUSED: c->pool.fused = value != 0; return 0;
@@ -2360,6 +2372,8 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_CRT4_MIN: *value = (int)std::min<long long>(c->crt4_min, INT32_MAX); return 0;
     case PAI_OPT_MATMUL_FUSED: *value = c->mm_fused ? 1 : 0; return 0;
     case PAI_OPT_MATMUL_BUCKET: *value = c->mm_bucket ? 1 : 0; return 0;
+    case PAI_OPT_MUL_BCAST: *value = c->mulb_mode; return 0;
+    case PAI_OPT_MUL_BCAST_PATH: *value = c->mulb_path; return 0;
     case PAI_OPT_INV_DEVICE: *value = c->inv_device ? 1 : 0; return 0;
     case PAI_OPT_MATMUL_PATH: *value = c->mm_path; return 0;
     case PAI_OPT_SEGDOT_FUSED: *value = c->sd_fused ? 1 : 0; return 0;
@@ -4535,6 +4549,124 @@ int pai_mul_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N
   return batch_invert(c, d_out, (const uint8_t*)c->d_mul, (long long)N, st);
 }
 
+// Which pai_mul_bcast[_dev] calls take the comb under PAI_OPT_MUL_BCAST = 1. Counted in Montgomery products mod n^2 a
+// k_mul chain costs about 14 + 60 + 15 = 89 per output and the comb about 60 + 16 * 14 = 284 per ciphertext plus at
+// most 15 per output: the counts cross near F = 4. Measured on an MI355X (tools/mulb_ab.py, profiles/mulb_ab.json,
+// DESIGN.md section 5; N = 4096 ciphertexts, F in 2, 4, 8, 16, 64, 256) the crossing lies higher, because a wave of the
+// comb serves 64 / TPI columns of ONE row and is mostly idle at small F: term / comb = 0.91 at F = 16 and 1.44 at F = 64
+// with 1024-bit keys, 1.05 and 1.67 at 2048, 1.02 and 1.60 at 4096 (N = 512). F = 64 is the smallest measured F at which
+// the comb wins beyond the repeats' spread at both 1024 and 2048 bits.
+constexpr size_t MULB_MIN_F = 64;
+
+static size_t mm_table_budget();
+
+static bool mulb_take_comb(const pai_ctx* c, size_t F) {
+  return c->mulb_mode == 2 || (c->mulb_mode == 1 && F >= MULB_MIN_F);
+}
+
+// The comb path of pai_mul_bcast_dev (kernels_mulb.hpp) without the closing inversion: k_mulb_plan encodes the scalars
+// once, then blocks of as many ciphertexts as the table budget holds (the matrix product's buffer and budget) build
+// their combs and multiply. Every output is a canonical residue, so the bits do not depend on the blocks.
+static int mul_bcast_comb(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int dtype, const void* d_x,
+                          size_t F, uint32_t* d_out, int32_t* d_exp_out, int32_t* d_status, uint8_t* neg, hipStream_t st) {
+  const size_t T = N * F, eb = mulb_entry_bytes(c->tpi_e);
+  const size_t o_top = align16(T * 8);
+  int rc = ensure_buf(&c->d_mulb, &c->mulb_bytes, o_top + N * 4);
+  if (rc) return rc;
+  char* base = (char*)c->d_mulb;
+  MulbPlanParams pp{};
+  pp.exp = d_exp;
+  pp.x = d_x;
+  pp.dtype = dtype;
+  pp.N = (long long)N;
+  pp.F = (long long)F;
+  pp.mag = (uint64_t*)base;
+  pp.exp_out = d_exp_out;
+  pp.status = d_status;
+  pp.neg = neg;
+  pp.rowtop = (int32_t*)(base + o_top);
+  HIPCHK(mulb_plan_launch(pp, c->cus, st));
+  const size_t nb = std::min(N, std::max<size_t>(mm_table_budget() / eb, 1));
+  if ((rc = ensure_buf(&c->d_mmtab, &c->mmtab_bytes, nb * eb))) return rc;
+  for (size_t i0 = 0; i0 < N; i0 += nb) {
+    MulbTabParams tp{};
+    tp.ct = d_ct;
+    tp.rowtop = pp.rowtop;
+    tp.i0 = (long long)i0;
+    tp.nb = (long long)std::min(nb, N - i0);
+    tp.tab = (uint32_t*)c->d_mmtab;
+    tp.N = c->d_N;
+    tp.R2 = c->d_R2;
+    tp.oneR = c->d_oneR;
+    tp.mprime = c->mprime_N;
+    tp.ct_words = c->ct_words;
+    HIPCHK(mulb_tab_launch(c->tpi_e, tp, c->cus, st));
+    MulbAccParams ap{};
+    ap.mag = pp.mag;
+    ap.rowtop = pp.rowtop;
+    ap.F = (long long)F;
+    ap.i0 = tp.i0;
+    ap.nb = tp.nb;
+    ap.tab = tp.tab;
+    ap.out = d_out;
+    ap.N = c->d_N;
+    ap.oneR = c->d_oneR;
+    ap.mprime = c->mprime_N;
+    ap.ct_words = c->ct_words;
+    HIPCHK(mulb_acc_launch(c->tpi_e, ap, c->cus, st));
+  }
+  return 0;
+}
+
+// pai_mul_bcast_dev below its argument checks, on the path the caller chose: out[i][j] = ct_i (x) x[i][j]. The term path
+// is k_mul over (i, j) with the scalar index i F + j and the ciphertext index i: nothing is replicated, and the bits are
+// those of pai_mul over the replicated array. Both paths flag the outputs of negative scalars and close with ONE batch
+// inversion over the N F outputs (invert(c)^|M| = invert(c^|M|)), where a ciphertext without inverse ends the call.
+static int mul_bcast_run(pai_ctx* c, bool comb, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int dtype,
+                         const void* d_x, size_t F, uint32_t* d_out, int32_t* d_exp_out, int32_t* d_status,
+                         hipStream_t st) {
+  const size_t T = N * F;
+  int rc = ensure_buf(&c->d_mul, &c->mul_bytes, T);
+  if (rc) return rc;
+  uint8_t* neg = (uint8_t*)c->d_mul;
+  if (comb) {
+    if ((rc = mul_bcast_comb(c, d_ct, d_exp, N, dtype, d_x, F, d_out, d_exp_out, d_status, neg, st))) return rc;
+  } else {
+    MulParams p{};
+    p.ct = d_ct;
+    p.exp = d_exp;
+    p.m = (long long)N;
+    p.d = (long long)F;
+    p.cs_i = 1;
+    p.xs_i = (long long)F;
+    p.xs_j = 1;
+    p.x = d_x;
+    p.dtype = dtype;
+    p.n = (long long)T;
+    p.out = d_out;
+    p.out_exp = d_exp_out;
+    p.status = d_status;
+    p.neg = neg;
+    if ((rc = launch_mul(c, p, st))) return rc;
+  }
+  return batch_invert(c, d_out, neg, (long long)T, st);
+}
+
+int pai_mul_bcast_dev(pai_ctx* c, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int dtype, const void* d_x,
+                      size_t F, uint32_t* d_out, int32_t* d_exp_out, int32_t* d_status, void* stream) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c, (hipStream_t)stream);
+  if (N == 0 || F == 0) return 0;
+  if (!d_ct || !d_exp || !d_x || !d_out || !d_exp_out || dtype < 0 || dtype > 2)
+    return fail(PAI_ERR_ARG, "pai_mul_bcast_dev: bad arguments (PAI_BIG scalars are not supported)");
+  if (N > (size_t)INT64_MAX / F / (4 * c->ct_words)) return fail(PAI_ERR_ARG, "pai_mul_bcast_dev: N F too large");
+  if (c->tpi_e != 2 && c->tpi_e != 4 && c->tpi_e != 8) return fail(PAI_ERR_KEY, "unsupported group size");
+  HIPCHK(hipSetDevice(c->device));
+  const bool comb = mulb_take_comb(c, F);
+  c->mulb_path = comb ? 2 : 1;
+  return mul_bcast_run(c, comb, d_ct, d_exp, N, dtype, d_x, F, d_out, d_exp_out, d_status, (hipStream_t)stream);
+}
+
 // Homomorphic negation: out_i = ct_i^-1 mod n^2, pai_mul by the integer -1 bit for bit (k_mul's factor for the scalar
 // -1 is the ciphertext itself, flagged for the inversion), as one batch inversion with no host step.
 int pai_neg_dev(pai_ctx* c, const uint32_t* d_ct, size_t N, uint32_t* d_out, uint32_t* d_status, void* stream) {
@@ -5567,6 +5699,57 @@ int pai_mul(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, int dt
   HIPCHK(hipMemcpy(ct_out, dout, N * W * 4, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(exp_out, dexo, N * 4, hipMemcpyDeviceToHost));
   if (status_out) HIPCHK(hipMemcpy(status_out, dst, N * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Host buffers: whole rows in slices of at most 1 GiB of output words (a single row may be longer), each one
+// mul_bcast_run on the path chosen once for the call. Every output depends on its own ciphertext and scalar only, so the
+// bits do not depend on the slices.
+constexpr size_t MULB_SLICE_BYTES = (size_t)1 << 30;
+
+int pai_mul_bcast(pai_ctx* c, const uint32_t* ct, const int32_t* exp, size_t N, int dtype, const void* x, size_t F,
+                  uint32_t* ct_out, int32_t* exp_out, int32_t* status_out) {
+  if (!c) return fail(PAI_ERR_ARG, "null ctx");
+  CtxLock lk(c);
+  if (N == 0 || F == 0) return 0;
+  if (!ct || !exp || !x || !ct_out || !exp_out || dtype < 0 || dtype > 2)
+    return fail(PAI_ERR_ARG, "pai_mul_bcast: bad arguments (PAI_BIG scalars are not supported)");
+  const size_t W = c->ct_words, esz = dtype == PAI_F32 ? 4 : 8;
+  if (N > (size_t)INT64_MAX / F / (4 * W)) return fail(PAI_ERR_ARG, "pai_mul_bcast: N F too large");
+  if (c->tpi_e != 2 && c->tpi_e != 4 && c->tpi_e != 8) return fail(PAI_ERR_KEY, "unsupported group size");
+  HIPCHK(hipSetDevice(c->device));
+  const bool comb = mulb_take_comb(c, F);
+  c->mulb_path = comb ? 2 : 1;
+  size_t slice = MULB_SLICE_BYTES;
+  if (const char* e = xcheck_env("FLEXPAI_MULB_SLICE_BYTES")) {   // test build: several slices at small shapes
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    if (v > 0) slice = (size_t)v;
+  }
+  const size_t rows = std::min(N, std::max<size_t>(slice / (F * W * 4), 1));
+  DevScope ds;
+  uint32_t* dct = ds.alloc<uint32_t>(rows * W);
+  int32_t* dexp = ds.alloc<int32_t>(rows);
+  void* dx = ds.alloc<uint8_t>(rows * F * esz);
+  uint32_t* dout = ds.alloc<uint32_t>(rows * F * W);
+  int32_t* dexo = ds.alloc<int32_t>(rows * F);
+  int32_t* dst = ds.alloc<int32_t>(rows * F);
+  if (!dct || !dexp || !dx || !dout || !dexo || !dst) return fail(PAI_ERR_HIP, "pai_mul_bcast: device allocation failed");
+  for (size_t i0 = 0; i0 < N; i0 += rows) {
+    const size_t nr = std::min(rows, N - i0), o0 = i0 * F, T = nr * F;
+    HIPCHK(hipMemcpy(dct, ct + i0 * W, nr * W * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dexp, exp + i0, nr * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dx, (const char*)x + o0 * esz, T * esz, hipMemcpyHostToDevice));
+    int rc;
+    {
+      CtxLock dl(c, (hipStream_t) nullptr);   // behind the context's previous device work, like a _dev call
+      rc = mul_bcast_run(c, comb, dct, dexp, nr, dtype, dx, F, dout, dexo, dst, nullptr);
+    }
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(ct_out + o0 * W, dout, T * W * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(exp_out + o0, dexo, T * 4, hipMemcpyDeviceToHost));
+    if (status_out) HIPCHK(hipMemcpy(status_out + o0, dst, T * 4, hipMemcpyDeviceToHost));
+  }
   return 0;
 }
 

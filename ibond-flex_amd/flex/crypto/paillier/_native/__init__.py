@@ -42,6 +42,7 @@ PAI_OPT_SCAN_TILE, PAI_OPT_SCAN_PATH = 23, 24
 PAI_OPT_FOLD_ROWS, PAI_OPT_FOLD_PATH = 25, 26
 PAI_OPT_INV_DEVICE = 27
 PAI_OPT_MATMUL_BUCKET = 28
+PAI_OPT_MUL_BCAST, PAI_OPT_MUL_BCAST_PATH = 29, 30
 PAI_SCAN_REVERSE = 1
 HIST_RUN = 64          # PAI_HIST_RUN: members of a histogram cell that one k_hist_acc instance sums
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
@@ -53,7 +54,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_ctx_public_fb_prepare", "pai_ctx_public_fb_set_bases", "pai_ctx_public_fb_info",
             "pai_ctx_public_fb_policy",
             "pai_encrypt", "pai_add", "pai_decrypt", "pai_encrypt_dev", "pai_add_dev", "pai_decrypt_dev",
-            "pai_mul", "pai_mul_dev", "pai_neg", "pai_neg_dev", "pai_debug_modinv", "pai_debug_modinv_info", "pai_matmul", "pai_matmul_dev", "pai_add_plain", "pai_add_plain_dev",
+            "pai_mul", "pai_mul_dev", "pai_mul_bcast", "pai_mul_bcast_dev", "pai_neg", "pai_neg_dev", "pai_debug_modinv", "pai_debug_modinv_info", "pai_matmul", "pai_matmul_dev", "pai_add_plain", "pai_add_plain_dev",
             "pai_encrypt_big", "pai_encrypt_big_dev", "pai_mul_big", "pai_mul_big_dev", "pai_add_plain_big",
             "pai_add_plain_big_dev",
             "pai_segment_add", "pai_segment_add_dev", "pai_comm_unique_id", "pai_comm_create", "pai_comm_destroy",
@@ -71,6 +72,7 @@ EXPORTED = ("pai_device_count", "pai_device_mem_info", "pai_ctx_create", "pai_ct
             "pai_dev_release_staging", "pai_take_dev", "pai_check_below_dev",
             "pai_take_idx_dev", "pai_segment_add_idx_dev")
 MODINV = ("pai_neg", "pai_neg_dev", "pai_debug_modinv", "pai_debug_modinv_info")
+MUL_BCAST = ("pai_mul_bcast", "pai_mul_bcast_dev")     # broadcast multiply (include/flexpai.h)
 BIG = tuple(n for n in EXPORTED if "_big" in n)     # PAI_BIG operands (include/flexpai.h)
 RESIDENT = EXPORTED[-11:-2]   # device-resident buffers (include/flexpai.h)
 DEVICE_INDEX = EXPORTED[-2:]  # take and segment sums over index lists that are device memory
@@ -205,9 +207,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.pai_encrypt_big_dev.argtypes = [P, P, P, S, S, I, P, S, S, P, U64, P, P, P, P]
             lib.pai_mul_big.argtypes = lib.pai_add_plain_big.argtypes = [P, P, P, S, P, P, S, S, P, P, P]
             lib.pai_mul_big_dev.argtypes = lib.pai_add_plain_big_dev.argtypes = [P, P, P, S, P, P, S, S, P, P, P, P]
+        mul_bcast = hasattr(lib, "pai_mul_bcast")    # (absent from a library built from an earlier commit: tools/mulb_ab.py)
+        if mul_bcast:
+            lib.pai_mul_bcast.argtypes = [P, P, P, S, I, P, S, P, P, P]
+            lib.pai_mul_bcast_dev.argtypes = [P, P, P, S, I, P, S, P, P, P, P]
         for name in EXPORTED:
             if (not resident and name in RESIDENT) or (not device_index and name in DEVICE_INDEX) or (not big and name in BIG) or \
-                    (not modinv and name in MODINV) or (not segdot_index and name in SEGDOT_INDEX):
+                    (not modinv and name in MODINV) or (not segdot_index and name in SEGDOT_INDEX) or \
+                    (not mul_bcast and name in MUL_BCAST):
                 continue
             if name not in ("pai_ctx_destroy", "pai_last_error", "pai_comm_destroy", "pai_release_table_cache"):
                 getattr(lib, name).restype = ctypes.c_int
@@ -1068,6 +1075,40 @@ class Context:
         self._chk(self.lib.pai_mul(self._h, _ptr(ct), _ptr(exp), N, scalar_dtype(x), _ptr(x), 1 if x.size == N and N > 1 else 0,
                                 _ptr(out), _ptr(oe), _ptr(st)))
         return out, oe, st
+
+    def mul_bcast(self, ct: np.ndarray, exp: np.ndarray, x2d: np.ndarray):
+        """pai_mul_bcast: ciphertext i times each scalar of row i of x2d [N, F]; returns (words [N * F, W], exponents
+        and statuses [N * F]), row-major, each output what mul gives for its pair. No ciphertext is replicated."""
+        ct = np.ascontiguousarray(ct, dtype=np.uint32)
+        exp = np.ascontiguousarray(exp, dtype=np.int32)
+        x2d = np.ascontiguousarray(x2d)
+        N = exp.size
+        self._check_words(ct, exp, N)
+        if x2d.ndim != 2 or x2d.shape[0] != N:
+            raise ValueError(f"the plain operand must have shape ({N}, F), not {x2d.shape}")
+        T = x2d.size
+        self.calls["pai_mul_bcast"] += 1
+        out = np.empty((T, self.ct_words), dtype=np.uint32)
+        oe = np.empty(T, dtype=np.int32)
+        st = np.empty(T, dtype=np.int32)
+        self._chk(self.lib.pai_mul_bcast(self._h, _ptr(ct), _ptr(exp), N, scalar_dtype(x2d), _ptr(x2d), x2d.shape[1],
+                                         _ptr(out), _ptr(oe), _ptr(st)))
+        return out, oe, st
+
+    @property
+    def mul_bcast_mode(self) -> int:
+        """PAI_OPT_MUL_BCAST: 1 automatic (rows of at least 64 scalars take the comb), 0 always one chain per output, 2
+        always the comb."""
+        return int(self._get_option(PAI_OPT_MUL_BCAST))
+
+    @mul_bcast_mode.setter
+    def mul_bcast_mode(self, mode: int) -> None:
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_MUL_BCAST, int(mode)))
+
+    @property
+    def mul_bcast_path(self) -> int:
+        """The path of the last pai_mul_bcast[_dev] call: 0 none yet, 1 term path, 2 comb."""
+        return int(self._get_option(PAI_OPT_MUL_BCAST_PATH))
 
     def neg(self, ct: np.ndarray) -> np.ndarray:
         """pai_neg: ct_i^-1 mod n^2, the words of ct_i * -1 (exponents unchanged). ZeroDivisionError where a ciphertext

@@ -501,10 +501,49 @@ def _encrypted_operand(a):
     return A, pk
 
 
+def bcast_row_form(a_shape, x: np.ndarray):
+    """The axis rule of the broadcast multiply (pai_mul_bcast): when numpy broadcasts a ciphertext array of shape a_shape
+    against the plain array x to a result LARGER than the ciphertext array, return (x2d, shape, perm); None when the
+    ciphertext array is not enlarged; ValueError (numpy's) when the shapes do not broadcast. `shape` is the result's.
+    The axes along which the ciphertext array has length 1 (or is missing) and the result does not are the broadcast
+    axes; perm lists the other axes first, in order, then the broadcast axes, and x2d [N, F] is the plain array
+    broadcast to `shape`, permuted by perm and flattened: row i holds the scalars that ciphertext i (flat order) meets.
+    The entry point's [N, F] outputs therefore have the shape (shape[k] for k in perm); np.argsort(perm) transposes them
+    into `shape` (a gather of the result, needed only when perm is not the identity)."""
+    shape = np.broadcast_shapes(tuple(a_shape), x.shape)
+    full = (1,) * (len(shape) - len(a_shape)) + tuple(a_shape)
+    N, T = int(np.prod(full, dtype=np.int64)), int(np.prod(shape, dtype=np.int64))
+    if T == N or T == 0:
+        return None
+    b_axes = [k for k in range(len(shape)) if full[k] == 1 and shape[k] != 1]
+    perm = [k for k in range(len(shape)) if k not in b_axes] + b_axes
+    x2d = np.ascontiguousarray(np.broadcast_to(x, shape).transpose(perm)).reshape(N, T // N)
+    return x2d, shape, perm
+
+
+def _mul_bcast(a, A, pk, x2d, shape, perm):
+    """mul_plain where the broadcast enlarges the ciphertext array: A is packed once and ONE pai_mul_bcast call makes
+    every product (no ciphertext is replicated); the result takes the broadcast shape, by a transpose of the object
+    array when the broadcast axes do not trail."""
+    from . import _runtime
+    words, exps, _ = pack(a if A is a else A, pk)
+    out, oe, st = _runtime.context(pk).mul_bcast(words, exps, x2d)
+    bad = np.flatnonzero(st)
+    if bad.size:
+        # as in mul_plain: the per-element operator on the first scalar the device does not encode raises
+        i, j = divmod(int(bad[0]), x2d.shape[1])
+        A.reshape(-1)[i] * x2d[i, j].item()
+        raise ValueError(f"the scalar {x2d[i, j]!r} at row {i}, column {j} does not encode")
+    res = materialize(pk, out, oe, tuple(shape[k] for k in perm), obfuscated=False)
+    return res if perm == sorted(perm) else res.transpose(np.argsort(perm))
+
+
 def mul_plain(a, y):
     """Encrypted array times a plain scalar or array on the GPU (PaillierEncryptedNumber.__mul__
     per element, encrypted_number.py:86-113, with numpy broadcasting). NotImplemented when an
-    operand is not of a device type (the caller then falls back to the per-element operators)."""
+    operand is not of a device type (the caller then falls back to the per-element operators).
+    A plain array that broadcasts the encrypted one to a larger shape (`enc[:, None] * X`, `enc_row * X`) takes ONE
+    pai_mul_bcast call over the packed array as it is (bcast_row_form, _mul_bcast)."""
     from . import _runtime
     if isinstance(y, PaillierEncryptedNumber):
         raise ValueError("PaillierEncryptedNumber * PaillierEncryptedNumber is not allowed.")
@@ -518,9 +557,12 @@ def mul_plain(a, y):
         if x is None:
             return NotImplemented
         try:
+            rows = None if x.dtype == object else bcast_row_form(A.shape, x)
             Ab, xb = np.broadcast_arrays(A, x)
         except ValueError:
             return NotImplemented
+        if rows is not None:
+            return _mul_bcast(a, A, pk, *rows)
         shape = Ab.shape
         if shape != A.shape:
             A = np.ascontiguousarray(Ab)

@@ -87,6 +87,34 @@ class BufferOps(object):
     def __rmul__(self, y):
         return self * y
 
+    def _mul_operand(self, y):
+        """(y, rows) for __mul__. A plain ndarray of neither 1 nor `size` elements follows numpy's broadcasting against
+        the buffer's shape: where the result is larger than the buffer, rows = (x2d, shape, perm) is the row form of
+        the broadcast multiply (cipher_array.bcast_row_form; one pai_mul_bcast[_dev] call, _mul_rows); where only the
+        plain array grows (`buf(N, F) * x(F,)`) it is expanded here and the element-wise call follows as before. Anything
+        else is returned as it is, with rows = None: the element-wise route accepts it or raises as it always did."""
+        if not isinstance(y, np.ndarray) or y.dtype == object or y.size in (1, self.size):
+            return y, None
+        from .cipher_array import _plain_array, bcast_row_form
+        x = _plain_array(y)
+        if x is None:
+            return y, None
+        try:
+            rows = bcast_row_form(self.shape, x)
+        except ValueError:
+            return y, None
+        if rows is None:
+            if np.broadcast_shapes(self.shape, x.shape) != tuple(self.shape):
+                return y, None                                  # an empty result of another shape: raises as before
+            return np.ascontiguousarray(np.broadcast_to(y, self.shape)), None
+        return y, rows
+
+    def _mul_rows(self, out, oe, shape, perm):
+        """The [N, F] outputs of the broadcast multiply as a buffer of the broadcast shape, not obfuscated. When the
+        broadcast axes do not trail (`buf(6,) * X(4, 6)`), the result is transposed into place: a gather of the result."""
+        res = self._like(out, oe, 0, tuple(shape[k] for k in perm))
+        return res if perm == sorted(perm) else res.transpose(tuple(int(k) for k in np.argsort(perm)))
+
     def __neg__(self):
         """self * -1 bit for bit (exponents unchanged, not re-randomised) as a call of its own: pai_neg / pai_neg_dev,
         one batch inversion with no host step. ZeroDivisionError where a ciphertext has no inverse mod n^2."""
@@ -269,6 +297,23 @@ class CiphertextBuffer(BufferOps):
     def __mul__(self, y):
         if isinstance(y, (PaillierEncryptedNumber, CiphertextBuffer)):
             raise ValueError("PaillierEncryptedNumber * PaillierEncryptedNumber is not allowed.")
+        y, rows = self._mul_operand(y)
+        if rows is not None:
+            x2d, shape, perm = rows
+            from . import _runtime
+            if not _runtime.gpu_available():                    # the per-element operators on Python integers
+                terms = [PaillierEncryptedNumber(self.public_key, c, int(e)) * s.item()
+                         for c, e, row in zip(_ints(self.words), self.exps, x2d) for s in row]
+                W = self.words.shape[1]
+                out = _runtime.ints_to_words([t.ciphertext(False) for t in terms], W).reshape(len(terms), W)
+                return self._mul_rows(out, np.array([t.exponent for t in terms], dtype=np.int32), shape, perm)
+            out, oe, st = self._ctx().mul_bcast(self.words, self.exps, x2d)
+            bad = np.flatnonzero(st)
+            if bad.size:
+                i, j = divmod(int(bad[0]), x2d.shape[1])
+                PaillierEncryptedNumber(self.public_key, _ints(self.words[i:i + 1])[0], int(self.exps[i])) * x2d[i, j].item()
+                raise ValueError(f"the scalar {x2d[i, j]!r} at row {i}, column {j} does not encode")
+            return self._mul_rows(out, oe, shape, perm)
         x = _plain(y, self.size)
         out, oe, st = self._ctx().mul(self.words, self.exps, x)
         bad = np.flatnonzero(st)

@@ -215,6 +215,23 @@ def mul_dev(pk, words: DeviceWords, exps, x: np.ndarray):
     return _scalar_call("pai_mul_dev", pk, words, exps, x)
 
 
+def mul_bcast_dev(pk, words: DeviceWords, exps, x2d: np.ndarray):
+    """pai_mul_bcast_dev: ciphertext i times each scalar of row i of x2d [N, F]: (words [N * F, W], exponents, statuses on
+    the host). The ciphertexts are read where they are; only the scalars go up."""
+    (N, W), dev = words.shape, words.device
+    ctx = context_on(pk, dev)
+    ex = _exp_mem(exps, N, dev)
+    x2d = np.ascontiguousarray(x2d)
+    if x2d.ndim != 2 or x2d.shape[0] != N:
+        raise ValueError(f"the plain operand must have shape ({N}, F), not {x2d.shape}")
+    T = x2d.size
+    dx = _native.device_upload(x2d, dev)
+    out, oe, st = DeviceWords.empty(T, W, dev), _i32(dev, T), _i32(dev, T)
+    ctx.dev_call("pai_mul_bcast_dev", words.ptr, ex.ptr, N, _native.scalar_dtype(x2d), dx.ptr, x2d.shape[1],
+                 out.ptr, oe.ptr, st.ptr)
+    return out, oe, st.download(np.int32, T)
+
+
 def neg_dev(pk, words: DeviceWords):
     """pai_neg_dev: (words, status word on the host). The entry point itself waits for nothing; the 4-byte download of
     the status word here is where this layer learns of a ciphertext without inverse."""
@@ -685,10 +702,15 @@ class DeviceCiphertextBuffer(BufferOps):
     def __mul__(self, y):
         if isinstance(y, (PaillierEncryptedNumber, CiphertextBuffer, DeviceCiphertextBuffer)):
             raise ValueError("PaillierEncryptedNumber * PaillierEncryptedNumber is not allowed.")
-        out, oe, st = mul_dev(self.public_key, self.words, self._ex, _plain(y, self.size))
+        y, rows = self._mul_operand(y)
+        if rows is not None:
+            x2d, shape, perm = rows
+            out, oe, st = mul_bcast_dev(self.public_key, self.words, self._ex, x2d)
+        else:
+            out, oe, st = mul_dev(self.public_key, self.words, self._ex, _plain(y, self.size))
         if np.any(st):
             return (self.to_host() * y).to_device()
-        return self._like(out, oe)
+        return self._like(out, oe) if rows is None else self._mul_rows(out, oe, shape, perm)
 
     def _neg(self):
         # the status word is read (4 bytes) before the result is handed out: ZeroDivisionError is raised here, as by * -1

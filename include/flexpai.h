@@ -247,6 +247,12 @@ typedef struct pai_comm pai_comm;
                                   * |M| 16^(E - e) fit 512 bits; other calls take the path they take with 0. Window of
                                   * 4 .. 8 bits from K (csrc/engine_pip.hpp). Same bits and the same PAI_ERR_NOINV
                                   * either way; whether it is faster has been measured per shape */
+#define PAI_OPT_MUL_BCAST 29     /* pai_mul_bcast[_dev]: 1 (default) automatic -- rows of at least 64 scalars share a
+                                  * fixed-base comb per ciphertext (csrc/kernels_mulb.hpp), shorter rows run one k_mul
+                                  * chain per output; 0: always the chains (the term path); 2: always the comb. Same bits
+                                  * and the same PAI_ERR_NOINV either way. Any other value is PAI_ERR_ARG.          */
+#define PAI_OPT_MUL_BCAST_PATH 30 /* read-only: the path of this context's last pai_mul_bcast[_dev] call: 0 = none yet,
+                                  * 1 = term path, 2 = comb                                                       */
 /* The automatic choice of PAI_OPT_FOLD_ROWS: the largest output count at which the row kernel was more than 5 % faster
  * than the group kernel in the same-process A/B of tools/fold_ab.py on an MI355X (profiles/fold_ab.json),
  * per key size (n^2 of 74 / 148 / 296 limbs). 0: that key size stays on lane groups. Measured at 64, 1 024, 4 096, 16 384
@@ -375,6 +381,18 @@ int pai_decrypt(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, 
  * contributes the factor 1 at exponent exp_i + 0: ciphertext 1, exponent exp_i.                  */
 int pai_mul(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int dtype, const void* x, size_t x_stride,
             uint32_t* ct_out, int32_t* exp_out, int32_t* status_out);
+/* Broadcast multiply: ciphertext i times each of the F scalars of row i of x [N][F] (row-major), nothing summed --
+ * `enc[:, None] * X`. ct_out [N][F][W], exp_out [N][F], status_out [N][F] (nullable); output (i, j) is, bit for bit,
+ * what pai_mul gives for ct_i and x[i][j]: exponent, status, ciphertext 1 at exp_i for a scalar that does not encode,
+ * and ONE batch inversion over the N F outputs for the negative scalars (a ciphertext without inverse that meets one
+ * ends the call with PAI_ERR_NOINV; outputs not yet copied back stay unwritten -- all of them unless the call needs
+ * more than one slice). No ciphertext is replicated. PAI_OPT_MUL_BCAST chooses between one k_mul chain per output and
+ * a fixed-base comb per ciphertext (16 windows of 15 powers, built once per row: at most 16 products and no squaring per
+ * output); PAI_OPT_MUL_BCAST_PATH reports the choice. dtype PAI_F32 / PAI_F64 / PAI_I64 (PAI_BIG: PAI_ERR_ARG).
+ * N = 0 or F = 0: PAI_OK, nothing written. Rows move in slices of at most 1 GiB of output; the bits do not depend on
+ * the slices, nor on the blocks of the comb's table budget. */
+int pai_mul_bcast(pai_ctx* ctx, const uint32_t* ct, const int32_t* exp, size_t N, int dtype, const void* x, size_t F,
+                  uint32_t* ct_out, int32_t* exp_out, int32_t* status_out);
 /* Ciphertext + plaintext, element-wise: out_i = ct_i (+) x_(i*x_stride), x encoded like
  * FixedPointNumber.encode(x, max_exponent=exp_i) (fixedpoint_number.py:81-84) and raw-encrypted with r = 1,
  * exponent max(exp_i, e(x)). status_out (nullable): PAI_EL_FLOAT_OVF where x * 16^E is not a finite double
@@ -571,6 +589,12 @@ int pai_obfuscate_dev(pai_ctx* ctx, const uint32_t* d_ct, size_t N, int obf_mode
                       const uint8_t* rng_key32, uint64_t index_base, uint32_t* d_out, void* stream);
 int pai_mul_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int dtype, const void* d_x,
                 size_t x_stride, uint32_t* d_out, int32_t* d_exp_out, int32_t* d_status, void* stream);
+/* pai_mul_bcast on device buffers (d_x [N][F], d_out [N][F][W], d_exp_out and d_status [N][F], d_status nullable; d_out
+ * must not overlap d_ct). Takes the context lock and waits for the context's previous call like every _dev call, and
+ * synchronises `stream` exactly where pai_mul_dev does: once, in the batch inversion that closes the call. On
+ * PAI_ERR_NOINV d_out holds the powers before the inversion. */
+int pai_mul_bcast_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int dtype, const void* d_x,
+                      size_t F, uint32_t* d_out, int32_t* d_exp_out, int32_t* d_status, void* stream);
 int pai_add_plain_dev(pai_ctx* ctx, const uint32_t* d_ct, const int32_t* d_exp, size_t N, int dtype,
                       const void* d_x, size_t x_stride, uint32_t* d_out, int32_t* d_exp_out, int32_t* d_status,
                       void* stream);
