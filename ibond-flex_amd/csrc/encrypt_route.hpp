@@ -25,7 +25,8 @@ struct EncryptRoute {
 //                                                     over-wide r with PAI_ERR_ARG, in launch_crt)
 //   4096-bit key holder, n > crt4_min                 k_crt4_*
 //   device RNG, public fixed base on, 2048-bit n      public sampler, ahead of k_pe_w (pfb_supported also holds at
-//                                                     1009..1024 bits under PAI_OPT_PUBLIC_FB = 2: k_pfb1)
+//                                                     1009..1024 bits under PAI_OPT_PUBLIC_FB = 2: k_pfb1, and at
+//                                                     2049..4096 bits without a private key: k_pfb4)
 //   n <= crtw_max and a k_pe_w op list                k_pe_w
 //   2048 / 1024 / 4096 bits                           k_pe_* / k_pe1_* / k_pe4_* (the last without a private key only)
 //   otherwise                                         k_encrypt

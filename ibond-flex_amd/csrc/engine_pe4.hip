@@ -42,4 +42,11 @@ hipError_t pe4_launch(const Pe4Params& p, const Pe4Geom& g, hipStream_t st, hipE
   return hipSuccess;
 }
 
+hipError_t pe4_launch_fin(const Pe4Params& p, int cus, hipStream_t st) {
+  const long long gb = (p.n + PE4_GPB - 1) / PE4_GPB;
+  const long long cap = (long long)occupancy(k_pe4_fin<PE4_TPI, PE4_LL>, fin_lds()) * cus;
+  hipLaunchKernelGGL((k_pe4_fin<PE4_TPI, PE4_LL>), dim3((int)std::max<long long>(1, std::min(gb, cap))), dim3(BLOCK), fin_lds(), st, p);
+  return hipGetLastError();
+}
+
 }  // namespace fpai

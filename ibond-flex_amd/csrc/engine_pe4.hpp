@@ -11,5 +11,7 @@ struct Pe4Geom {
 int pe4_geometry(int cus, long long chunk, Pe4Geom* g);
 // k_pe4_pre, k_pe4_pow, k_pe4_fin on `st`; ev[0..3] nullable
 hipError_t pe4_launch(const Pe4Params& p, const Pe4Geom& g, hipStream_t st, hipEvent_t* ev);
+// k_pe4_fin alone, over pairs in p.xw that another kernel left (k_pfb4, kernels_pfb4.hpp)
+hipError_t pe4_launch_fin(const Pe4Params& p, int cus, hipStream_t st);
 
 }  // namespace fpai

@@ -49,6 +49,7 @@ static const char* xcheck_env(const char* name) {
 #include "engine_pe.hpp"
 #include "engine_pfb.hpp"
 #include "engine_pfb1.hpp"
+#include "engine_pfb4.hpp"
 #include "engine_sgp.hpp"
 #include "engine_sgs.hpp"
 #include "engine_grp.hpp"
@@ -143,6 +144,7 @@ struct PfbTables {
   PfbConst* d_pfb = nullptr;
   SgpHalf* d_sgp = nullptr;        // the split-pair sampler over the public tables (kernels_sgp.hpp)
   Pfb1Const* d_pfb1 = nullptr;     // 1024-bit keys: Montgomery pair rows for k_pfb1 (kernels_pfb1.hpp)
+  Pfb4Const* d_pfb4 = nullptr;     // 2049..4096-bit keys: pair rows on pair groups for k_pfb4 (kernels_pfb4.hpp)
   std::vector<void*> mem, tables;
   void release() {
     free_device(mem, tables);
@@ -246,7 +248,7 @@ struct pai_ctx {
   // Built lazily past the break-even count (or pai_ctx_public_fb_prepare); never needed for correctness.
   int pfb_state = FB_UNTRIED;
   std::string pfb_reason;
-  int pfb_enabled = 1;         // PAI_OPT_PUBLIC_FB: 0 off, 1 the 2048-bit sampler, 2 the 1024-bit one (k_pfb1) as well
+  int pfb_enabled = 1;         // PAI_OPT_PUBLIC_FB: 0 off, 1 the 2048-bit sampler, 2 also k_pfb1 (1024 bits) and k_pfb4 (4096)
   int pfb_W = 0;                // requested window; 0 = not chosen yet
   std::vector<HBig> pfb_bases;  // g_0 .. g_PFB_SHORT (chosen at the first build unless set)
   PfbTables pfb;
@@ -1453,6 +1455,7 @@ static long long fb_break_even(const pai_ctx* c, uint64_t rows, int row_bytes) {
 static bool fb_wanted(pai_ctx* c, long long n);
 static bool pfb_supported(const pai_ctx* c);
 static bool pfb1_key(const pai_ctx* c);
+static bool pfb4_key(const pai_ctx* c);
 
 static int fb_unavailable(pai_ctx* c, const std::string& why) {
   c->fb.release();
@@ -2334,7 +2337,7 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
     case PAI_OPT_FIXED_BASE: c->fb_enabled = value != 0; return 0;
     case PAI_OPT_PUBLIC_FB: {
       const int v = value == 2 ? 2 : value != 0;
-      if (pfb1_key(c) && (v == 2) != (c->pfb_enabled == 2)) {   // the 1024-bit sampler switched on or off: start afresh
+      if ((pfb1_key(c) || pfb4_key(c)) && (v == 2) != (c->pfb_enabled == 2)) {   // an opt-in sampler switched on or off: start afresh
         HIPCHK(hipSetDevice(c->device));
         c->pfb.release();
         c->pfb_state = pai_ctx::FB_UNTRIED;
@@ -2746,9 +2749,13 @@ static int launch_fb(pai_ctx* c, const EncParams& e, hipStream_t st) {
 // Under PAI_OPT_PUBLIC_FB = 2 the keys of 64 ciphertext words (n of 1009..1024 bits) qualify too: k_pfb1 over Montgomery
 // pair rows of 2 x 32 words, k_pe1_fin's 37-limb pairs (kernels_pfb1.hpp). Opt-in: the default leaves them on k_pe1_*.
 static bool pfb1_key(const pai_ctx* c) { return c->pe1_ok && c->ct_words == 2 * PFB1_PW; }
+// Under the same value every public-only context that k_pe4_* serves (n of 2049..4096 bits) qualifies as well: k_pfb4 over
+// pair rows of 2 x 152 limbs, finished by k_pe4_fin (kernels_pfb4.hpp). A key holder at these sizes never does: its
+// route is CRT.
+static bool pfb4_key(const pai_ctx* c) { return c->pe4_ok && !c->has_priv; }
 
 static bool pfb_supported(const pai_ctx* c) {
-  if (c->pfb_enabled == 2 && pfb1_key(c)) return true;
+  if (c->pfb_enabled == 2 && (pfb1_key(c) || pfb4_key(c))) return true;
   return c->pe_ok && c->ct_words == 2 * PFB_PW && (size_t)c->nb + 24 <= (size_t)LB * PFB_S;
 }
 
@@ -2760,7 +2767,7 @@ static void pfb_digit_counts(const pai_ctx* c, int W, int* K0, int* KS) {
 static uint64_t pfb_bytes(const pai_ctx* c, int W) {
   int K0, KS;
   pfb_digit_counts(c, W, &K0, &KS);
-  return (uint64_t)(K0 + PFB_SHORT * KS) * (1ull << W) * (pfb1_key(c) ? PFB1_ROW4 : PFB_ROW4) * 16ull;
+  return (uint64_t)(K0 + PFB_SHORT * KS) * (1ull << W) * (pfb4_key(c) ? PFB4_ROW4 : pfb1_key(c) ? PFB1_ROW4 : PFB_ROW4) * 16ull;
 }
 
 static int pfb_choose_window(pai_ctx* c) {
@@ -2918,12 +2925,47 @@ static int build_pfb1(pai_ctx* c, int W, int K0, int KS) {
   return rc;
 }
 
+// The 2049..4096-bit tables (kernels_pfb4.hpp), as build_pfb1: n, (1 - R) mod n, the pair of R mod n^2, the pairs of
+// g_j R and n's words up; everything else is made on the device.
+static int build_pfb4(pai_ctx* c, int W, int K0, int KS) {
+  const HBig &n = c->n, &n2 = c->N;
+  const size_t RS = (size_t)LB * PE4_S;
+  const int K = K0 + PFB_SHORT * KS, LO = W / 2;
+  const size_t nent = ((size_t)1 << LO) + ((size_t)1 << (W - LO));
+  PfbTables& pfb = c->pfb;
+  std::vector<uint32_t> gR;
+  for (const HBig& g : c->pfb_bases) append(gR, pair_split(mul_pow2_mod(g, RS, n2), n, PE4_S));
+  uint32_t *dn, *dx1, *done, *dgR, *dnw, *dbases = nullptr, *dlohi = nullptr;
+  int rc;
+  if ((rc = upload_to(pfb.mem, n.limbs(PE4_S, LB), &dn)) ||
+      (rc = upload_to(pfb.mem, mod(sub(add(n, HBig(1)), mul_pow2_mod(HBig(1), RS, n)), n).limbs(PE4_S, LB), &dx1)) ||
+      (rc = upload_to(pfb.mem, pair_split(mul_pow2_mod(HBig(1), RS, n2), n, PE4_S), &done)) ||
+      (rc = upload_to(pfb.mem, gR, &dgR)) || (rc = upload_to(pfb.mem, n.words((n.bits() + 31) / 32), &dnw)))
+    return rc;
+  uint32_t* table = (uint32_t*)TableArena::get().alloc(c->device, ((size_t)K << W) * PFB4_ROW4 * sizeof(uint4));
+  if (!table) return fail(PAI_ERR_HIP, "table allocation failed");
+  pfb.tables.push_back(table);
+  if (hipMalloc(&dbases, (size_t)K * 2 * PE4_S * 4) == hipSuccess && hipMalloc(&dlohi, (size_t)K * nent * 2 * PE4_S * 4) == hipSuccess) {
+    const Pfb4Const pc{dn, dx1, done, dgR, dnw, dbases, dlohi, (const uint4*)table, mont_prime(n, LB), (int)n.bits(),
+                       (int)c->pfb_bases.size(), K, W, K0, KS};
+    SetupTrace tr("  pfb4 chain, lohi, fill");
+    if (!(rc = upload_to(pfb.mem, std::vector<Pfb4Const>{pc}, &pfb.d_pfb4)) &&
+        (pfb4_build(pfb.d_pfb4, pc.nbases, K, W, table, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+      rc = fail(PAI_ERR_HIP, "table construction failed");
+  } else {
+    rc = fail(PAI_ERR_HIP, "table allocation failed");
+  }
+  if (dbases) (void)hipFree(dbases);
+  if (dlohi) (void)hipFree(dlohi);
+  return rc;
+}
+
 static int ensure_pfb(pai_ctx* c) {
   if (c->pfb_state == pai_ctx::FB_READY) return 1;
   if (c->pfb_state == pai_ctx::FB_UNAVAILABLE) return 0;
   if (!pfb_supported(c))
-    return pfb_unavailable(c, "the public fixed-base kernels need an n of 2033..2048 bits (128 ciphertext words), or of "
-                              "1009..1024 bits (64 words) under PAI_OPT_PUBLIC_FB = 2");
+    return pfb_unavailable(c, "the public fixed-base kernels need an n of 2033..2048 bits (128 ciphertext words), or, under "
+                              "PAI_OPT_PUBLIC_FB = 2, of 1009..1024 bits (64 words) or of 2049..4096 bits without a private key");
   const int W = pfb_choose_window(c);
   if (!W) return pfb_unavailable(c, "tables do not fit the device memory budget");
   SetupTrace tr_all("ensure_pfb");
@@ -2936,8 +2978,8 @@ static int ensure_pfb(pai_ctx* c) {
   }
   PfbTables& pfb = c->pfb;
   pfb.release();
-  if (pfb1_key(c)) {
-    if (build_pfb1(c, W, K0, KS)) return pfb_unavailable(c, pai_last_error());
+  if (pfb1_key(c) || pfb4_key(c)) {
+    if (pfb4_key(c) ? build_pfb4(c, W, K0, KS) : build_pfb1(c, W, K0, KS)) return pfb_unavailable(c, pai_last_error());
     pfb.K = K;
     pfb.K0 = K0;
     pfb.W_used = W;
@@ -2985,6 +3027,21 @@ static long long pfb_threshold(pai_ctx* c) {
     const double build_s = 0.067 + (double)(K0 + PFB_SHORT * KS) * (double)(1ull << W) * 0.88e-9;
     const double save_s = 1.0 / 4.43e6 - 1.0 / (W >= 16 ? 15.3e6 : 12.0e6);
     return (long long)(build_s / save_s) + 1;
+  }
+  if (pfb4_key(c)) {
+    // The 2049..4096-bit tables, one MI355X, 262 144 elements on an n of 4096 bits, all from one run
+    // (tools/gpu/pfb4_rate.py, profiles/pfb4_rate.json): the first build takes 0.3504 s at W = 12 (603 positions,
+    // 2 469 888 rows) and 0.4753 s at W = 16 (452 positions, 29 622 272 rows) -- a line of 4.60 ns per row through the
+    // two -- and an element then costs 1 / 402 638 s (W = 12) or 1 / 534 647 s (W = 16) on k_pfb4 instead of 1 / 60 716 s
+    // on k_pe4_*: the break-even is ~25 k elements at W = 12 and ~32.5 k at the default W = 16. Every n of the range runs
+    // on the same 152 limbs, so a shorter n scales k_pe4_*'s time by its bits (the squarings of r^n) and k_pfb4's by its
+    // positions (the row products); that scaling is not measured. W = 20 never fits a device.
+    const double K = (double)(K0 + PFB_SHORT * KS);
+    const double per_row = (0.4753 - 0.3504) / (29622272.0 - 2469888.0);
+    const double build_s = 0.3504 + (K * (double)(1ull << W) - 2469888.0) * per_row;
+    const double pe4_s = (double)c->nb / 4096.0 / 60716.0;
+    const double pfb4_s = W >= 16 ? K / 452.0 / 534647.0 : K / 603.0 / 402638.0;
+    return (long long)(build_s / (pe4_s - pfb4_s)) + 1;
   }
   const double build_s = 0.114 + (double)(K0 + PFB_SHORT * KS) * (double)(1ull << W) * 1.91e-9;
   const double rate = W >= 20 ? 4.78e6 : W >= 16 ? 3.93e6 : 3.00e6;
@@ -3040,9 +3097,49 @@ static int launch_pfb1(pai_ctx* c, const EncParams& e, hipStream_t st) {
   return 0;
 }
 
+// 2049..4096-bit keys: digits, k_pfb4, k_pe4_fin per chunk of CRT_CHUNK elements
+static int launch_pfb4(pai_ctx* c, const EncParams& e, hipStream_t st) {
+  const long long N = e.n;
+  const long long chunk = std::min(N, CRT_CHUNK);
+  int occ = 1;
+  pfb4_occupancy(&occ);
+  const size_t dbytes = (size_t)c->pfb.K * 4, xbytes = (size_t)2 * PE4_S * 4;
+  int rc;
+  if ((rc = ensure_work(c, (dbytes + xbytes) * chunk))) return rc;
+  uint32_t* digits = (uint32_t*)c->d_work;
+  uint32_t* xw = (uint32_t*)((char*)c->d_work + dbytes * chunk);
+  for (long long off = 0; off < N; off += chunk) {
+    const long long n = std::min(chunk, N - off);
+    const EncSlice sl = enc_slice(e, off);
+    PfbDigitParams pd{};
+    pd.n = n;
+    std::memcpy(pd.rng_key, sl.rnd.rng_key, sizeof(pd.rng_key));
+    pd.index_base = sl.rnd.index_base;
+    pd.K = c->pfb.K;
+    pd.W = c->pfb.W_used;
+    pd.digits = digits;
+    const int gD = (int)std::max<long long>(1, std::min<long long>((long long)8 * c->cus, (n + PFB_DIG_BLOCK - 1) / PFB_DIG_BLOCK));
+    stage_mark(c, 0, st);
+    HIPCHK(pfb_launch_digits(pd, gD, st));
+    stage_mark(c, 1, st);
+    const long long gb = (n + PE4_GPB - 1) / PE4_GPB;
+    HIPCHK(pfb4_launch(Pfb4Params{c->pfb.d_pfb4, n, digits, (const uint4*)c->pfb.tables[0], sl.src, sl.dst, xw}, (int)std::min<long long>(gb, (long long)occ * c->cus), st));
+    stage_mark(c, 2, st);
+    Pe4Params pf{};
+    pf.k = c->d_pe4;
+    pf.dst = sl.dst;
+    pf.n = n;
+    pf.xw = xw;
+    HIPCHK(pe4_launch_fin(pf, c->cus, st));
+    stage_mark(c, 3, st);
+  }
+  return 0;
+}
+
 // digits, k_pfb, k_pe_fin per chunk of CRT_CHUNK elements
 static int launch_pfb(pai_ctx* c, const EncParams& e, hipStream_t st) {
   if (c->pfb.d_pfb1) return launch_pfb1(c, e, st);
+  if (c->pfb.d_pfb4) return launch_pfb4(c, e, st);
   const long long N = e.n;
   const long long chunk = std::min(N, CRT_CHUNK);
 #if FLEXPAI_XCHECK

@@ -721,8 +721,9 @@ class Context:
         return bool(self._get_option(PAI_OPT_PUBLIC_FB))
 
     def set_public_fixed_base(self, enabled):
-        """False / True as before; 2 also enables the 1024-bit sampler (k_pfb1) for an n of 1009..1024 bits, which
-        then engages once prepare_public_fixed_base() has built its tables (include/flexpai.h)."""
+        """False / True as before; 2 also enables the 1024-bit sampler (k_pfb1) for an n of 1009..1024 bits and the
+        4096-bit one (k_pfb4) for a public-only n of 2049..4096 bits, which then engage past their break-even counts or
+        once prepare_public_fixed_base() has built the tables (include/flexpai.h)."""
         self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_PUBLIC_FB, 2 if enabled == 2 else 1 if enabled else 0))
 
     @property

@@ -169,13 +169,19 @@ typedef struct pai_comm pai_comm;
                                   * 2 (opt-in): the same, and an n of 1009..1024 bits (64 ciphertext words) gets the
                                   * same sampler on Montgomery pair rows of 256 B (kernels_pfb1.hpp: k_pfb1): same
                                   * bases, exponents, windows and calls as at 2048 bits, same r; measured break-even
-                                  * ~510 k elements at the default window 16 (pai_ctx_public_fb_policy). At other
-                                  * key sizes 2 acts as 1; 0 and 1 leave a 1024-bit context on k_pe1_*, bit for bit
-                                  * as before                                                                  */
+                                  * ~510 k elements at the default window 16 (pai_ctx_public_fb_policy). Likewise an
+                                  * n of 2049..4096 bits in a context WITHOUT the private key (the keys k_pe4_* serve)
+                                  * gets it on pair groups over rows of 1216 B (kernels_pfb4.hpp: k_pfb4); measured
+                                  * break-even ~32.5 k elements at 4096 bits and window 16. At other key sizes 2 acts
+                                  * as 1; 0 and 1 leave a 1024-bit context on k_pe1_* and a 4096-bit one on k_pe4_*,
+                                  * bit for bit as before; a key holder above 2048 bits is never affected      */
 #define PAI_OPT_PFB_READY 11     /* read-only: 1 when the public fixed-base tables are resident               */
 #define PAI_OPT_PFB_WINDOW 12    /* digit window of the public tables: 12, 16 or 20 (the windows pinned to the
                                   * reference's goldens; default 16: 324 rows of 512 B per element, 10.9 GB of
-                                  * tables; $FLEXPAI_FB_WINDOW=auto: 20 for a process with one context)       */
+                                  * tables; $FLEXPAI_FB_WINDOW=auto: 20 for a process with one context). k_pfb1's
+                                  * rows of 256 B: 0.36 / 4.36 / 57.7 GB at 12 / 16 / 20. k_pfb4's rows of 1216 B at
+                                  * 4096 bits: 3.0 GB (603 rows per element) / 36.0 GB (452); 20 would take 469 GB
+                                  * and falls to 16 by the memory budget                                       */
 #define PAI_OPT_SPLIT_SAMPLER 13 /* read-only: bit 0 = the resident 4096-bit key-holder tables, bit 1 = the resident
                                   * public tables are sampled on split pairs (kernels_sgp.hpp: k_sgp, the default;
                                   * $FLEXPAI_SGP=0 at table build selects k_fbgp / k_pfb); bit 2 = the resident
