@@ -20,7 +20,8 @@ struct EncryptRoute {
 //   PAI_OBF_NONE                                      k_encrypt
 //   key holder, CRT on, device RNG, fixed base on     key holder's sampler, ahead of the rows (resident or wanted
 //                                                     tables take precedence over them)
-//   4096-bit key holder, n <= crtw_max, r fits        k_crt_w<74, 148>; an r too wide for the rows goes on down
+//   4096-bit key holder, n <= crtw_max, r fits        k_crt_w<74, 148> (<56, 112> where PAI_OPT_PRIME_LIMBS chose 56
+//                                                     limbs; rows_sa tells); an r too wide for the rows goes on down
 //   1024/2048-bit key holder                          k_crt_w at n <= crtw_max, lane CRT above (both reject an
 //                                                     over-wide r with PAI_ERR_ARG, in launch_crt)
 //   4096-bit key holder, n > crt4_min                 k_crt4_*

@@ -185,7 +185,12 @@ struct pai_ctx {
   // protocol-sized calls); PAI_OPT_ROWS_MAX
   long long crtw_max = CRTW_DEFAULT_MAX;
   int crt_sa = 0, crt_sb = 0;
-  int rows_sa = 0;   // 74: a 4096-bit key's row-kernel constants (k_crt_w<74, 148>, k_dec_w<74, 148>; setup_rows4096)
+  int rows_sa = 0;   // split_s: a 2049..4096-bit key's row-kernel constants (k_crt_w<S, 2 S>, k_dec_w<S, 2 S>; setup_rows4096)
+  // limbs of p_h on the split-pair kernels and the rows of a 2049..4096-bit key holder: D4_S (74), or D4_S3 (56) for a
+  // larger prime of at most 1556 bits when PAI_OPT_PRIME_LIMBS was set before the private key (setup_crt). The
+  // fixed-base sampler keeps its own 74-limb constants either way.
+  bool prime_limbs_opt = false;
+  int split_s = D4_S;
   CrtHalf* d_crt_a = nullptr;   // [2] stage A halves
   CrtHalf* d_crt_b = nullptr;   // [2] stage B halves
   uint32_t *d_kq = nullptr, *d_kp = nullptr;
@@ -761,7 +766,8 @@ static bool build_pef_program(const HBig& n, size_t RS, std::vector<uint32_t>& p
 // then Y' (A~, 0) (iota taken before it) and the product with (1, 0) into tile D4F_G. kf gets the closing sum's
 // constants: K'_t = R sum over the chain's multiplies by entry t of 2^(squares after it) mod p_h, slot 0 = -R mod
 // p_h (entry 1 is B-free, its slot carries the ciphertext's B_c term). tools/dec4f_model.py restates the algebra.
-static bool build_dec4f_program(const HBig& ph, size_t RS, std::vector<uint32_t>& prog, std::vector<uint32_t>& kf) {
+static bool build_dec4f_program(const HBig& ph, int S, std::vector<uint32_t>& prog, std::vector<uint32_t>& kf) {
+  const size_t RS = (size_t)LB * S;
   const HBig e = sub(ph, HBig(2));
   if (e.bits() < 8) return false;
   std::vector<uint16_t> sched;
@@ -799,7 +805,7 @@ static bool build_dec4f_program(const HBig& ph, size_t RS, std::vector<uint32_t>
   kf.clear();
   for (int t = 0; t < LANE_NTILE; ++t) {
     const HBig v = t == 0 ? sub(ph, mul_pow2_mod(HBig(1), RS, ph)) : mul_pow2_mod(K[t], RS, ph);
-    const std::vector<uint32_t> l = v.limbs(D4_S, LB);
+    const std::vector<uint32_t> l = v.limbs(S, LB);
     kf.insert(kf.end(), l.begin(), l.end());
   }
   return true;
@@ -1921,13 +1927,16 @@ static int setup_fbg(pai_ctx* c, const HBig& p, const HBig& q) {
   c->fb_p = p;
   c->fb_q = q;
   c->fbg_ok = true;
-  // split-pair decryption (kernels_dec4.hpp): p_h of at most 28 * 74 - 24 bits (R >= 2^24 p_h), the ciphertext
-  // in at most 4 chunks of 74 limbs; $FLEXPAI_PAIR=0 keeps the group engine's k_decrypt
+  // split-pair decryption (kernels_dec4.hpp) over the S = split_s limbs of p_h: at 74, p_h of at most 28 * 74 - 24
+  // bits (R >= 2^24 p_h); at 56, setup_crt's pair bound (R >= 2^12 p_h: the bounds in kernels_dec4.hpp). The
+  // ciphertext in at most 4 chunks of S limbs (ceil(32 ct_words / (28 S)): 4 across either band);
+  // $FLEXPAI_PAIR=0 keeps the group engine's k_decrypt
   bool pair = true;
   if (const char* e = xcheck_env("FLEXPAI_PAIR")) pair = atoi(e) != 0;
-  const size_t RS = (size_t)LB * D4_S;
+  const int S = c->split_s;
+  const size_t RS = (size_t)LB * S;
   const int kp = (int)((32 * (size_t)c->ct_words + RS - 1) / RS);
-  if (pair && pb + 24 <= RS && kp <= 4 && c->tpi_d == 4) {
+  if (pair && pb + (S == D4_S ? 24 : 12) <= RS && kp <= 4 && c->tpi_d == 4) {
     const HBig primes[2] = {p, q};
     Dec4Half dh[2];
     for (int h = 0; h < 2; ++h) {
@@ -1937,16 +1946,16 @@ static int setup_fbg(pai_ctx* c, const HBig& p, const HBig& q) {
         return mod(sub(add(ph, HBig(1)), r), ph);
       };
       std::vector<uint32_t> pd, kf;
-      if (!build_dec4f_program(ph, RS, pd, kf)) return 0;
+      if (!build_dec4f_program(ph, S, pd, kf)) return 0;
       HBig oi = inv_mod(mod(primes[1 - h], ph), ph);
       if (oi.is_zero()) return 0;
       const HBig hh = sub(ph, oi);
       uint32_t *dp, *dx1, *dxk, *dck, *dhr, *dprog, *dkf;
-      if ((rc = upload(c, ph.limbs(D4_S, LB), &dp)) ||
-          (rc = upload(c, one_minus(mul_pow2_mod(HBig(1), RS, ph)).limbs(D4_S, LB), &dx1)) ||
-          (rc = upload(c, one_minus(mul_pow2_mod(HBig(1), RS * kp, ph)).limbs(D4_S, LB), &dxk)) ||
-          (rc = upload(c, pair_split(mul_pow2_mod(HBig(1), RS * (kp + 1), m2), ph, D4_S), &dck)) ||
-          (rc = upload(c, mul_pow2_mod(hh, RS, ph).limbs(D4_S, LB), &dhr)) || (rc = upload(c, pd, &dprog)) ||
+      if ((rc = upload(c, ph.limbs(S, LB), &dp)) ||
+          (rc = upload(c, one_minus(mul_pow2_mod(HBig(1), RS, ph)).limbs(S, LB), &dx1)) ||
+          (rc = upload(c, one_minus(mul_pow2_mod(HBig(1), RS * kp, ph)).limbs(S, LB), &dxk)) ||
+          (rc = upload(c, pair_split(mul_pow2_mod(HBig(1), RS * (kp + 1), m2), ph, S), &dck)) ||
+          (rc = upload(c, mul_pow2_mod(hh, RS, ph).limbs(S, LB), &dhr)) || (rc = upload(c, pd, &dprog)) ||
           (rc = upload(c, kf, &dkf)))
         return rc;
       dh[h] = Dec4Half{dp, dx1, dxk, dck, dhr, dprog, (int)pd.size(), mont_prime(ph, LB), dkf};
@@ -1959,14 +1968,18 @@ static int setup_fbg(pai_ctx* c, const HBig& p, const HBig& q) {
   return 0;
 }
 
-// A 4096-bit key's constants for the row kernels (kernels_crtw.hpp; the lane CRT kernels stop at 2048 bits): per
-// half, stage A over the 74 limbs of p_h (R^(K+1) mod p_h, the op list over q_h mod (p_h - 1)), stage B over the 148
-// limbs of p_h^2 (R^2, coef, the op list over p_h) and decryption (R^(K+1) mod p_h^2, the op list over p_h - 1); the
-// finish reuses setup_fbg's q^2 R^2 / p^2 R^2 mod n^2 and the k_dec4 halves. Soft: an unusable key leaves rows_sa = 0.
+// A 2049..4096-bit key's constants for the row kernels (kernels_crtw.hpp; the lane CRT kernels stop at 2048 bits): per
+// half, stage A over the SA limbs of p_h (R^(K+1) mod p_h, the op list over q_h mod (p_h - 1)), stage B over the SB =
+// 2 SA limbs of p_h^2 (R^2, coef, the op list over p_h) and decryption (R^(K+1) mod p_h^2, the op list over p_h - 1); the
+// finish reuses setup_fbg's q^2 R^2 / p^2 R^2 mod n^2 and the k_dec4 halves. SA = split_s: 74, or 56 in the 3072-bit
+// band (k_crt_w<56, 112> and k_dec_w<56, 112> instantiate as the other widths do, 4 and 8 limbs per lane of a row; 28 SB
+// >= 2 pb + 2 keeps R >= 4 p_h^2). Soft: an unusable key leaves rows_sa = 0.
 static int setup_rows4096(pai_ctx* c, const HBig& p, const HBig& q) {
-  constexpr int SA = 74, SB = 148;
+  const int SA = c->split_s, SB = 2 * SA;
   c->rows_sa = 0;
-  if (c->tpi_e != 8 || !c->d_kq || std::max(p.bits(), q.bits()) + 2 > (size_t)LB * SA) return 0;
+  if (c->tpi_e != 8 || !c->d_kq || std::max(p.bits(), q.bits()) + 2 > (size_t)LB * SA ||
+      2 * std::max(p.bits(), q.bits()) + 2 > (size_t)LB * SB)
+    return 0;
   const size_t RA = (size_t)LB * SA, RB = (size_t)LB * SB;
   const int kd = (int)((32 * (size_t)c->ct_words + RB - 1) / RB);
   if (kd > KMAX_CHUNKS) return 0;
@@ -2021,8 +2034,11 @@ static int setup_crt4(pai_ctx* c, const HBig& p, const HBig& q) {
 #if FLEXPAI_XCHECK
   return 0;
 #endif
-  const size_t RS = (size_t)LB * D4_S;
-  if (!c->fbg_ok || c->rows_sa != D4_S || !c->d_crt_a || c->tpi_e != 8 || std::max(p.bits(), q.bits()) + 24 > RS) return 0;
+  const int S = c->split_s;
+  const size_t RS = (size_t)LB * S;
+  if (!c->fbg_ok || c->rows_sa != S || !c->d_crt_a || c->tpi_e != 8 ||
+      std::max(p.bits(), q.bits()) + (S == D4_S ? 24 : 12) > RS)
+    return 0;
   SetupTrace tr("    crt4 consts");
   const HBig primes[2] = {p, q};
   const HBig sq[2] = {mul(p, p), mul(q, q)};
@@ -2035,11 +2051,11 @@ static int setup_crt4(pai_ctx* c, const HBig& p, const HBig& q) {
     const HBig coef = inv_mod(sq[1 - h], sq[h]);
     if (coef.is_zero()) return 0;
     const HBig cb = div_big(coef, ph), ca = sub(coef, mul(cb, ph));
-    std::vector<uint32_t> cpair = ca.limbs(D4_S, LB), b = cb.limbs(D4_S, LB);
+    std::vector<uint32_t> cpair = ca.limbs(S, LB), b = cb.limbs(S, LB);
     cpair.insert(cpair.end(), b.begin(), b.end());
     const HBig x1 = mod(sub(add(ph, HBig(1)), mul_pow2_mod(HBig(1), RS, ph)), ph);   // (1 - R) mod p_h
     uint32_t *dp, *dx1, *dcf, *dprog;
-    if ((rc = upload(c, ph.limbs(D4_S, LB), &dp)) || (rc = upload(c, x1.limbs(D4_S, LB), &dx1)) ||
+    if ((rc = upload(c, ph.limbs(S, LB), &dp)) || (rc = upload(c, x1.limbs(S, LB), &dx1)) ||
         (rc = upload(c, cpair, &dcf)) || (rc = upload(c, pb, &dprog)))
       return rc;
     hb[h] = Crt4Half{dp, dx1, dcf, dprog, (int)pb.size(), mont_prime(ph, LB)};
@@ -2063,6 +2079,9 @@ static int setup_crt(pai_ctx* c, const HBig& p, const HBig& q) {
     }
   }
   if (!sa) {   // too large for the lane engine: fixed-base on the group engine, protocol-sized calls on rows
+    // PAI_OPT_PRIME_LIMBS: the narrowest width that meets the pair bound 28 S >= pb + 12 and the rows' 28 (2 S) >=
+    // 2 pb + 2 -- 56 limbs for a larger prime of at most 1556 bits, else 74 (19 and 37 are the loop's above)
+    c->split_s = (c->prime_limbs_opt && (size_t)LB * D4_S3 >= pb + 12 && (size_t)LB * 2 * D4_S3 >= 2 * pb + 2) ? D4_S3 : D4_S;
     int rc0 = setup_fbg(c, p, q);
     if (!rc0) rc0 = setup_rows4096(c, p, q);
     return rc0 ? rc0 : setup_crt4(c, p, q);
@@ -2229,6 +2248,7 @@ int pai_ctx_set_private(pai_ctx* c, const uint8_t* p_le, const uint8_t* q_le, si
     c->d_decw = nullptr;
     c->decw_kchunks = 0;
     c->rows_sa = 0;
+    c->split_s = D4_S;
     c->fb_state = pai_ctx::FB_UNTRIED;
     g_last_error = msg;
   }
@@ -2310,6 +2330,11 @@ int pai_ctx_set_option(pai_ctx* c, int option, int value) {
       if (value < 0) return fail(PAI_ERR_ARG, "PAI_OPT_CRT4_MIN must be >= 0");
       c->crt4_min = value;
       return 0;
+    case PAI_OPT_PRIME_LIMBS:
+      if (value != 0 && value != 1) return fail(PAI_ERR_ARG, "PAI_OPT_PRIME_LIMBS must be 0 or 1");
+      if (c->has_priv) return fail(PAI_ERR_ARG, "PAI_OPT_PRIME_LIMBS must be set before pai_ctx_set_private");
+      c->prime_limbs_opt = value != 0;
+      return 0;
     case PAI_OPT_MATMUL_FUSED: c->mm_fused = value != 0; return 0;
     case PAI_OPT_MATMUL_BUCKET: c->mm_bucket = value != 0; return 0;
     case PAI_OPT_MUL_BCAST:
@@ -2373,6 +2398,7 @@ int pai_ctx_get_option(const pai_ctx* c, int option, int* value) {
     case PAI_OPT_CRT_AVAILABLE: *value = c->crt_ok ? 1 : 0; return 0;
     case PAI_OPT_ROWS_MAX: *value = (int)std::min<long long>(c->crtw_max, INT32_MAX); return 0;
     case PAI_OPT_CRT4_MIN: *value = (int)std::min<long long>(c->crt4_min, INT32_MAX); return 0;
+    case PAI_OPT_PRIME_LIMBS: *value = (c->split_s == D4_S3 && (c->dec4_ok || c->crt4_ok)) ? D4_S3 : 0; return 0;
     case PAI_OPT_MATMUL_FUSED: *value = c->mm_fused ? 1 : 0; return 0;
     case PAI_OPT_MATMUL_BUCKET: *value = c->mm_bucket ? 1 : 0; return 0;
     case PAI_OPT_MUL_BCAST: *value = c->mulb_mode; return 0;
@@ -3501,7 +3527,7 @@ static int launch_crt(pai_ctx* c, const EncParams& e, bool rows, hipStream_t st)
 // 466 MB per chunk; CRT_CHUNK's 4 M would make it 7.4 GB). Stage times: stage A, stage B, finish, summed over chunks.
 constexpr long long CRT4_CHUNK = 1ll << 18;
 static int launch_crt4(pai_ctx* c, const EncParams& e, hipStream_t st) {
-  constexpr int S = D4_S;
+  const int S = c->split_s;
   const long long N = e.n;
   const int r_words = enc_r_words(e);
   const int kchunks = (32 * r_words + LB * S - 1) / (LB * S);
@@ -3509,7 +3535,7 @@ static int launch_crt4(pai_ctx* c, const EncParams& e, hipStream_t st) {
     return fail(PAI_ERR_ARG, "CRT encrypt: obfuscator too wide");
   const long long chunk = std::min(N, CRT4_CHUNK);
   Crt4Geom g;
-  crt4_geometry(c->cus, chunk, &g);
+  if (crt4_geometry(S, c->cus, chunk, &g)) return fail(PAI_ERR_KEY, "CRT encrypt: unsupported width");
   int rc = ensure_scratch(c, g.scratch_bytes);
   if (rc) return rc;
   const size_t ybytes = (size_t)2 * S * 4;   // per element
@@ -3528,10 +3554,10 @@ static int launch_crt4(pai_ctx* c, const EncParams& e, hipStream_t st) {
     p.u = u;
     p.scratch = (uint32_t*)c->d_scratch;
     stage_mark(c, 0, st);
-    HIPCHK(crt4_launch_a(p, g, st));
+    HIPCHK(crt4_launch_a(S, p, g, st));
     HIPCHK(hipGetLastError());
     stage_mark(c, 1, st);
-    HIPCHK(crt4_launch_b(p, g, st));
+    HIPCHK(crt4_launch_b(S, p, g, st));
     HIPCHK(hipGetLastError());
     stage_mark(c, 2, st);
     if ((rc = crt_finish(c, e, u, 2 * S, off, n, st))) return rc;
@@ -4115,13 +4141,14 @@ static int launch_dec_pair(pai_ctx* c, const DecParams& d, hipStream_t st) {
 }
 
 // 4096-bit split-pair decryption (kernels_dec4.hpp, engine_dec4.hip), in chunks of CRT_CHUNK elements
-// A 4096-bit call of at most crtw_max ciphertexts: c^(p_h - 1) mod p_h^2 on rows (k_dec_w<74, 148>) into the pairs
+// A 2049..4096-bit key's call of at most crtw_max ciphertexts: c^(p_h - 1) mod p_h^2 on rows (k_dec_w<S, 2 S>) into the pairs
 // k_dec4_L takes, then k_dec4_L and k_dec4_fin; stage times: k_dec_w, k_dec4_L + k_dec4_fin.
 static int launch_decw4(pai_ctx* c, const DecParams& d, hipStream_t st) {
   const long long N = d.n;
+  const int S = c->split_s;
   Dec4Geom g;
-  dec4_geometry(c->cus, N, &g);
-  const size_t xbytes = (size_t)2 * 2 * D4_S * 4, mbytes = (size_t)2 * D4_S * 4;   // per element
+  if (dec4_geometry(S, c->cus, N, &g)) return fail(PAI_ERR_KEY, "decrypt: unsupported width");
+  const size_t xbytes = (size_t)2 * 2 * S * 4, mbytes = (size_t)2 * D4_S * 4;   // per element (m_h: k_dec4_fin's layout)
   int rc = ensure_work(c, (xbytes + mbytes) * N);
   if (rc) return rc;
   Dec4Params p{};
@@ -4137,7 +4164,7 @@ static int launch_decw4(pai_ctx* c, const DecParams& d, hipStream_t st) {
   stage_mark(c, 0, st);
   HIPCHK(decw_launch(c->rows_sa, w, st));
   stage_mark(c, 1, st);
-  HIPCHK(dec4_launch_tail(p, d, g, st));
+  HIPCHK(dec4_launch_tail(S, p, d, g, st));
   stage_mark(c, 2, st);
   return 0;
 }
@@ -4146,11 +4173,12 @@ static int launch_dec4(pai_ctx* c, const DecParams& d, hipStream_t st) {
   const long long N = d.n;
   if (N <= c->crtw_max && c->rows_sa && c->d_decw) return launch_decw4(c, d, st);
   const long long chunk = std::min(N, CRT_CHUNK);
+  const int S = c->split_s;
   Dec4Geom g;
-  dec4_geometry(c->cus, chunk, &g);
+  if (dec4_geometry(S, c->cus, chunk, &g)) return fail(PAI_ERR_KEY, "decrypt: unsupported width");
   int rc = ensure_scratch(c, g.scratch_bytes);
   if (rc) return rc;
-  const size_t xbytes = (size_t)2 * 2 * D4_S * 4, mbytes = (size_t)2 * D4_S * 4;   // per element
+  const size_t xbytes = (size_t)2 * 2 * S * 4, mbytes = (size_t)2 * D4_S * 4;   // per element (m_h: k_dec4_fin's layout)
   if ((rc = ensure_work(c, (xbytes + mbytes) * chunk))) return rc;
   for (long long off = 0; off < N; off += chunk) {
     const long long n = std::min(chunk, N - off);
@@ -4173,7 +4201,7 @@ static int launch_dec4(pai_ctx* c, const DecParams& d, hipStream_t st) {
     if (f.mant) f.mant += off;
     f.status += off;
     if (f.raw) f.raw += (size_t)off * c->pt_words;
-    HIPCHK(dec4_launch(p, f, g, st, ev));
+    HIPCHK(dec4_launch(S, p, f, g, st, ev));
   }
   return 0;
 }

@@ -1,6 +1,7 @@
 // CRT encryption for holders of a 2049..4096-bit private key above the row kernels' range: kernels_crt.hpp's
-// identity, r^n mod p_h^2 = (r^(q_h mod (p_h - 1)) mod p_h)^(p_h) mod p_h^2, over the S = 74 limbs of p_h, where
-// the lane kernels (k_crt_a, k_crt_b_pair) stop at 37. Same ciphertext bits as k_encrypt<8>.
+// identity, r^n mod p_h^2 = (r^(q_h mod (p_h - 1)) mod p_h)^(p_h) mod p_h^2, over the S = 74 limbs of p_h (56 for a
+// p_h of at most 1556 bits under PAI_OPT_PRIME_LIMBS: D4Cfg, kernels_dec4.hpp), where the lane kernels (k_crt_a,
+// k_crt_b_pair) stop at 37. Same ciphertext bits as k_encrypt<8>.
 //
 //   k_crt4_pre stage A, one element-half per lane: r R mod p_h by K CIOS passes over r's S-limb chunks against
 //              R^(K+1) mod p_h (setup_rows4096's stage-A half)
@@ -18,7 +19,13 @@
 
 namespace fpai {
 
-constexpr int C4_ROW = D4_S + 1;   // LDS words of a stage-A lane's multiplier row (odd stride: conflict-free reads)
+// LDS words of a stage-A lane's multiplier row: S + 1, an odd stride at both widths (75, 57), so the 64 lanes of a
+// wave read digit j of their rows from 64 different banks
+template <int S>
+constexpr int c4_row() {
+  static_assert(S % 2 == 0, "S + 1 must be odd");
+  return S + 1;
+}
 
 struct Crt4Half {          // stage B
   const uint32_t* p;       // p_h, S limbs
@@ -41,14 +48,10 @@ struct Crt4Params {
 };
 
 // ---------------------------------------------------------------- stage A
-// waves per SIMD the two chains are built for (measurement builds: tools/crt4_ab.py --lib). At two waves both spill to
-// scratch (k_crt4_a 144 B, k_crt4_b 700 B per lane) and measured slower (stage B 1 657 -> 2 405 ms per 262 144 elements)
-#ifndef FPAI_CRT4_OCC_A
-#define FPAI_CRT4_OCC_A 1
-#endif
-#ifndef FPAI_CRT4_OCC_B
-#define FPAI_CRT4_OCC_B 1
-#endif
+// waves per SIMD the two chains are built for: D4Cfg<S>::OCC_A / OCC_B (kernels_dec4.hpp). At 74 limbs one
+// (FPAI_CRT4_OCC_A / _B; measurement builds: tools/crt4_ab.py --lib): at two waves both spill to scratch (k_crt4_a
+// 144 B, k_crt4_b 700 B per lane) and measured slower (stage B 1 657 -> 2 405 ms per 262 144 elements). At 56 limbs
+// two: k_crt4_a<56> needs 219 VGPRs and no scratch, k_crt4_b<56> spills 51 VGPRs (208 B) outside the digit passes.
 // (an opaque copy of the lane index: LICM would otherwise hoist the quad addresses of a constant tile out of the
 // element loop and keep them live across the products; kernels_pe4.hpp)
 __device__ __forceinline__ LaneScratch c4_opaque(const LaneScratch& t) {
@@ -62,6 +65,7 @@ __device__ __forceinline__ LaneScratch c4_opaque(const LaneScratch& t) {
 template <int S>
 __global__ __launch_bounds__(LANE_BLOCK, 1) void k_crt4_pre(Crt4Params p) {
   constexpr int TQ = tile_quads<S>();
+  constexpr int C4_ROW = c4_row<S>();
   __shared__ uint32_t lds[LANE_BLOCK * C4_ROW];
   const int half = blockIdx.y;
   const CrtHalf* H = p.ha + half;
@@ -128,8 +132,9 @@ __global__ __launch_bounds__(LANE_BLOCK, 1) void k_crt4_pre(Crt4Params p) {
 // y_h R = (r R)^(e_h) mod p_h in place over p.y: the lane machine (kernels_crt.hpp's op list) without the closing
 // product, so y_h stays in Montgomery form
 template <int S>
-__global__ __launch_bounds__(LANE_BLOCK, FPAI_CRT4_OCC_A) void k_crt4_a(Crt4Params p) {
+__global__ __launch_bounds__(LANE_BLOCK, D4Cfg<S>::OCC_A) void k_crt4_a(Crt4Params p) {
   constexpr int TQ = tile_quads<S>();
+  constexpr int C4_ROW = c4_row<S>();
   using Q = std::make_integer_sequence<int, TQ>;
   __shared__ uint32_t lds[LANE_BLOCK * C4_ROW];
   const int half = blockIdx.y;
@@ -202,10 +207,11 @@ __device__ __forceinline__ void c4_wide(uint64_t (&P)[S], const uint32_t (&m)[S]
 }
 
 template <int S>
-__global__ __launch_bounds__(LANE_BLOCK, FPAI_CRT4_OCC_B) void k_crt4_b(Crt4Params p) {
+__global__ __launch_bounds__(LANE_BLOCK, D4Cfg<S>::OCC_B) void k_crt4_b(Crt4Params p) {
   constexpr int TQ = tile_quads<S>();
+  constexpr int RSLOT = D4Cfg<S>::RSLOT;
   using Q = std::make_integer_sequence<int, TQ>;
-  __shared__ uint32_t lds[D4_PAIRS * D4R_SLOT + S];
+  __shared__ uint32_t lds[D4_PAIRS * RSLOT + S];
   const int half = blockIdx.y;
   const Crt4Half* H = p.hb + half;
   uint32_t m[S];
@@ -215,13 +221,13 @@ __global__ __launch_bounds__(LANE_BLOCK, FPAI_CRT4_OCC_B) void k_crt4_b(Crt4Para
   const int nprog = H->nprog;
   const uint32_t* prog = H->prog;
   const uint32_t* cf = H->coef;
-  uint32_t* x1 = lds + D4_PAIRS * D4R_SLOT;   // (1 - R) mod p_h: the odd row's start in squares
+  uint32_t* x1 = lds + D4_PAIRS * RSLOT;      // (1 - R) mod p_h: the odd row's start in squares
   for (int i = threadIdx.x; i < S; i += blockDim.x) x1[i] = H->X1[i];
   __syncthreads();
   const int tig = threadIdx.x & 1;
   const bool odd = tig != 0;
   const int pib = threadIdx.x >> 1;
-  uint32_t* st = lds + pib * D4R_SLOT;
+  uint32_t* st = lds + pib * RSLOT;
   const LaneScratch tl = lane_scratch(p.scratch);
   for (long long base = (long long)blockIdx.x * D4_PAIRS; base < p.n; base += (long long)gridDim.x * D4_PAIRS) {
     const long long e = base + pib;

@@ -1,4 +1,5 @@
-// CRT decryption for 4096-bit keys on p-adic pairs split over a lane pair (bn_pair.hpp's algebra).
+// CRT decryption for 4096-bit keys on p-adic pairs split over a lane pair (bn_pair.hpp's algebra). The same kernels
+// at S = 56 serve a p_h of at most 1556 bits (the 3072-bit keys) under PAI_OPT_PRIME_LIMBS: D4Cfg, below.
 //
 // p_h has 2048 bits, S = 74 limbs: a pair (A, B) with v = A + p_h B (mod p_h^2) and its two CIOS rows
 // (2 x 74 64-bit accumulators) do not fit one lane next to the operand, so the rows go to the two lanes of a
@@ -27,9 +28,77 @@
 
 namespace fpai {
 
-constexpr int D4_S = 74;                     // limbs of p_h
+constexpr int D4_S = 74;                     // limbs of a 2048-bit p_h (and of n in kernels_pe.hpp)
+constexpr int D4_S3 = 56;                    // limbs of a p_h of at most 1556 bits: the 3072-bit band (below)
 constexpr int D4_PAIRS = LANE_BLOCK / 2;     // element-halves per block
-constexpr int D4_SLOT = 4 * D4_S;            // LDS words per element-half: x [A][B], t [A][B]
+
+// What is decided per width S of the split-pair machine (this file and kernels_crt4.hpp): the LDS words per
+// element-half and the waves per SIMD each chain is built for.
+//
+// S = 74 (p_h of at most 2048 bits, R = 2^2072): the slots are the bare rows (4 S for k_dec4_pre's ciphertext chunks,
+// 2 S for the chains' multiplier [A][B]); k_dec4_pow at two waves, stage A and stage B of the CRT at one (at two
+// they spill, kernels_crt4.hpp).
+//
+// S = 56 (p_h of 1036..1556 bits, R = 2^1568; PAI_OPT_PRIME_LIMBS). Bounds, re-derived for this width:
+//   * operands of every pass are below 4 p_h (d4r_run's B' = REDC(..) + REDC(..); everything else below 2 p_h), so a
+//     pass leaves (4 p_h)^2 / R + p_h < 2 p_h as soon as R >= 16 p_h, and the closing sums (G + delta, B + 1) stay
+//     below 5 p_h < R. The context asks for 28 S >= pb + 12, the pair bound of the 19- and 37-limb kernels: pb <=
+//     1556. (The 74-limb family asks for 24 spare bits because 2072 - 2048 gives them; it needs no more than these.)
+//   * a column of the 64-bit accumulator row takes, per digit step, one product a_i y < 2^56 (2^57 in the odd lane's
+//     square, y = 2 A_j) and one q m_i < 2^56, for S steps before it retires, plus a carry below 2^36:
+//     56 (2^57 + 2^56) + 2^36 < 2^63.4 < 2^64 (74: 2^63.8).
+//   * lane::mont_sqr's triangle in stage A: S 1.5 2^57 + 2^36 < 2^64 (bn_lane.hpp) holds a fortiori.
+// Layout: a lane pair reads its multiplier one digit per step, every pair at the same offset of its own slot, so the
+// bank of pair k is k SLOT mod the bank count. The bare 2 S = 112 words (16 mod 32, 48 mod 64) would put all the
+// pairs of a wave on 2 banks of 32, or 4 of 64: every digit read serialised 8 ways. (148 = 20 mod 32 spreads the
+// 74-limb pairs over 8 or 16 banks.) Two words of padding make the stride 114 = 18 mod 32 = 50 mod 64, gcd 2: the 16
+// pairs of a half-wave, and the 32 of a wave, all on different banks. k_dec4_pre's slot is padded the same way
+// (4 S + 2 = 226). 56 limbs are 14 whole quads, so the tile moves (d4_tile_*, d4r_tile_*) are full 16-byte quads with
+// no zero-filled remainder (the bounds checks in them are compile-time and vanish); their LDS side stays word stores
+// (the padded stride is not a multiple of 16 bytes, and a tile moves once per product against 2 S digit reads).
+// Work split: both lanes of a pair run one instruction stream, so a square costs the odd lane's full 2AB row plus
+// its reduction (2 S^2) whatever the even lane does; cutting the even lane's A^2 to its triangle would shorten no
+// instruction, and it is not done at 56 either. What the width buys besides the S^2 is the register budget: a, m and
+// the 64-bit row are 4 S = 224 VGPRs (296 at 74). Built for two waves per SIMD (256 VGPRs), the gfx950 code object
+// reports: k_crt4_a<56> 219 VGPRs, no scratch (74: AGPR copies at one wave, 144 B of scratch at two); k_dec4_pow<56>
+// 66 VGPRs spilled (268 B; 74: 134, 540 B) and k_crt4_b<56> 51 (208 B; 74: 700 B), and in both the disassembly has
+// every scratch access outside the digit passes -- per element before the op list and in the closing steps; in
+// k_crt4_b 14 of them per product, between its two passes. So all three chains run at two waves at this width; at one
+// wave the same code needs 66 / 50 AGPRs and no scratch (DESIGN.md section 3 has the table) and measured 1.12x
+// (encryption) and 1.13x (decryption) slower on 262 144 elements of a 3072-bit key (section 5).
+#ifndef FPAI_DEC4_OCC
+#define FPAI_DEC4_OCC 2   // waves per SIMD (measurement builds: tools/gpu/ab_dec4_occ_run.sh)
+#endif
+#ifndef FPAI_CRT4_OCC_A
+#define FPAI_CRT4_OCC_A 1
+#endif
+#ifndef FPAI_CRT4_OCC_B
+#define FPAI_CRT4_OCC_B 1
+#endif
+#ifndef FPAI_D56_OCC_POW
+#define FPAI_D56_OCC_POW 2
+#endif
+#ifndef FPAI_D56_OCC_A
+#define FPAI_D56_OCC_A 2
+#endif
+#ifndef FPAI_D56_OCC_B
+#define FPAI_D56_OCC_B 2
+#endif
+template <int S>
+struct D4Cfg;
+template <>
+struct D4Cfg<D4_S> {
+  static constexpr int SLOT = 4 * D4_S;    // k_dec4_pre: x [A][B], t [A][B] (the ciphertext's chunks)
+  static constexpr int RSLOT = 2 * D4_S;   // the chains: the multiplier [A][B]
+  static constexpr int OCC_POW = FPAI_DEC4_OCC, OCC_A = FPAI_CRT4_OCC_A, OCC_B = FPAI_CRT4_OCC_B;
+};
+template <>
+struct D4Cfg<D4_S3> {
+  static constexpr int SLOT = 4 * D4_S3 + 2;
+  static constexpr int RSLOT = 2 * D4_S3 + 2;
+  static constexpr int OCC_POW = FPAI_D56_OCC_POW, OCC_A = FPAI_D56_OCC_A, OCC_B = FPAI_D56_OCC_B;
+};
+constexpr int D4_SLOT = D4Cfg<D4_S>::SLOT;   // kernels_pe.hpp
 
 struct Dec4Half {
   const uint32_t* p;       // p_h, S limbs
@@ -50,7 +119,7 @@ struct Dec4Params {
   int ct_words;
   int kchunks;
   uint32_t* x;             // [2][2S][n]: pairs (A: limbs 0..S-1, B: S..2S-1)
-  uint32_t* mh;            // [2][S][n]
+  uint32_t* mh;            // [2][D4_S][n] whatever S (k_dec4_fin's layout; limbs S.. are zero)
   uint32_t* scratch;       // per-lane tiles (LaneScratch, tile_quads<S> quads per tile)
 };
 
@@ -87,7 +156,8 @@ __device__ __forceinline__ void d4_fence() { wave_lds_fence(); }
 // in LDS), R^-K: one split CIOS, the odd row started at (1 - R^K) mod p_h.
 template <int S>
 __global__ __launch_bounds__(LANE_BLOCK, 1) void k_dec4_pre(Dec4Params p) {
-  __shared__ uint32_t lds[D4_PAIRS * D4_SLOT];
+  constexpr int SLOT = D4Cfg<S>::SLOT;
+  __shared__ uint32_t lds[D4_PAIRS * SLOT];
   const int half = blockIdx.y;
   const Dec4Half* H = p.halves + half;
   uint32_t m[S];
@@ -97,7 +167,7 @@ __global__ __launch_bounds__(LANE_BLOCK, 1) void k_dec4_pre(Dec4Params p) {
   const int tig = threadIdx.x & 1;
   const bool odd = tig != 0;
   const int pib = threadIdx.x >> 1;
-  uint32_t* sx = lds + pib * D4_SLOT;
+  uint32_t* sx = lds + pib * SLOT;
   for (long long base = (long long)blockIdx.x * D4_PAIRS; base < p.n; base += (long long)gridDim.x * D4_PAIRS) {
     const long long e = base + pib;
     const bool valid = e < p.n;
@@ -166,10 +236,13 @@ __device__ __forceinline__ void d4_tile_load(const LaneScratch& t, int k, uint32
 // Only the multiplier lives in LDS (2S words per lane pair instead of 4S): two blocks of 256 lanes per CU, two
 // waves per SIMD. A multiplier kept across products (LOP_B_READY without a prefetch: the table's x~^2) has its B
 // half clobbered by z: LOP_B_SET also stores it in a spare tile, reloaded before each later product that keeps it.
-constexpr int D4R_SLOT = 2 * D4_S;       // LDS words per element-half: the multiplier [A][B]
+constexpr int D4R_SLOT = D4Cfg<D4_S>::RSLOT;   // LDS words per element-half: the multiplier [A][B] (kernels_pe.hpp)
 constexpr int D4R_KEPT = LANE_NTILE;     // spare tile (in the lane scratch's stage-A buffer, unused here)
-static_assert((LANE_NTILE + 1) * tile_quads<D4_S>() <= LANE_NTILE * tile_quads<D4_S>() + RBUF_WORDS / 4,
-              "the spare tile fits the lane scratch");
+// k spare tiles after the op list's fit the lane scratch (they take the stage-A staging's place)
+template <int S>
+constexpr bool d4_spare_fits(int k) {
+  return (LANE_NTILE + k) * tile_quads<S>() <= LANE_NTILE * tile_quads<S>() + RBUF_WORDS / 4;
+}
 
 template <int S, int J>
 __device__ __forceinline__ void d4r_sqr_step(uint64_t (&P)[S], const uint32_t (&a)[S], int tig, const uint32_t (&m)[S],
@@ -217,6 +290,7 @@ __device__ __forceinline__ void d4r_run(uint32_t (&a)[S], uint32_t* st, const La
                                         int nprog, const uint32_t* x1, const uint32_t (&m)[S], uint32_t mprime, int tig,
                                         FinalB&& final_b) {
   constexpr int TQ = tile_quads<S>();
+  static_assert(d4_spare_fits<S>(1), "the spare tile fits the lane scratch");
   using Q = std::make_integer_sequence<int, TQ>;
   const bool odd = tig != 0;
   const uint32_t oddmask = odd ? 0xFFFFFFFFu : 0u;
@@ -301,8 +375,6 @@ __device__ __forceinline__ void d4r_run(uint32_t (&a)[S], uint32_t* st, const La
 constexpr int D4F_G = LANE_NTILE;         // spare tile: the pair (1 + p G)
 constexpr int D4F_ACC = LANE_NTILE + 1;   // spare tile: the Horner accumulator
 constexpr int D4F_HORNER = 2 * LANE_NTILE + 2;   // passes after the chain: w, 16 x (c_j, acc), delta
-static_assert((LANE_NTILE + 2) * tile_quads<D4_S>() <= LANE_NTILE * tile_quads<D4_S>() + RBUF_WORDS / 4,
-              "the two spare tiles fit the lane scratch");
 
 // the even lane's component of tile k -> LDS row dst (the odd lane's copy is not needed: B-free multipliers)
 template <int S, int... Gs>
@@ -337,6 +409,7 @@ __device__ __forceinline__ void d4f_run(uint32_t (&a)[S], uint32_t* st, uint32_t
                                         const uint32_t* x1, const uint32_t (&m)[S], uint32_t mprime, int tig,
                                         const PefIn& pe = PefIn{}) {
   constexpr int TQ = tile_quads<S>();
+  static_assert(d4_spare_fits<S>(2), "the two spare tiles fit the lane scratch");
   using Q = std::make_integer_sequence<int, TQ>;
   const bool odd = tig != 0;
   if constexpr (PE) {   // (A_r, B_r) -> (A_r, 0): the base's B part does not change x^n mod n^2
@@ -507,13 +580,11 @@ __device__ __forceinline__ void d4f_run(uint32_t (&a)[S], uint32_t* st, uint32_t
 }
 
 template <int S>
-#ifndef FPAI_DEC4_OCC
-#define FPAI_DEC4_OCC 2   // waves per SIMD (measurement builds: tools/gpu/ab_dec4_occ_run.sh)
-#endif
-__global__ __launch_bounds__(LANE_BLOCK, FPAI_DEC4_OCC) void k_dec4_pow(Dec4Params p) {
+__global__ __launch_bounds__(LANE_BLOCK, D4Cfg<S>::OCC_POW) void k_dec4_pow(Dec4Params p) {
   constexpr int TQ = tile_quads<S>();
+  constexpr int RSLOT = D4Cfg<S>::RSLOT;
   using Q = std::make_integer_sequence<int, TQ>;
-  __shared__ uint32_t lds[D4_PAIRS * D4R_SLOT + 2 * S];
+  __shared__ uint32_t lds[D4_PAIRS * RSLOT + 2 * S];
   const int half = blockIdx.y;
   const Dec4Half* H = p.halves + half;
   uint32_t m[S];
@@ -523,13 +594,13 @@ __global__ __launch_bounds__(LANE_BLOCK, FPAI_DEC4_OCC) void k_dec4_pow(Dec4Para
   const int nprog = H->nprog;
   const uint32_t* prog = H->prog;
   const uint32_t* kf = H->kf;
-  uint32_t* x1 = lds + D4_PAIRS * D4R_SLOT;   // (1 - R) mod p_h: the odd row's start in squares (LDS: no SGPRs)
+  uint32_t* x1 = lds + D4_PAIRS * RSLOT;      // (1 - R) mod p_h: the odd row's start in squares (LDS: no SGPRs)
   uint32_t* kb = x1 + S;                       // K'_t of the current Horner step (block-wide)
   for (int i = threadIdx.x; i < S; i += blockDim.x) x1[i] = H->X1[i];
   __syncthreads();
   const int tig = threadIdx.x & 1;
   const int pib = threadIdx.x >> 1;
-  uint32_t* st = lds + pib * D4R_SLOT;
+  uint32_t* st = lds + pib * RSLOT;
   const LaneScratch tl = lane_scratch(p.scratch);
   for (long long base = (long long)blockIdx.x * D4_PAIRS; base < p.n; base += (long long)gridDim.x * D4_PAIRS) {
     const long long e = base + pib;
@@ -596,11 +667,15 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_dec4_L(Dec4Params p) {
     lane::normalize<S>(P, b);
     lane::cond_sub<S>(b, m);
 #pragma unroll
-    for (int i = 0; i < S; ++i) p.mh[((size_t)half * S + i) * p.n + e] = b[i];
+    for (int i = 0; i < S; ++i) p.mh[((size_t)half * D4_S + i) * p.n + e] = b[i];
+    if constexpr (S < D4_S) {   // k_dec4_fin reads D4_S limbs of m_h
+#pragma unroll
+      for (int i = S; i < D4_S; ++i) p.mh[((size_t)half * D4_S + i) * p.n + e] = 0u;
+    }
   }
 }
 
-// CRT + decode from m_p, m_q ([2][74][n]) on a lane group of TPI = 4 (S = 148), k_decrypt's steps 8-9
+// CRT + decode from m_p, m_q ([2][D4_S][n], whatever width k_dec4_L ran at) on a lane group of TPI = 4 (S = 148), k_decrypt's steps 8-9
 template <int TPI>
 __global__ __launch_bounds__(BLOCK) void k_dec4_fin(DecParams p, const uint32_t* __restrict__ mh) {
   constexpr int S = TPI * L;

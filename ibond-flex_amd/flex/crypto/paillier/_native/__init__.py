@@ -43,6 +43,7 @@ PAI_OPT_FOLD_ROWS, PAI_OPT_FOLD_PATH = 25, 26
 PAI_OPT_INV_DEVICE = 27
 PAI_OPT_MATMUL_BUCKET = 28
 PAI_OPT_MUL_BCAST, PAI_OPT_MUL_BCAST_PATH = 29, 30
+PAI_OPT_PRIME_LIMBS = 31
 PAI_SCAN_REVERSE = 1
 HIST_RUN = 64          # PAI_HIST_RUN: members of a histogram cell that one k_hist_acc instance sums
 PAI_OPT_PUBLIC_FB, PAI_OPT_PFB_READY, PAI_OPT_PFB_WINDOW = 10, 11, 12
@@ -468,6 +469,17 @@ def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
 
 
+_prime_limbs = False
+
+
+def set_prime_limbs(enabled: bool):
+    """Process-wide PAI_OPT_PRIME_LIMBS for the contexts created from now on (default off):
+    the key holders of the 3072-bit band get their kernels at 56 limbs, e.g. generate_paillier_encryptor_decryptor(3072).
+    Contexts that exist keep their width (Context.set_prime_limbs, before the private key, sets one context)."""
+    global _prime_limbs
+    _prime_limbs = bool(enabled)
+
+
 def int_to_le(v: int, nbytes: int) -> bytes:
     return int(v).to_bytes(nbytes, "little")
 
@@ -492,6 +504,8 @@ class Context:
         self.key_bits, self.ct_words, self.pt_words = kb.value, cw.value, pw.value
         self.has_private = False
         self.calls = collections.Counter()     # C-ABI entry points this context has run (tests, stats)
+        if _prime_limbs:
+            self.set_prime_limbs(True)
         if p is not None:
             self.set_private(p, q)
 
@@ -725,6 +739,17 @@ class Context:
         4096-bit one (k_pfb4) for a public-only n of 2049..4096 bits, which then engage past their break-even counts or
         once prepare_public_fixed_base() has built the tables (include/flexpai.h)."""
         self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_PUBLIC_FB, 2 if enabled == 2 else 1 if enabled else 0))
+
+    @property
+    def prime_limbs(self) -> int:
+        """56 when this key holder's split-pair CRT and decryption kernels run on the 56 limbs of a prime of at most
+        1556 bits (PAI_OPT_PRIME_LIMBS, include/flexpai.h), else 0."""
+        return int(self._get_option(PAI_OPT_PRIME_LIMBS))
+
+    def set_prime_limbs(self, enabled: bool):
+        """True: set_private chooses the narrowest limb count the primes fit (56 instead of 74 for the 3072-bit band).
+        Before set_private only; same ciphertexts and plaintexts either way. Process-wide: set_prime_limbs()."""
+        self._chk(self.lib.pai_ctx_set_option(self._h, PAI_OPT_PRIME_LIMBS, 1 if enabled else 0))
 
     @property
     def pfb_ready(self) -> bool:

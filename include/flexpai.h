@@ -158,7 +158,9 @@ typedef struct pai_comm pai_comm;
                                     the kernels they replace); bit 3 = this context holds a private key of
                                     2049..4096 bits and its encryption above the rows (more than PAI_OPT_ROWS_MAX and
                                     more than PAI_OPT_CRT4_MIN elements, explicit r or device RNG without resident
-                                    fixed-base tables) runs the split-pair CRT (kernels_crt4.hpp). A key holder's
+                                    fixed-base tables) runs the split-pair CRT (kernels_crt4.hpp). Bits 0 and 3 of such
+                                    a key are over 74 limbs of p_h, or over 56 for a larger prime of 1036..1556 bits
+                                    under PAI_OPT_PRIME_LIMBS = 1 (which reads back the width). A key holder's
                                     bit 2 stays 0 at 2049..4096 bits. Bit 2 says the constants are set up: of the
                                     1537..2048-bit keys only those of 128 ciphertext words (n of 2033..2048 bits)
                                     run k_pe_*, the others k_encrypt. The whole order: csrc/encrypt_route.hpp  */
@@ -259,6 +261,21 @@ typedef struct pai_comm pai_comm;
                                   * and the same PAI_ERR_NOINV either way. Any other value is PAI_ERR_ARG.          */
 #define PAI_OPT_MUL_BCAST_PATH 30 /* read-only: the path of this context's last pai_mul_bcast[_dev] call: 0 = none yet,
                                   * 1 = term path, 2 = comb                                                       */
+#define PAI_OPT_PRIME_LIMBS 31   /* 0 (default): a key holder of 2049..4096 bits runs its split-pair kernels and rows on
+                                  * the 74 limbs of a 2048-bit prime, whatever its primes' size. 1 (opt-in):
+                                  * pai_ctx_set_private chooses the narrowest limb count S of 28 bits that meets the
+                                  * pair bound 28 S >= pb + 12 and the rows' 28 (2 S) >= 2 pb + 2, pb the bits of the
+                                  * larger prime: 19 and 37 as before, 56 for 1036 <= pb <= 1556 (n of about
+                                  * 2072..3112 bits, the 3072-bit keys among them), 74 above. At 56 the decryption
+                                  * above the rows (k_dec4_*<56>: ceil(32 ct_words / (28 56)) = 4 ciphertext chunks),
+                                  * the CRT encryption above the rows (k_crt4_*<56>) and the rows (k_crt_w<56, 112>,
+                                  * k_dec_w<56, 112>: ceil(32 ct_words / (28 112)) = 2 chunks) do (56/74)^2 of the
+                                  * multiply-accumulates; the fixed-base sampler keeps its 74-limb tables and
+                                  * constants, and device-RNG calls with resident tables give the bits they give
+                                  * with 0. Same ciphertexts and plaintexts either way. It has to be set before
+                                  * pai_ctx_set_private: afterwards (and for a value other than 0 or 1) set returns
+                                  * PAI_ERR_ARG and nothing changes. Read back: 56 when this context's split-pair CRT
+                                  * and decryption kernels run on 56 limbs, else 0                               */
 /* The automatic choice of PAI_OPT_FOLD_ROWS: the largest output count at which the row kernel was more than 5 % faster
  * than the group kernel in the same-process A/B of tools/fold_ab.py on an MI355X (profiles/fold_ab.json),
  * per key size (n^2 of 74 / 148 / 296 limbs). 0: that key size stays on lane groups. Measured at 64, 1 024, 4 096, 16 384
